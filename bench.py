@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """Headline benchmark: HSM training images/sec of the CIFAR-10 PSLD NCSN++ (C10-SOTA) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run is the headline figure alone: set-up, W warm-up steps, the K timed steps, the outputs of the last step if
+--dump-outputs is given, the JSON line.  --full adds everything else the line can carry: the CPU baseline, the probed
+second pass (`roofline`), the measured sampling batches, the eval-forward block and the CelebA-64 block (the --no-* and
+--sample-* options switch parts of it off).
 
 `--gpus N` with N > 1 and no launcher in the environment (WORLD_SIZE unset) starts the N ranks itself: the parent
 spawns `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process before it has touched the
@@ -554,16 +559,49 @@ def wgrad_summary(probe, dt_pass):
     return out or None
 
 
+DUMP_SAMPLE = 1 << 22     # entries kept of each parameter-sized output: 3 x 16 MiB of float32
+
+
+def dump_outputs(dirname, loss, net, ema):
+    """What a caller of the training step holds after the last timed step, as float32 DIR/<name>.npy: the loss, and of the
+    updated parameters, their gradients and the EMA parameters (each flattened in parameters() order) a fixed sample of
+    DUMP_SAMPLE entries, the same sorted indices in every run (all entries when there are no more than that)."""
+    import numpy as np
+
+    def flat(tensors):
+        return torch.cat([t.detach().reshape(-1).float() for t in tensors])
+
+    params = list(net.parameters())
+    outs = {"loss": loss.detach().reshape(1).float(),
+            "params": flat(params),
+            "grads": flat(p.grad if p.grad is not None else torch.zeros_like(p) for p in params),
+            "ema_params": flat(ema.parameters())}
+    n = outs["params"].numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in outs.items():
+        assert name == "loss" or v.numel() == n, (name, v.numel(), n)
+        if idx is not None and name != "loss":
+            v = v[idx.to(v.device)]
+        np.save(os.path.join(dirname, name + ".npy"), v.cpu().numpy())
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=128, help="per-GPU batch")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline steps: CPU baseline, probed pass (roofline), sampling, forward and CelebA-64 blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left to its caller as DIR/<name>.npy (float32; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probe", action="store_true")
     ap.add_argument("--no-forward", action="store_true", help="skip the eval-forward block (kernel-stats profiles of the training steps only)")
-    ap.add_argument("--no-config-block", action="store_true", help="skip the CelebA-64 (BASELINE configs[3]) train-step block of the default run")
+    ap.add_argument("--no-config-block", action="store_true", help="skip the CelebA-64 (BASELINE configs[3]) train-step block of the --full run")
     ap.add_argument("--bucket-mb", type=int, default=64)
     ap.add_argument("--config", default="c10_sota", choices=["c10_sota", "celeba64_sota"],
                     help="c10_sota = BASELINE.json configs[0..2] (headline); celeba64_sota = configs[3] (extra data point)")
@@ -727,6 +765,10 @@ def main():
             dist.destroy_process_group()
         return 0
 
+    if not args.full:
+        # a plain run: the headline steps alone (the sampling run is gated on args.full where it is decided)
+        args.no_cpu_baseline = args.no_probe = args.no_forward = args.no_config_block = True
+
     # the CPU baseline runs FIRST, in a child process with its own thread pool pinned to physical cores, before this
     # process has touched the GPU; nothing else is running on the box while it is timed
     cpu_base = None
@@ -809,6 +851,8 @@ def main():
         reducer.stats()                                       # drop the warm-up steps' events
     # pass 1 = the headline: the product's step, no per-launch HIP-event brackets inside the timed region
     dt, last = timed_pass(args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, net, ema)
     # pass 2 = the same K steps with every 3x3 limb convolution bracketed by HIP events -> `roofline`
     dt_probed = None
     if not args.no_probe:
@@ -832,7 +876,7 @@ def main():
         in_sync = bool(lo.item() == hi.item())
 
     sampling = None
-    if args.sample_batch > 0 and args.config == "c10_sota":
+    if args.full and args.sample_batch > 0 and args.config == "c10_sota":
         # second half of the metric: EVERY rank samples one batch of its own shard at the same time (eval/sample.py:100-109)
         # and then the LAST, partial batch of that shard (50 000 / 8 = 6250 = 12 x 512 + 106 per GPU on 8 GPUs)
         shard = sampling_shard(rank, world, int(cfg.evaluation.seed), batch=args.sample_batch)
@@ -902,11 +946,11 @@ def main():
                                   "gradient_bytes_per_step": int(net.flat_grad().numel()) * 4,
                                   "shared_gpu_rehearsal": share_gpu}
             out["overlap"] = st if st is not None else {"note": "no collective ran"}
-        pmc, pmc_err = pmc_traffic_record()
-        hbm, hbm_err = hbm_in_situ_record()
-        if hbm is not None and (args.batch != hbm.get("batch", 128) or args.config != "c10_sota"):
-            hbm, hbm_err = None, f"the in-situ record was measured at C10-SOTA B={hbm.get('batch', 128)}, this run is {args.config} B={args.batch}"
         if ps is not None:
+            pmc, pmc_err = pmc_traffic_record()
+            hbm, hbm_err = hbm_in_situ_record()
+            if hbm is not None and (args.batch != hbm.get("batch", 128) or args.config != "c10_sota"):
+                hbm, hbm_err = None, f"the in-situ record was measured at C10-SOTA B={hbm.get('batch', 128)}, this run is {args.config} B={args.batch}"
             peak = PEAK_BF16_MFMA_TFLOPS / LIMB_PRODUCTS
             issued = ((pw["total_flop"] / 2.25 if pw else 0.0) + (pd["total_flop"] if pd else 0.0)) * LIMB_PRODUCTS / (ps["total_ms"] * 1e-3) / 1e12
             out["roofline"] = {
@@ -973,7 +1017,8 @@ def main():
             out["sampling"] = sampling
         out["cpu_baseline"] = cpu_base
         out["env"] = psld_env()
-        out["options"] = {"per_layer_reductions": bool(args.per_layer_reductions), "graphs": bool(args.graphs)}
+        out["options"] = {"per_layer_reductions": bool(args.per_layer_reductions), "graphs": bool(args.graphs),
+                          "full": bool(args.full)}
         import ctypes
         ctypes.CDLL(None).fflush(None)
         sys.stdout.flush()

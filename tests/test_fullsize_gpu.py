@@ -332,3 +332,31 @@ def test_team_groupnorm_backward_beside_a_resident_foreign_kernel():
         assert ops.gn_team_errors(DEV) == 0, "a team member timed out beside the resident kernel"
         assert torch.equal(got, ref), f"repetition {rep}: the gradient changed beside a resident foreign kernel"
     ops.check_device_errors(DEV)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline steps alone (no CPU baseline, no
+    probed pass, no sampling / forward / CelebA-64 blocks), ms_per_step of exactly K steps, and the last step's outputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from tests.conftest import ROOT
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "16", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["options"]["full"] is False
+    assert out["unit"] == "images/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert abs(out["value"] - 16 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    assert out["cpu_baseline"] is None and out["roofline"] is None and out["ms_per_step_probed_pass"] is None
+    assert not {"sampling", "forward", "celeba64"} & set(out)
+    total = 0
+    for name in ("loss", "params", "grads", "ema_params"):
+        a = np.load(out_dir / f"{name}.npy")
+        total += a.nbytes
+        assert a.dtype == np.float32 and np.isfinite(a).all(), name
+    assert float(np.load(out_dir / "loss.npy")[0]) == pytest.approx(out["final_loss"], rel=1e-6)
+    assert total <= 64e6

@@ -289,3 +289,39 @@ def test_bucket_timing_sources_and_missing_timing():
     red._prof.append(([Work(None)], (Ev(0.0), Ev(0.1))))
     st = red.stats()
     assert st["comm_ms_per_step"] is None and st["hidden_ms_per_step"] is None and abs(st["exposed_ms_per_step"] - 0.1) < 1e-12
+
+
+def test_bench_dump_outputs_is_a_fixed_float32_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the loss and the same sorted sample of the parameters, gradients and EMA parameters in every
+    run, float32, 64 MB at most in all at the real sample size."""
+    import copy
+
+    import numpy as np
+
+    import bench
+    assert 3 * bench.DUMP_SAMPLE * 4 + 4 <= 64e6
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(50, 40), torch.nn.Linear(40, 3))
+    ema = copy.deepcopy(net)
+    net[1].bias.requires_grad_(False)                    # no gradient: dumped as zeros
+    loss = net(torch.randn(8, 50)).square().mean()
+    loss.backward()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss, net, ema)
+    names = ["ema_params.npy", "grads.npy", "loss.npy", "params.npy"]
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).numpy()
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        b = np.load(tmp_path / "b" / n)
+        assert a[n].dtype == np.float32 and b.dtype == np.float32 and np.array_equal(a[n], b)
+    assert a["loss.npy"].shape == (1,) and a["loss.npy"][0] == loss.item()
+    assert a["params.npy"].shape == (1000,) and np.isin(a["params.npy"], flat).all()
+    assert np.array_equal(a["params.npy"], a["ema_params.npy"])
+    assert (a["grads.npy"] != 0).any()
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1 << 20)   # no more entries than the sample: all of them, in order
+    bench.dump_outputs(str(tmp_path / "c"), loss, net, ema)
+    assert np.array_equal(np.load(tmp_path / "c" / "params.npy"), flat)
+    g = np.load(tmp_path / "c" / "grads.npy")
+    assert (g[:-3] != 0).any() and (g[-3:] == 0).all()

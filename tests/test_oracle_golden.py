@@ -20,6 +20,14 @@ def rel_l2(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
+def equal_f64(a, b):
+    """float64 equality up to the last bits at the tensor's scale.  The goldens hold the rounding of the CPU they were
+    captured on; MKL and ATen take other vector code paths on other CPUs, which can round a product one float64 ulp
+    apart (a tensor of zeros still has to match exactly)."""
+    return a.dtype == b.dtype == torch.float64 and a.shape == b.shape and \
+        bool((a - b).abs().max() <= 4 * torch.finfo(torch.float64).eps * b.abs().max())
+
+
 def make_sde(nu=4.01, gamma=0.01, dm="lower"):
     return O.PSLDOracle(8.0, 8.0, nu, gamma, 0.04, 1e-9, dm)
 
@@ -47,17 +55,17 @@ def test_perturb_and_drift(golden):
     x0, eps, t = T(g["x0"]), T(g["eps"]), T(g["t"])
     u, mu, _ = sde.perturb_data(x0, torch.zeros_like(x0), 0, sde.mm_0, t, eps)
     assert u.dtype == torch.float64
-    assert torch.equal(u, T(g["u_hsm"])) and torch.equal(mu, T(g["mu_hsm"]))
+    assert equal_f64(u, T(g["u_hsm"])) and equal_f64(mu, T(g["mu_hsm"]))
     u, mu, _ = sde.perturb_data(x0, T(g["m0"]), 0, 0.0, T(g["t_dsm"]), eps)
-    assert torch.equal(u, T(g["u_dsm"])) and torch.equal(mu, T(g["mu_dsm"]))
+    assert equal_f64(u, T(g["u_dsm"])) and equal_f64(mu, T(g["mu_dsm"]))
     uu = T(g["u"])
     f, gg = sde.sde(uu, t)
-    assert torch.equal(f, T(g["f"])) and torch.equal(gg, T(g["g"]))
+    assert equal_f64(f, T(g["f"])) and equal_f64(gg, T(g["g"]))
     fake = lambda a, b: 0.1 * a + b.view(-1, 1, 1, 1)
     for pf, tag in ((False, ""), (True, "_pf")):
         fb, gb = sde.reverse_sde(uu, t, fake, probability_flow=pf)
         assert fb.dtype == torch.float64
-        assert torch.equal(fb, T(g["f_bar" + tag])) and torch.equal(gb, T(g["g_bar" + tag]))
+        assert equal_f64(fb, T(g["f_bar" + tag])) and equal_f64(gb, T(g["g_bar" + tag]))
     sc = sde.get_score(T(g["eps_score"]), 0, sde.mm_0, t)
     assert sc.dtype == torch.float32 and torch.equal(sc, T(g["score"]))
 
@@ -118,8 +126,15 @@ def test_attn_fwd_bwd(golden, name):
     assert rel_l2(y, T(g[f"{name}.y"])) < 1e-6
     y.backward(T(g[f"{name}.gy"]))
     assert rel_l2(x.grad, T(g[f"{name}.gin0"])) < 1e-5
+    gw = {k: T(g[f"{name}.gw.{k[len('all_modules.0.'):]}"]) for k in sd}
+    total = torch.stack([v.double().norm() for v in gw.values()]).norm().item()
     for k, v in sd.items():
-        assert rel_l2(v.grad, T(g[f"{name}.gw.{k[len('all_modules.0.'):]}"])) < 1e-5, k
+        if k.endswith("NIN_1.b"):
+            # the key bias: its gradient is zero up to rounding (softmax is invariant to a shift along the key axis), so
+            # the golden holds rounding noise of the capture CPU; it has to match at fp32 rounding of the block's gradients
+            assert (v.grad.double() - gw[k].double()).norm().item() < 1e-7 * total, k
+        else:
+            assert rel_l2(v.grad, gw[k]) < 1e-5, k
 
 
 @pytest.mark.parametrize("name", ["pyr_down6", "pyr_down32"])
@@ -299,7 +314,9 @@ def test_sscs_sampler(golden, tag):
     x = O.sscs_sample(sde, lambda u, t: O.ncsnpp_forward(sd, cfg, u, t), T(g[f"batch_{tag}"]), T(g[f"ts_{tag}"]), n,
                       True, cfg.evaluation.eval_eps, noise=list(T(g[f"noise_{tag}"])))
     assert x.dtype == torch.float64
-    assert rel_l2(x, T(g[f"x_{tag}"])) < 1e-12
+    # float64 sampler steps around the float32 network: the network's rounding differs from CPU to CPU (MKL / ATen vector
+    # paths), the same bound as the EM sampler's above
+    assert rel_l2(x, T(g[f"x_{tag}"])) < 2e-6
 
 
 @pytest.mark.parametrize("tag", ["hsm_3", "hsm_6", "dsm_3", "dsm_6"])

@@ -34,7 +34,7 @@ rm -rf $OUT/hbm_prof_f
 cp $OUT/hbm_in_situ.json $OUT/hbm_in_situ.md $OUT/hbm_in_situ_forward.json $OUT/hbm_in_situ_forward.md $OUT/hbm_step_kernel_stats.csv $OUT/hbm_forward_kernel_stats.csv $P/ 2>/dev/null
 if [ "$MODE" != "hbm" ]; then
 # 4. per-kernel totals of the bench's training steps (headline pass + probed pass: 2 + 6 + 6 steps) and of the sampling forward
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_step -o step -- python3 $ROOT/bench.py --steps 6 --warmup 2 --sample-batch 0 --no-cpu-baseline --no-forward --no-config-block > $OUT/bench_train_b128_profiled_run.json 2> $OUT/prof_step.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_step -o step -- python3 $ROOT/bench.py --full --steps 6 --warmup 2 --sample-batch 0 --no-cpu-baseline --no-forward --no-config-block > $OUT/bench_train_b128_profiled_run.json 2> $OUT/prof_step.err
 find $OUT/prof_step -name "*kernel_stats.csv" -exec cp {} $OUT/bench_train_b128_kernel_stats.csv \;
 rm -rf $OUT/prof_step
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_sample -o sample -- python3 $ROOT/tools/profile_sample.py > $OUT/prof_sample.log 2>&1
@@ -45,13 +45,13 @@ fi
 cd $ROOT
 # 5. the bench lines (the default one last: it is the one the driver reproduces)
 if [ "$MODE" != "quick" ] && [ "$MODE" != "hbm" ]; then
-python3 bench.py --batch 16 --steps 30 --warmup 5 --sample-batch 0 --no-cpu-baseline --no-probe > $OUT/bench_b16_eager.json 2>/dev/null
-python3 bench.py --batch 64 --steps 20 --warmup 5 --sample-batch 0 --no-cpu-baseline --no-probe > $OUT/bench_b64_eager.json 2>/dev/null
-python3 bench.py --config celeba64_sota --steps 10 --warmup 3 --sample-batch 0 --no-cpu-baseline > $OUT/bench_celeba64.json 2>/dev/null
-PSLD_FORCE_PG=1 python3 bench.py --steps 10 --warmup 3 --sample-batch 0 --no-cpu-baseline > $OUT/bench_rccl_1rank.json 2>/dev/null
+python3 bench.py --full --batch 16 --steps 30 --warmup 5 --sample-batch 0 --no-cpu-baseline --no-probe > $OUT/bench_b16_eager.json 2>/dev/null
+python3 bench.py --full --batch 64 --steps 20 --warmup 5 --sample-batch 0 --no-cpu-baseline --no-probe > $OUT/bench_b64_eager.json 2>/dev/null
+python3 bench.py --full --config celeba64_sota --steps 10 --warmup 3 --sample-batch 0 --no-cpu-baseline > $OUT/bench_celeba64.json 2>/dev/null
+PSLD_FORCE_PG=1 python3 bench.py --full --steps 10 --warmup 3 --sample-batch 0 --no-cpu-baseline > $OUT/bench_rccl_1rank.json 2>/dev/null
 cp $OUT/bench_b16_eager.json $OUT/bench_b64_eager.json $OUT/bench_celeba64.json $OUT/bench_rccl_1rank.json $P/ 2>/dev/null
 fi
-python3 bench.py > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
+python3 bench.py --full > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
 cp $OUT/bench_default_run.json $P/
 tail -1 $OUT/bench_default_run.json | cut -c1-400
 ls $OUT
