@@ -31,6 +31,7 @@ import torch.nn as nn
 
 from . import ops
 from .registry import register_module
+from .weight_cache import Entry, WeightCache
 
 Tensor = torch.Tensor
 _ALIGN = 64  # floats: every parameter starts on a 256-byte boundary inside the flat buffers
@@ -572,7 +573,7 @@ class _Exec:
             out = prev if prev is not None else torch.zeros((co, 64), device=conv.weight.device, dtype=torch.float32)
             ops.scale_copy2d(conv.weight.detach(), ci * 9, out, 64, co, ci * 9)
             return out
-        return self.net._gfrag(conv.weight, "small_in", build)
+        return self.net._wcache.get(conv.weight, "small_in", _built_entry, build)
 
     def small_in_conv(self, x: Tensor, conv: _Affine, stride: int, pad: int, oh: int, ow: int, out: Tensor, epi):
         """Forward of a 3x3 convolution whose input has <= 7 channels; returns the im2col matrix for the wgrad."""
@@ -603,7 +604,7 @@ class _Exec:
             for o in range(co):
                 ops.scale_copy2d(conv.weight.detach(), 9, out, 64, ci, 9, src_off=o * ci * 9, dst_off=o * 9)
             return out
-        wd = self.net._gfrag(conv.weight, "small_out", build)
+        wd = self.net._wcache.get(conv.weight, "small_out", _built_entry, build)
         ops.gemm_raw(0, 1, m, ci, 64, cols, 64, 0, wd, 64, 0, da, ci, 0)
 
         def side():
@@ -667,7 +668,8 @@ class _Exec:
         plan = net._temb_plan()
         self.tp_all = self.dtp_all = None
         if plan is not None:
-            wcat, bcat, total = plan["wcat"], plan["bcat"], plan["total"]
+            wcat, bcat, self.temb_offsets = plan
+            total = wcat.shape[0]
             self.tp_all = torch.empty((b, total), device=t.device, dtype=torch.float32)
             ops.gemm_raw(0, 1, b, total, wcat.shape[1], st.v, wcat.shape[1], 0, wcat, wcat.shape[1], 0, self.tp_all,
                          total, 0, 1, ops.epilogue(bias=bcat))
@@ -681,27 +683,26 @@ class _Exec:
         # With a reducer (and no side stream) the same GEMM runs once per BUCKET, over the columns of the blocks finished since
         # the last one (flush_dense, called with the other parked reductions before a bucket is exchanged).
         self.dense_ok = self.dtp_all is not None and self.defer and self.split and \
-            ops.gemm_tn_split_supported(plan["total"], plan["wcat"].shape[1], b)
+            ops.gemm_tn_split_supported(total, wcat.shape[1], b)
         self.dense_batched = self.dense_ok and net._reducer is None
         dense_batched = self.dense_batched
 
         def bwd():
             self.join_side()            # every block wrote its slice of dtp_all / accumulated into st.g
             if dense_batched:
-                total, kd = plan["total"], plan["wcat"].shape[1]
+                kd = wcat.shape[1]
                 dwcat = net._persist("dwcat", (total, kd))
                 ops.gemm_tn_split(total, kd, b, dtp_all, total, st.v, kd, dwcat, kd, 1)
                 rows, first = [], 0
-                for m_ in plan["blocks"]:
-                    o, w_ = plan["offsets"][id(m_)], m_.Dense_0.weight
+                for m_, o in self.temb_offsets.items():
+                    w_ = m_.Dense_0.weight
                     n4 = w_.numel() // 4
                     rows += [dwcat.data_ptr() + 4 * o * kd, self.g(w_).data_ptr(), n4, first]
                     first += n4
-                ops.copy_batch(net._tables.get(rows, dwcat.device), len(plan["blocks"]), first)
+                ops.copy_batch(net._tables.get(rows, dwcat.device), len(self.temb_offsets), first)
             if dtp_all is not None:     # d act(temb) = sum over blocks dtp_i W_i = dtp_all Wcat: one GEMM
-                wcat = plan["wcat"]
                 gb, acc = _gbuf(st)
-                total, kd = plan["total"], wcat.shape[1]
+                kd = wcat.shape[1]
                 # M = batch is one tile tall and K = sum of the blocks' C_out is long (14592 for C10): cut K into
                 # ranges that run as the batches of one launch, then add the partial products in range order
                 ks = next((k for k in (256, 128, 64) if total % k == 0), 0)
@@ -789,7 +790,7 @@ class _Exec:
         ho, wo = ho_, wo_
         tp, tp_ld, tp_off = None, 0, None
         if self.temb_act is not None:
-            tp_off = net._temb_offset(mod) if self.tp_all is not None else None
+            tp_off = self.temb_offsets[mod] if self.tp_all is not None else None
             if tp_off is not None:
                 tp, tp_ld = self.tp_all[:, tp_off:tp_off + cout], self.tp_all.shape[1]
             else:
@@ -1149,8 +1150,8 @@ class _Exec:
             cols = self.small_in_conv(xf, conv, 2, 0, oh, ow, out, epi)
         elif limb:
             patches = ops.im2col3x3(xf, 2, 0, oh, ow)
-            fr = net._gfrag(conv.weight, "s2fwd",
-                            lambda prev: ops.gemm_frag(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev))
+            fr = net._wcache.get(conv.weight, "s2fwd", _built_entry,
+                                 lambda prev: ops.gemm_frag(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev))
             ops.gemm_split(patches, None, m, fr, cout, out, epi)
             del patches
         else:
@@ -1177,8 +1178,9 @@ class _Exec:
             if not first:
                 dxf = torch.empty_like(xf)
                 if limb:
-                    frd = net._gfrag(conv.weight, "s2dgrad",
-                                     lambda prev: ops.gemm_frag(net._packed(conv), 9 * cin, cout, 1, 9 * cin, prev))
+                    frd = net._wcache.get(
+                        conv.weight, "s2dgrad", _built_entry,
+                        lambda prev: ops.gemm_frag(net._packed(conv), 9 * cin, cout, 1, 9 * cin, prev))
                     dpatches = torch.empty((m, 9 * cin), device=dout.device, dtype=torch.float32)
                     ops.gemm_split(dout, None, m, frd, 9 * cin, dpatches, ops.epilogue(alpha=s))
                     ops.col2im3x3(dpatches, xf.shape, 2, 0, oh, ow, out=dxf)
@@ -1493,6 +1495,83 @@ class _NCSNppParamFn(torch.autograd.Function):
         return (ex.dx_nchw, None, None) + grads
 
 
+# ---- derived-weight entries of NCSNpp (weight_cache.py): make(owner, *args) -> Entry, called on first use ------------
+def _packed_entry(w: Tensor, dgrad: bool) -> Entry:
+    co, ci, kh, kw = w.shape
+
+    def build(prev):
+        out = prev if prev is not None else \
+            torch.empty((ci, kh * kw, co) if dgrad else (co, kh * kw, ci), device=w.device, dtype=torch.float32)
+        (ops.pack_dgrad if dgrad else ops.pack_ohwi)(w.detach(), out)
+        return out
+    return Entry(w, build=build, graph=not dgrad)
+
+
+def _frag_entry(w: Tensor, dgrad: bool, wino: bool) -> Entry:
+    pack, row = (ops.conv3x3_wino_frag, ops.conv3x3_wino_frag_entry) if wino else \
+        (ops.conv3x3_frag, ops.conv3x3_frag_entry)
+    return Entry(w, build=lambda prev: pack(w.detach(), dgrad, prev), family="wino" if wino else "limb",
+                 rows=lambda out: [(row(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
+
+
+def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor], chunk0: int,
+                 chunks_total: int) -> Entry:
+    def rows(out):
+        return [([p.data_ptr(), out.data_ptr(), n, k | (chunk0 << 20) | (chunks_total << 40), 1, sn, sk], n * k // 8)]
+
+    def build(prev):
+        if into is None:
+            return ops.gemm_frag(p.detach(), n, k, sn, sk, prev)
+        # a one-entry table through the batched entry point (the only one that takes a K placement)
+        (row, items), = rows(into)
+        ops.pack_frag_batch(torch.tensor(row + [0], dtype=torch.int64, device=p.device), 1, items)
+        return into
+    return Entry(p, build=build, family="limb", rows=rows, graph=tag in ("fwd", "qkv_f"))
+
+
+def _built_entry(owner: Tensor, build) -> Entry:
+    """Fragments built by ``build(prev)`` from ``owner`` (and possibly sibling parameters)."""
+    return Entry(owner, build=build, graph=True)
+
+
+def _qkv_entry(b0: Tensor, mod: "AttnBlockpp") -> Entry:
+    """out: the forward and data-gradient q | k | v fragment sets (filled by the "qkv_f" / "qkv_d" entries) and the
+    gathered [b_q | b_k | b_v] (filled by the "qkv_bias" family's batched copy)."""
+    c = b0.numel()
+    fb = ops.gemm_frag_bytes(c, c)
+    out = (torch.empty(3 * fb, dtype=torch.uint8, device=b0.device),
+           torch.empty(3 * fb, dtype=torch.uint8, device=b0.device),
+           torch.empty(3 * c, dtype=torch.float32, device=b0.device))
+
+    def rows(out):
+        bq = out[2]
+        return [([nin.b.data_ptr(), bq.data_ptr() + 4 * i * c, c // 4], c // 4)
+                for i, nin in enumerate((mod.NIN_0, mod.NIN_1, mod.NIN_2))]
+    return Entry(b0, out=out, family="qkv_bias", rows=rows, graph=True)
+
+
+def _temb_entry(w0: Tensor, modules) -> Entry:
+    """out: (wcat, bcat, {block: first row}) of NCSNpp._temb_plan, filled by the "temb" family's batched copy."""
+    offsets, total = {}, 0
+    for m in modules:
+        if isinstance(m, ResnetBlockBigGANpp):
+            offsets[m] = total
+            total += m.Dense_0.weight.shape[0]
+    out = (torch.empty((total, w0.shape[1]), device=w0.device, dtype=torch.float32),
+           torch.empty((total,), device=w0.device, dtype=torch.float32), offsets)
+
+    def rows(out):
+        wcat, bcat, offsets = out
+        r = []
+        for m, o in offsets.items():
+            w, bias = m.Dense_0.weight, m.Dense_0.bias
+            for src, dst, n in ((w, wcat[o], w.numel()), (bias, bcat[o:], bias.numel())):
+                assert n % 4 == 0 and src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0
+                r.append(([src.data_ptr(), dst.data_ptr(), n // 4], n // 4))
+        return r
+    return Entry(w0, out=out, family="temb", rows=rows, graph=True)
+
+
 @register_module(category="score_fn", name="ncsnpp")
 class NCSNpp(nn.Module):
     """NCSN++ (ncsnpp.py:35-285 for the module list; forward in ``_Exec.run``)."""
@@ -1583,22 +1662,7 @@ class NCSNpp(nn.Module):
             modules.append(_conv(in_ch, sf.out_ch, 3, init_scale))
         self.all_modules = nn.ModuleList(modules)
 
-        # executor state (never part of state_dict)
-        self._flat: Optional[Tensor] = None
-        self._flat_grad: Optional[Tensor] = None
-        self._offsets = None
-        self._pack_cache = {}
-        self._frag_table = None     # (signature, device table, entries, total work items) of the batched fragment refresh
-        self._qkv_bias_table = None
-        self._qkv_bias_stamp = {}
-        self._wfrag_table = None    # the same for the Winograd fragment sets
-        self._temb_plan_cache = None
-        self._pack_key = None
-        self._epoch = 0
-        self._anchor = None
-        self._reducer = None
-        self._posfreq = None
-        self._module_offs = None
+        self._init_runtime()
         # parameter-gradient kernels on a side stream: None = automatic (small batches, see _Exec._run); True / False or
         # PSLD_OVERLAP_WGRAD=1 / 0 force it
         import os as _os
@@ -1608,14 +1672,29 @@ class NCSNpp(nn.Module):
         # dgamma / dbeta / bias gradients / split-K slab reductions of a backward pass in batched launches (_Exec.defer_param,
         # _Exec.reduce_slabs); False: one launch per layer, right where the reference's autograd would compute them
         self.defer_param_grads = True
-        self._tables = ops.TableCache()
-        self._parena = self._sarena = None
-        self._persistent = {}
         # None (auto): parameters become inputs of the autograd node (gradients delivered through AccumulateGrad, so
         # torch DDP / Lightning's ddp strategy can reduce them) when a multi-rank process group exists and no
         # BucketReducer is attached; True / False (or PSLD_AUTOGRAD_PARAMS=1 / 0) force it.
         _ap = _os.environ.get("PSLD_AUTOGRAD_PARAMS")
         self.autograd_params = None if _ap is None else _ap == "1"
+        self.use_graphs = _os.environ.get("PSLD_GRAPHS", "0") == "1"
+
+    def _init_runtime(self):
+        """Executor state (never part of state_dict, started afresh by deepcopy): flat parameter / gradient storage,
+        arenas, job tables, persistent buffers, derived weights, captured graphs, side stream."""
+        self._flat: Optional[Tensor] = None
+        self._flat_grad: Optional[Tensor] = None
+        self._offsets = None
+        # derived weights; a batched refresh needs two entries of a limb / Winograd family, one of a gathered copy
+        self._wcache = WeightCache({"limb": (ops.pack_frag_batch, 2), "wino": (ops.pack_wino_batch, 2),
+                                    "qkv_bias": (ops.copy_batch, 1), "temb": (ops.copy_batch, 1)})
+        self._anchor = None
+        self._reducer = None
+        self._posfreq = None
+        self._module_offs = None
+        self._tables = ops.TableCache()
+        self._parena = self._sarena = None
+        self._persistent = {}
         self._plist = None
         self._tlist = None
         self._gviews = None
@@ -1626,9 +1705,7 @@ class NCSNpp(nn.Module):
         self._grad_stale = False
         self._scratch_grad = None
         self._sviews = None
-        self.use_graphs = _os.environ.get("PSLD_GRAPHS", "0") == "1"
         self._graphs = {}
-        self._conv_by_weight = {}
         self._side = None
 
     def pin_scratch(self):
@@ -1705,10 +1782,7 @@ class NCSNpp(nn.Module):
             self._flat_grad = None
             self._gviews = None
             self._scratch_grad = self._sviews = None
-            self._pack_cache.clear()
-            self._qkv_bias_table = None
-            self._qkv_bias_stamp = {}
-            self._epoch += 1
+            self._wcache.clear()
         self._offsets = offs
         self._module_offs = None
         return self._flat
@@ -1747,139 +1821,28 @@ class NCSNpp(nn.Module):
 
     def weights_changed(self):
         """Call after writing parameters through raw pointers (fused optimiser / EMA kernels)."""
-        self._epoch += 1
+        self._wcache.invalidate()
 
+    # ---- derived weights (weight_cache.py): cached until the weights change, refreshed in place ------------------
     def _packed(self, conv: _Affine, dgrad: bool = False) -> Tensor:
-        """[co][tap][ci] (forward) or [ci][flip tap][co] (data-gradient) copy of an OIHW weight,
-        cached until the weights change."""
-        w = conv.weight
-        key = (id(w), dgrad)
-        self._conv_by_weight[id(w)] = conv
-        ent = self._pack_cache.get(key)
-        stamp = (self._epoch, w._version, w.data_ptr())
-        if ent is not None and ent[0] == stamp:
-            return ent[1]
-        co, ci, kh, kw = w.shape
-        out = ent[1] if ent is not None and ent[1].device == w.device else \
-            torch.empty((ci, kh * kw, co) if dgrad else (co, kh * kw, ci), device=w.device, dtype=torch.float32)
-        (ops.pack_dgrad if dgrad else ops.pack_ohwi)(w.detach(), out)
-        self._pack_cache[key] = (stamp, out)
-        return out
+        """[co][tap][ci] (forward) or [ci][flip tap][co] (data-gradient) copy of an OIHW weight."""
+        return self._wcache.get(conv.weight, "dpack" if dgrad else "pack", _packed_entry, dgrad)
 
     def _frag(self, conv: _Affine, dgrad: bool) -> Tensor:
-        """bf16 limb fragments of a 3x3 weight (ops.conv3x3_frag), cached until the weights change; once two or
-        more exist, a weight update refreshes ALL of them with one batched launch."""
-        w = conv.weight
-        key = (id(w), dgrad, "frag")
-        self._conv_by_weight[id(w)] = conv
-        ent = self._pack_cache.get(key)
-        stamp = (self._epoch, w._version, w.data_ptr())
-        if ent is not None and ent[0] == stamp:
-            return ent[1]
-        if ent is not None and ent[1].device == w.device and self._refresh_frags():
-            ent = self._pack_cache[key]
-            if ent[0] == stamp:
-                return ent[1]
-        out = ops.conv3x3_frag(w.detach(), dgrad, ent[1] if ent is not None and ent[1].device == w.device else None)
-        self._pack_cache[key] = (stamp, out)
-        self._frag_table = None
-        return out
+        """bf16 limb fragments of a 3x3 weight (ops.conv3x3_frag)."""
+        return self._wcache.get(conv.weight, "dfrag" if dgrad else "frag", _frag_entry, dgrad, False)
 
     def _wfrag(self, conv: _Affine, dgrad: bool) -> Tensor:
-        """Winograd-transformed bf16 limb fragments of a 3x3 weight (ops.conv3x3_wino_frag), cached and refreshed like
-        ``_frag`` (one batched launch for all of them after a weight update)."""
-        w = conv.weight
-        key = (id(w), dgrad, "wfrag")
-        self._conv_by_weight[id(w)] = conv
-        ent = self._pack_cache.get(key)
-        stamp = (self._epoch, w._version, w.data_ptr())
-        if ent is not None and ent[0] == stamp:
-            return ent[1]
-        if ent is not None and ent[1].device == w.device and self._refresh_wfrags():
-            ent = self._pack_cache[key]
-            if ent[0] == stamp:
-                return ent[1]
-        out = ops.conv3x3_wino_frag(w.detach(), dgrad, ent[1] if ent is not None and ent[1].device == w.device else None)
-        self._pack_cache[key] = (stamp, out)
-        self._wfrag_table = None
-        return out
-
-    def _refresh_wfrags(self) -> bool:
-        """Re-transform every registered Winograd fragment set into its existing buffer with ONE launch
-        (psld_pack_wino_batch).  False when there is nothing to batch."""
-        keys = [k for k in self._pack_cache if len(k) == 3 and k[2] == "wfrag"]
-        if len(keys) < 2:
-            return False
-        ws = [self._conv_by_weight[k[0]].weight for k in keys]
-        outs = [self._pack_cache[k][1] for k in keys]
-        if any(o.device != w.device for o, w in zip(outs, ws)):
-            return False
-        sig = tuple((k, w.data_ptr(), o.data_ptr()) for k, w, o in zip(keys, ws, outs))
-        if self._wfrag_table is None or self._wfrag_table[0] != sig:
-            rows, total = [], 0
-            for k, w, o in zip(keys, ws, outs):
-                rows.append(ops.conv3x3_wino_frag_entry(w.detach(), k[1], o) + [total])
-                total += w.shape[0] * w.shape[1] // 8
-            self._wfrag_table = (sig, torch.tensor(rows, dtype=torch.int64, device=ws[0].device), len(rows), total)
-        _, table, n, total = self._wfrag_table
-        ops.pack_wino_batch(table, n, total)
-        for k, w, o in zip(keys, ws, outs):
-            self._pack_cache[k] = ((self._epoch, w._version, w.data_ptr()),) + tuple(self._pack_cache[k][1:])
-        return True
-
-    def _refresh_frags(self) -> bool:
-        """Re-split every registered 3x3 / pointwise weight into its existing fragment buffer with ONE launch
-        (psld_pack_frag_batch).  False when there is nothing to batch."""
-        keys = [k for k in self._pack_cache if len(k) == 3 and k[2] in ("frag", "pfrag")]
-        if len(keys) < 2:
-            return False
-        ws = [self._conv_by_weight[k[0]].weight if k[2] == "frag" else self._pack_cache[k][2] for k in keys]
-        outs = [self._pack_cache[k][1] for k in keys]
-        if any(o.device != w.device for o, w in zip(outs, ws)):
-            return False
-        sig = tuple((k, w.data_ptr(), o.data_ptr()) for k, w, o in zip(keys, ws, outs))
-        if self._frag_table is None or self._frag_table[0] != sig:
-            rows, total = [], 0
-            for k, w, o in zip(keys, ws, outs):
-                if k[2] == "frag":
-                    rows.append(ops.conv3x3_frag_entry(w.detach(), k[1], o) + [total])
-                    total += w.shape[0] * w.shape[1] // 8        # work items: one per lane slot
-                else:
-                    n, kk, sn, sk, c0, ct = self._pack_cache[k][3]
-                    rows.append([w.data_ptr(), o.data_ptr(), n, kk | (c0 << 20) | (ct << 40), 1, sn, sk, total])
-                    total += n * kk // 8
-            self._frag_table = (sig, torch.tensor(rows, dtype=torch.int64, device=ws[0].device), len(rows), total)
-        _, table, n, total = self._frag_table
-        ops.pack_frag_batch(table, n, total)
-        for k, w, o in zip(keys, ws, outs):
-            self._pack_cache[k] = ((self._epoch, w._version, w.data_ptr()),) + tuple(self._pack_cache[k][1:])
-        return True
+        """Winograd-transformed bf16 limb fragments of a 3x3 weight (ops.conv3x3_wino_frag)."""
+        return self._wcache.get(conv.weight, "dwfrag" if dgrad else "wfrag", _frag_entry, dgrad, True)
 
     def _pfrag(self, owner: nn.Parameter, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor] = None,
                chunk0: int = 0, chunks_total: int = 0) -> Tensor:
-        """Limb fragments (ops.gemm_frag) of the [n][k] view of ONE parameter (element (i, j) at i*sn + j*sk), cached
-        until the weights change and refreshed together with the 3x3 fragments by the batched launch.
-        ``into``: the buffer to fill (several parameters that share one fragment set: q | k | v) - then ``chunk0`` /
-        ``chunks_total`` place this parameter's K range inside the set's K dimension (psld_pack_frag_batch)."""
-        key = (id(owner), tag, "pfrag")
-        ent = self._pack_cache.get(key)
-        stamp = (self._epoch, owner._version, owner.data_ptr())
-        if ent is not None and ent[0] == stamp and (into is None or ent[1].data_ptr() == into.data_ptr()):
-            return ent[1]
-        if ent is not None and ent[1].device == owner.device and (into is None or ent[1].data_ptr() == into.data_ptr()) and \
-                self._refresh_frags():
-            ent = self._pack_cache[key]
-            if ent[0] == stamp:
-                return ent[1]
-        if into is None:
-            out = ops.gemm_frag(owner.detach(), n, k, sn, sk, ent[1] if ent is not None and ent[1].device == owner.device else None)
-        else:       # first use: a one-entry table through the batched entry point (the only one that takes a K placement)
-            out = into
-            row = [owner.data_ptr(), out.data_ptr(), n, k | (chunk0 << 20) | (chunks_total << 40), 1, sn, sk, 0]
-            ops.pack_frag_batch(torch.tensor(row, dtype=torch.int64, device=owner.device), 1, n * k // 8)
-        self._pack_cache[key] = (stamp, out, owner, (n, k, sn, sk, chunk0, chunks_total))
-        self._frag_table = None
-        return out
+        """Limb fragments (ops.gemm_frag) of the [n][k] view of ONE parameter (element (i, j) at i*sn + j*sk), refreshed
+        together with the 3x3 fragments by the batched launch.  ``into``: the buffer to fill (several parameters that
+        share one fragment set: q | k | v) - then ``chunk0`` / ``chunks_total`` place this parameter's K range inside the
+        set's K dimension (psld_pack_frag_batch)."""
+        return self._wcache.get(owner, tag, _pfrag_entry, tag, n, k, sn, sk, into, chunk0, chunks_total)
 
     def _qkv_frags(self, mod):
         """Fragments of an attention block's q | k | v projections as ONE GEMM operand each way - forward B[n][k] =
@@ -1887,100 +1850,26 @@ class NCSNpp(nn.Module):
         bias.  Packed straight from the three parameters into shared buffers by the batched refresh of all fragments (no
         concatenated copy of the weights, no launch of their own after the first step); the biases of ALL attention blocks
         are gathered by one batched copy when they change."""
-        n0, n1, n2 = mod.NIN_0, mod.NIN_1, mod.NIN_2
+        n0 = mod.NIN_0
         c = n0.W.shape[0]
-        key = (id(n0.W), "qkv", "bufs")
-        bufs = self._pack_cache.get(key)
-        dev = n0.W.device
-        if bufs is None or bufs[0].device != dev:
-            fb = ops.gemm_frag_bytes(c, c)
-            bufs = (torch.empty(3 * fb, dtype=torch.uint8, device=dev), torch.empty(3 * fb, dtype=torch.uint8, device=dev),
-                    torch.empty(3 * c, dtype=torch.float32, device=dev), fb, mod)
-            self._pack_cache[key] = bufs
-            self._qkv_bias_table = None
-        pf, pd, bq, fb = bufs[:4]
-        for i, nin in enumerate((n0, n1, n2)):
+        e = self._wcache.entry(n0.b, "qkv", _qkv_entry, mod)
+        pf, pd = e.out[:2]
+        fb = pf.numel() // 3
+        for i, nin in enumerate((n0, mod.NIN_1, mod.NIN_2)):
             # forward: rows n of the set are output channels -> each projection is a contiguous third of the set
             self._pfrag(nin.W, "qkv_f", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
             # data gradient: the three projections are concatenated along K
             self._pfrag(nin.W, "qkv_d", c, c, c, 1, into=pd, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
-        stamp = (self._epoch, n0.b._version, n0.b.data_ptr())
-        if self._qkv_bias_stamp.get(id(mod)) != stamp:
-            self._refresh_qkv_biases()
-        return pf, pd, bq
-
-    def _refresh_qkv_biases(self):
-        mods = [m for m in self.all_modules if isinstance(m, AttnBlockpp) and (id(m.NIN_0.W), "qkv", "bufs") in self._pack_cache]
-        sig = tuple((m.NIN_0.b.data_ptr(), self._pack_cache[(id(m.NIN_0.W), "qkv", "bufs")][2].data_ptr()) for m in mods)
-        if self._qkv_bias_table is None or self._qkv_bias_table[0] != sig:
-            rows, first = [], 0
-            for m in mods:
-                bq = self._pack_cache[(id(m.NIN_0.W), "qkv", "bufs")][2]
-                c = m.NIN_0.b.numel()
-                for i, nin in enumerate((m.NIN_0, m.NIN_1, m.NIN_2)):
-                    rows += [nin.b.data_ptr(), bq.data_ptr() + 4 * i * c, c // 4, first]
-                    first += c // 4
-            self._qkv_bias_table = (sig, torch.tensor(rows, dtype=torch.int64, device=mods[0].NIN_0.b.device), 3 * len(mods), first)
-        _, table, jobs, total = self._qkv_bias_table
-        ops.copy_batch(table, jobs, total)
-        for m in mods:
-            self._qkv_bias_stamp[id(m)] = (self._epoch, m.NIN_0.b._version, m.NIN_0.b.data_ptr())
-
-    def _temb_offset(self, mod) -> Optional[int]:
-        plan = self._temb_plan_cache
-        return None if plan is None else plan["offsets"].get(id(mod))
+        return self._wcache.fresh(e)
 
     def _temb_plan(self):
-        """Gathered time-embedding projections: ``wcat`` [sum C_out][4*nf] and ``bcat`` [sum C_out] hold Dense_0.weight /
-        .bias of every ResBlock back to back (refreshed with ONE batched copy when the weights change), ``offsets`` the
-        first row of each block.  None when the network is not noise-conditioned."""
+        """Gathered time-embedding projections ``(wcat, bcat, offsets)``: wcat [sum C_out][4*nf] and bcat [sum C_out]
+        hold Dense_0.weight / .bias of every ResBlock back to back, offsets maps each block to its first row.  None when
+        the network is not noise-conditioned."""
         if not self.noise_cond:
             return None
-        blocks = [m for m in self.all_modules if isinstance(m, ResnetBlockBigGANpp)]
-        dev = blocks[0].Dense_0.weight.device
-        plan = self._temb_plan_cache
-        stamp = (self._epoch, blocks[0].Dense_0.weight._version, blocks[0].Dense_0.weight.data_ptr(), str(dev))
-        if plan is not None and plan["stamp"] == stamp:
-            return plan
-        if plan is None or plan["wcat"].device != dev:
-            total = sum(m.Dense_0.weight.shape[0] for m in blocks)
-            kd = blocks[0].Dense_0.weight.shape[1]
-            plan = {"wcat": torch.empty((total, kd), device=dev, dtype=torch.float32),
-                    "bcat": torch.empty((total,), device=dev, dtype=torch.float32), "total": total, "offsets": {},
-                    "table": None, "sig": None, "blocks": blocks}
-            off = 0
-            for m in blocks:
-                plan["offsets"][id(m)] = off
-                off += m.Dense_0.weight.shape[0]
-        sig = tuple((m.Dense_0.weight.data_ptr(), m.Dense_0.bias.data_ptr()) for m in blocks)
-        if plan["table"] is None or plan["sig"] != sig:
-            rows, first = [], 0
-            for m in blocks:
-                w, bias = m.Dense_0.weight, m.Dense_0.bias
-                o = plan["offsets"][id(m)]
-                for src, dst, n in ((w, plan["wcat"][o], w.numel()), (bias, plan["bcat"][o:], bias.numel())):
-                    assert n % 4 == 0 and src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0
-                    rows.append([src.data_ptr(), dst.data_ptr(), n // 4, first])
-                    first += n // 4
-            plan["table"], plan["sig"], plan["total4"] = torch.tensor(rows, dtype=torch.int64, device=dev), sig, first
-        ops.copy_batch(plan["table"], plan["table"].shape[0], plan["total4"])
-        plan["stamp"] = stamp
-        self._temb_plan_cache = plan
-        return plan
-
-    def _gfrag(self, owner: nn.Parameter, tag: str, build):
-        """Limb fragments derived from ``owner`` (and possibly sibling parameters), cached until the weights change.
-        ``build(prev)`` returns the tensor (or tuple of tensors) to keep and refreshes ``prev`` IN PLACE when given
-        (captured graphs hold these addresses)."""
-        key = (id(owner), tag, "gfrag")
-        ent = self._pack_cache.get(key)
-        stamp = (self._epoch, owner._version, owner.data_ptr())
-        if ent is not None and ent[0] == stamp:
-            return ent[1]
-        prev = ent[1] if ent is not None and (ent[1][0] if isinstance(ent[1], tuple) else ent[1]).device == owner.device else None
-        out = build(prev)
-        self._pack_cache[key] = (stamp, out, owner, build)
-        return out
+        first = next(m for m in self.all_modules if isinstance(m, ResnetBlockBigGANpp))
+        return self._wcache.get(first.Dense_0.weight, "temb", _temb_entry, self.all_modules)
 
     def _pos_freq(self, device):
         if self._posfreq is None or self._posfreq.device != device:
@@ -2141,29 +2030,9 @@ class NCSNpp(nn.Module):
             ent = self._graphs[key] = [graph, sx, st, sy, None]
             self.pin_scratch()       # the graph holds raw pointers into arenas / job tables: no eviction, no freeing from now on
         graph, sx, st, sy, stamp = ent
-        now = (self._epoch, self._flat._version)
+        now = (self._wcache.epoch, self._flat._version)
         if stamp != now:
-            self._temb_plan()                                   # gathered Dense_0 weights (refreshed in place)
-            for ck, cv in list(self._pack_cache.items()):       # refresh, in the same storage, what the graph reads
-                if ck[-1] == "gfrag":
-                    self._gfrag(cv[2], ck[1], cv[3])
-                elif ck[-1] == "pfrag":
-                    if ck[1] in ("fwd", "qkv_f"):
-                        n_, k_, sn_, sk_, c0_, ct_ = cv[3]
-                        self._pfrag(cv[2], ck[1], n_, k_, sn_, sk_, into=cv[1] if ck[1] == "qkv_f" else None, chunk0=c0_,
-                                    chunks_total=ct_)
-                elif ck[-1] == "bufs":                          # an attention block's gathered q | k | v bias
-                    m_ = cv[4]
-                    if self._qkv_bias_stamp.get(id(m_)) != (self._epoch, m_.NIN_0.b._version, m_.NIN_0.b.data_ptr()):
-                        self._refresh_qkv_biases()
-                elif ck[-1] == "wfrag":                         # Winograd fragments the captured forward reads
-                    if not ck[1]:
-                        self._wfrag(self._conv_by_weight[ck[0]], False)
-                elif ck[-1] == "frag":
-                    if not ck[1]:
-                        self._frag(self._conv_by_weight[ck[0]], False)
-                elif len(ck) == 2 and not ck[1]:
-                    self._packed(self._conv_by_weight[ck[0]])
+            self._wcache.refresh(forward_only=True)              # refresh, in the same storage, what the graph reads
             ent[4] = now
         sx.copy_(x)
         st.copy_(t)
@@ -2171,37 +2040,15 @@ class NCSNpp(nn.Module):
         return sy.clone()
 
     def __deepcopy__(self, memo):
+        """Modules and configuration are copied, the executor state starts afresh (_init_runtime)."""
         import copy
         cls = self.__class__
         new = cls.__new__(cls)
         memo[id(self)] = new
-        skip = {"_tables", "_parena", "_sarena", "_persistent", "_flat", "_flat_grad", "_pack_cache", "_frag_table", "_wfrag_table", "_qkv_bias_table", "_qkv_bias_stamp", "_temb_plan_cache", "_anchor", "_reducer", "_offsets", "_module_offs", "_posfreq",
-                "_side", "_plist", "_tlist", "_gviews", "_dropout_seed_dev", "_graphs", "_conv_by_weight", "_scratch_grad", "_sviews"}
+        new._init_runtime()
         for k, v in self.__dict__.items():
-            if k in skip:
-                continue
-            new.__dict__[k] = copy.deepcopy(v, memo)
-        new._flat = new._flat_grad = new._offsets = new._anchor = new._reducer = new._posfreq = new._side = None
-        new._tables = ops.TableCache()
-        new._parena = new._sarena = None
-        new._persistent = {}
-        new._module_offs = None
-        new._plist = new._tlist = new._gviews = None
-        new._graphs = {}
-        new._conv_by_weight = {}
-        new._pending = 0
-        new._backward_count = 0
-        new._dropout_seed_dev = None
-        new._scratch_grad = new._sviews = None
-        new._accumulating = new._grad_stale = False
-        new._pack_cache = {}
-        new._frag_table = None
-        new._wfrag_table = None
-        new._qkv_bias_table = None
-        new._qkv_bias_stamp = {}
-        new._temb_plan_cache = None
-        new._pack_key = None
-        new._epoch = 0
+            if k not in new.__dict__:
+                new.__dict__[k] = copy.deepcopy(v, memo)
         # detach copied params from the source's flat buffer (they are re-flattened on first use)
         for p in new.parameters():
             p.data = p.data.clone()
