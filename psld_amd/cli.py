@@ -485,20 +485,24 @@ def inpaint(args, overrides):
         dist.destroy_process_group()
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="psld_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
     for name in ("train", "sample", "inpaint", "train_clf", "cc_sample"):
         p = sub.add_parser(name)
-        p.add_argument("--config", default="c10_sota", choices=["c10_sota", "celeba64_sota", "yaml_default", "tiny"])
+        p.add_argument("--config", default="c10_sota", choices=["c10_sota", "celeba64_sota", "afhqv2_128", "yaml_default", "tiny"])
         p.add_argument("--data", default="synthetic", help="uint8 [N,H,W,3] .npy file or 'synthetic'")
         p.add_argument("--synthetic-size", type=int, default=2048)
         p.add_argument("--max-steps", type=int, default=0)
         p.add_argument("--log-every", type=int, default=10)
         p.add_argument("--mask", default="synthetic", help="inpaint: uint8 [N,H,W,3] .npy (1 = keep) or 'synthetic'")
-        p.add_argument("--clf-config", default="clf_c10", choices=["clf_c10", "clf_default", "tiny_clf"])
+        p.add_argument("--clf-config", default="clf_c10", choices=["clf_c10", "clf_afhqv2_128", "clf_default", "tiny_clf"])
         p.add_argument("--labels", default="synthetic", help="train_clf: int [N] .npy or 'synthetic'")
-    args, overrides = ap.parse_known_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args, overrides = build_parser().parse_known_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("psld_amd needs an MI355X: there is no CPU fallback")
     {"train": train, "sample": sample, "inpaint": inpaint, "train_clf": train_clf,

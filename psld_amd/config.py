@@ -10,7 +10,9 @@ unchanged wherever a ``Config`` is accepted.
 Key names and default values follow main/configs/dataset/cifar10/cifar10_psld.yaml:1-99;
 ``c10_sota`` applies the overrides of
 scripts_psld/sota/uncond/cifar10/train_uncond_psld.sh:6-21 and ``celeba64_sota``
-those of scripts_psld/sota/uncond/celeba64/train_uncond_psld.sh:7-20.
+those of scripts_psld/sota/uncond/celeba64/train_uncond_psld.sh:7-20; ``afhqv2_128`` is
+main/configs/dataset/afhqv2/afhqv2128_psld.yaml with the overrides of
+scripts_psld/ablations/uncond/afhqv2/train_uncond_psld.sh.
 """
 from __future__ import annotations
 
@@ -132,6 +134,30 @@ def celeba64_sota() -> Config:
     return c
 
 
+def afhqv2_128() -> Config:
+    """AFHQv2 at 128x128: afhqv2128_psld.yaml + scripts_psld/ablations/uncond/afhqv2/train_uncond_psld.sh (batch 8)."""
+    c = yaml_default()
+    c.data.name = "afhqv2"
+    c.data.image_size = 128
+    c.data.hflip = True
+    c.data.norm = True
+    sf = c.model.score_fn
+    sf.nf = 128
+    sf.ch_mult = [1, 2, 2, 2, 3]
+    sf.num_res_blocks = 2
+    sf.attn_resolutions = [16]
+    sf.dropout = 0.2
+    sf.fir = False
+    sf.progressive_input = "none"
+    sf.embedding_type = "positional"
+    sde = c.model.sde
+    sde.nu, sde.gamma, sde.kappa, sde.decomp_mode = 4.01, 0.01, 0.04, "lower"
+    c.training.optimizer.lr = 1e-4
+    c.training.optimizer.warmup = 5000
+    c.training.batch_size = 8
+    return c
+
+
 def tiny(image_size: int = 16, nf: int = 32, ch_mult=(1, 2), num_res_blocks: int = 1,
          attn_resolutions=(8,)) -> Config:
     """Reduced net with every block kind of C10-SOTA (used by parity tests/smoke)."""
@@ -202,6 +228,21 @@ def clf_c10() -> Config:
     cf.num_res_blocks = 4
     cf.attn_resolutions = [16, 8]
     cf.n_cls = 10
+    return c
+
+
+def clf_afhqv2_128() -> Config:
+    """The ``clf`` node of afhqv2128_psld.yaml (n_cls is ``???`` there; 3 = AFHQv2's cat / dog / wild)."""
+    c = clf_default()
+    c.data.name = "afhqv2"
+    c.data.image_size = 128
+    cf = c.model.clf_fn
+    cf.ch_mult = [1, 2, 2, 2]
+    cf.num_res_blocks = 2
+    cf.attn_resolutions = [16]
+    cf.dropout = 0.1
+    cf.n_cls = 3
+    c.training.optimizer.lr = 2e-4
     return c
 
 

@@ -133,7 +133,9 @@ struct DConvArgs {
     int ldc;
     long long c_stride_split;
     int nseg, rps;          // image segments per 128-pixel tile and output rows per segment
-    int pitch;              // pixel rows of the LDS halo image per image row: W + 2, or 16 for 8-wide maps on 64-row tiles (see dconv_pitch)
+    int pitch;              // pixel rows of the LDS halo image per image row: cw + 2, or 16 for 8-wide maps on 64-row tiles (see dconv_pitch)
+    int cw, lg_xb;          // 3x3: width of a tile's pixel region (W, or 64 on 128-wide maps) and log2 of the regions per row band (W / cw)
+    int xskip;              // W - cw: pixels between the end of one region row and the start of the next (0: tiles are consecutive pixels)
     PsldEpilogue e;
     const float* zero;
     int v4;                 // rows of C / residual / bias / row bias are 16-byte aligned: dwordx4 epilogue (set by plan_split)
@@ -165,6 +167,13 @@ __device__ __forceinline__ T* uni(T* p) {
     // become flat_load / flat_store (which also tick the LDS counter and can only be waited for with vmcnt(0) lgkmcnt(0))
     typedef __attribute__((address_space(1))) T G;
     return (T*)(G*)(((unsigned long long)hi << 32) | lo);
+}
+
+// First output pixel of pixel tile tile_m: tiles are MT consecutive pixels, except on x-blocked maps (128-wide: lg_xb = 1),
+// where the 1 << lg_xb tiles of a row band are (MT / cw) x cw blocks side by side.
+__device__ __forceinline__ int dconv_tile_m0(const DConvArgs& a, int tile_m, int mt) {
+    const int xb = tile_m & ((1 << a.lg_xb) - 1);
+    return (tile_m - xb) * mt + xb * a.cw;
 }
 
 template <int MBK>      // 8: 128-row tile, 4: 64-row tile (small grids)
@@ -200,8 +209,10 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
     // are issued BEFORE the stores of row mb, so waiting for them does not wait for those stores.
     const float* zp = a.zero;
     const bool any_load = e_res || accumulate || e_rowbias;
+    // first pixel of block row mb: 16 consecutive pixels; x-blocked tiles (xskip > 0) skip to the next image row every cw = 64 rows
+    const int xskip = uni(a.xskip);
     auto row_loads = [&](int mb, f32x4v (&rv)[2], f32x4v (&cv)[2], f32x4v (&tb)[2]) {
-        const int row_base = m0 + mb * 16;
+        const int row_base = m0 + mb * 16 + (mb >> 2) * xskip;
         const int gm = min(row_base + r16, M - 1);
         const long long coff = (long long)gm * ldc, roff = (long long)gm * ldres;
         const long long toff = (long long)((rb_uniform ? min(row_base, M - 1) : gm) / rows_per_img) * ld_rowbias;
@@ -214,7 +225,7 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
         }
     };
     auto row_store = [&](int mb, const f32x4v (&rv)[2], const f32x4v (&cv)[2], const f32x4v (&tb)[2]) {
-        const int row_base = m0 + mb * 16;
+        const int row_base = m0 + mb * 16 + (mb >> 2) * xskip;
         const int gm = min(row_base + r16, M - 1);
         const bool ok = row_base + r16 < M;
         const long long coff = (long long)gm * ldc;
@@ -256,7 +267,7 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
         const int fine = fine4 ? a.N >> 2 : a.N >> 3, chunks = e.gn_hw >> 6;
 #pragma unroll
         for (int r = 0; r < RUNS; ++r) {
-            const int row0 = m0 + r * 64;
+            const int row0 = m0 + r * (64 + xskip);      // a 64-row run is 64 consecutive pixels of one image either way
             if (row0 >= a.M) continue;
             const int img = row0 / e.gn_hw, chunk = (row0 - img * e.gn_hw) >> 6;
 #pragma unroll
@@ -314,12 +325,12 @@ __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
     const int tiles_n = a.N >> 7;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_m = bid / tiles_n, tile_n = bid - tile_m * tiles_n;
-    const int m0 = tile_m * MT, n0 = tile_n * 128;
+    const int m0 = dconv_tile_m0(a, tile_m, MT), n0 = tile_n * 128;
     const int split = blockIdx.y;
     const int c_beg = split * a.chunks_per_split;               // stages: chunks (conv) or groups of TAPS chunks (PW)
     const int c_end = min(a.chunks, c_beg + a.chunks_per_split);
 
-    const int W2 = a.pitch;          // >= W + 2 (columns beyond W + 1 are never read)
+    const int W2 = a.pitch;          // >= cw + 2 (columns beyond cw + 1 are never read)
     const float* zp = a.zero;
 
     // source pixel of every item this thread stages (-1: zero padding / beyond the batch)
@@ -334,6 +345,7 @@ __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
         const int HW = a.H * a.W;
         const int img0 = m0 / HW;
         const int oy0 = (m0 - img0 * HW) / a.W;     // 0 when a tile holds whole images
+        const int ox0 = m0 - img0 * HW - oy0 * a.W;  // 0 unless the map is x-blocked
         const int seg_px = (a.rps + 2) * W2;
 #pragma unroll
         for (int i = 0; i < NH; ++i) {
@@ -341,7 +353,7 @@ __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
             const int seg = px / seg_px;
             const int rem = px - seg * seg_px;
             const int hr = rem / W2, hx = rem - hr * W2;
-            const int img = img0 + seg, iy = oy0 + hr - 1, ix = hx - 1;
+            const int img = img0 + seg, iy = oy0 + hr - 1, ix = ox0 + hx - 1;
             const bool ok = seg < a.nseg && img < a.B && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
             hoff[i] = ok ? (img * a.H + iy) * a.W + ix : -1;
         }
@@ -383,9 +395,9 @@ __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
         if constexpr (PW) {
             abase[mb] = ml;
         } else {
-            const int seg = ml / (a.rps * a.W);
-            const int rem = ml - seg * (a.rps * a.W);
-            const int ry = rem / a.W, ox = rem - ry * a.W;
+            const int seg = ml / (a.rps * a.cw);
+            const int rem = ml - seg * (a.rps * a.cw);
+            const int ry = rem / a.cw, ox = rem - ry * a.cw;
             abase[mb] = (seg * (a.rps + 2) + ry) * W2 + ox;
         }
     }
@@ -491,12 +503,12 @@ __global__ void __launch_bounds__(256, 2) dconv_lp_kernel(const DConvArgs a) {
     const int tiles_n = a.N >> 7;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_m = bid / tiles_n, tile_n = bid - tile_m * tiles_n;
-    const int m0 = tile_m * MT, n0 = tile_n * 128;
+    const int m0 = dconv_tile_m0(a, tile_m, MT), n0 = tile_n * 128;
     const int split = blockIdx.y;
     const int c_beg = split * a.chunks_per_split;
     const int c_end = min(a.chunks, c_beg + a.chunks_per_split);
 
-    const int W2 = a.pitch;          // >= W + 2 (columns beyond W + 1 are never read)
+    const int W2 = a.pitch;          // >= cw + 2 (columns beyond cw + 1 are never read)
     const unsigned char* zp = reinterpret_cast<const unsigned char*>(a.zero);
     const unsigned char* p1 = reinterpret_cast<const unsigned char*>(a.x1);
     const unsigned char* p2 = reinterpret_cast<const unsigned char*>(a.x2);
@@ -510,6 +522,7 @@ __global__ void __launch_bounds__(256, 2) dconv_lp_kernel(const DConvArgs a) {
         const int HW = a.H * a.W;
         const int img0 = m0 / HW;
         const int oy0 = (m0 - img0 * HW) / a.W;
+        const int ox0 = m0 - img0 * HW - oy0 * a.W;
         const int seg_px = (a.rps + 2) * W2;
 #pragma unroll
         for (int i = 0; i < NRG; ++i) {
@@ -517,7 +530,7 @@ __global__ void __launch_bounds__(256, 2) dconv_lp_kernel(const DConvArgs a) {
             const int seg = px / seg_px;
             const int rem = px - seg * seg_px;
             const int hr = rem / W2, hx = rem - hr * W2;
-            const int img = img0 + seg, iy = oy0 + hr - 1, ix = hx - 1;
+            const int img = img0 + seg, iy = oy0 + hr - 1, ix = ox0 + hx - 1;
             const bool ok = seg < a.nseg && img < a.B && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
             hpix[i] = ok ? (img * a.H + iy) * a.W + ix : -1;
             sslot[i] = ((lane & 3) ^ lds_swz(px)) << 4;
@@ -550,9 +563,9 @@ __global__ void __launch_bounds__(256, 2) dconv_lp_kernel(const DConvArgs a) {
 #pragma unroll
     for (int mb = 0; mb < MBK; ++mb) {
         const int ml = mb * 16 + r16;
-        const int seg = ml / (a.rps * a.W);
-        const int rem = ml - seg * (a.rps * a.W);
-        const int ry = rem / a.W, ox = rem - ry * a.W;
+        const int seg = ml / (a.rps * a.cw);
+        const int rem = ml - seg * (a.rps * a.cw);
+        const int ry = rem / a.cw, ox = rem - ry * a.cw;
         abase[mb] = (seg * (a.rps + 2) + ry) * W2 + ox;
     }
 
@@ -797,7 +810,8 @@ __global__ void __launch_bounds__(256, CB == 2 ? 3 : 2) dwgrad_kernel(const DWgr
     constexpr int NXI = XLP ? 5 : WG_NB;        // limb planes: 48 rows x 3 limbs x 8 sixteen-byte slots = 1152 items
     unsigned xoff[NXI];     // byte offset from pixel (img, oy0 + ky - 1, ox0 - 1), channel ci0
     int xmeta[NXI];         // bits 0-4: staged row of the item (31: never valid); bit 5: column valid when the K tile
-                            // starts at ox0 = 0, bit 6: at ox0 = 32 (W = 64)
+                            // starts at ox0 = 0, bit 6: when it ends the row (ox0 = W - 32 > 0: W = 64, 128), bit 7: in
+                            // between (W = 128: ox0 = 32, 64 - every staged column lies inside the image)
     int xdst[NXI];          // limb planes: LDS byte offset of the item inside Bs
 #pragma unroll
     for (int i = 0; i < NXI; ++i) {
@@ -807,13 +821,13 @@ __global__ void __launch_bounds__(256, CB == 2 ? 3 : 2) dwgrad_kernel(const DWgr
             const int px = rem >> 3, t = rem & 7;
             const int hr = px / a.hw_w, hc = px - hr * a.hw_w;
             xoff[i] = (unsigned)((hr * a.W + hc) * xc * 6 + ((t >> 2) * 3 + l) * 64 + (t & 3) * 16);
-            xmeta[i] = ((id < 1152 && hr < a.hrows) ? hr : 31) | ((hc >= 1 && hc <= a.W) ? 32 : 0) | ((hc + 31 < a.W) ? 64 : 0);
+            xmeta[i] = ((id < 1152 && hr < a.hrows) ? hr : 31) | ((hc >= 1 && hc <= a.W) ? 32 : 0) | (hc <= 32 ? 64 : 0) | 128;
             xdst[i] = l * WG_BLIMB + px * WG_RS + t * 16;
         } else {
             const int px = ra + 16 * i;
             const int hr = px / a.hw_w, hc = px - hr * a.hw_w;
             xoff[i] = (unsigned)(((hr * a.W + hc) * xc + qa * 4) * 4);
-            xmeta[i] = (hr < a.hrows ? hr : 31) | ((hc >= 1 && hc <= a.W) ? 32 : 0) | ((hc + 31 < a.W) ? 64 : 0);
+            xmeta[i] = (hr < a.hrows ? hr : 31) | ((hc >= 1 && hc <= a.W) ? 32 : 0) | (hc <= 32 ? 64 : 0) | 128;
             xdst[i] = 0;
         }
     }
@@ -829,7 +843,7 @@ __global__ void __launch_bounds__(256, CB == 2 ? 3 : 2) dwgrad_kernel(const DWgr
         const int iy0 = oy0 + ky - 1;
         unsigned rowmask = 0;                       // bit r: staged row r lies inside the image
         for (int rr = 0; rr < a.hrows; ++rr) rowmask |= (iy0 + rr >= 0 && iy0 + rr < a.H) ? 1u << rr : 0u;
-        const int colsel = 5 + (ox0 >> 5);
+        const int colsel = ox0 == 0 ? 5 : (ox0 + 32 >= a.W ? 6 : 7);
         // limb planes: 6 bytes per element, the tile's first 32-channel chunk at (ci0 / 32) * 192 bytes into the pixel
         const unsigned char* xb8 = reinterpret_cast<const unsigned char*>(xsrc) +
                                    (XLP ? ((long long)((img * a.H + iy0) * a.W + ox0 - 1) * xc * 6 + (ci0 >> 5) * 192)
@@ -982,7 +996,7 @@ __global__ void __launch_bounds__(512) dwgrad_ws_kernel(const DWgradArgs a) {
             const int px = ra + 16 * i;
             const int hr = px / a.hw_w, hc = px - hr * a.hw_w;
             xoff[i] = (unsigned)(((hr * a.W + hc) * xc + qa * 4) * 4);
-            xmeta[i] = (hr < a.hrows ? hr : 31) | ((hc >= 1 && hc <= a.W) ? 32 : 0) | ((hc + 31 < a.W) ? 64 : 0);
+            xmeta[i] = (hr < a.hrows ? hr : 31) | ((hc >= 1 && hc <= a.W) ? 32 : 0) | (hc <= 32 ? 64 : 0) | 128;
         }
         unsigned aoff[CB];
 #pragma unroll
@@ -996,7 +1010,7 @@ __global__ void __launch_bounds__(512) dwgrad_ws_kernel(const DWgradArgs a) {
             const int iy0 = oy0 + ky - 1;
             unsigned rowmask = 0;
             for (int rr = 0; rr < a.hrows; ++rr) rowmask |= (iy0 + rr >= 0 && iy0 + rr < a.H) ? 1u << rr : 0u;
-            const int colsel = 5 + (ox0 >> 5);
+            const int colsel = ox0 == 0 ? 5 : (ox0 + 32 >= a.W ? 6 : 7);
             const unsigned char* xb8 = reinterpret_cast<const unsigned char*>(xsrc) + ((long long)((img * a.H + iy0) * a.W + ox0 - 1) * xc + ci0) * 4;
             const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(xb8), 0, 0x7fffffff, 0x00020000);
             const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
@@ -1711,9 +1725,18 @@ int plan_split(DConvArgs& a, const PsldEpilogue& e, float* y, int ldy, void* wor
 // nothing in an interleaved A/B (profiles/r03/ab_w8.txt: 181.1 vs 181.6 TFLOP/s at B=128, 58.5 vs 60.0 at B=16): the
 // conflict cycles sat in the shadow of the MFMAs; what holds these launches at half the pipe is their grid (256
 // workgroups of 64 rows at B=128: one per CU).
-int dconv_pitch(int w, int mt) { return (w == 8 && mt == 64) ? 16 : w + 2; }
+int dconv_pitch(int w, int mt) { return (w == 8 && mt == 64) ? 16 : (w == 128 ? 64 : w) + 2; }
 
+// 128-wide maps: a 128-pixel tile of whole rows would be one row with a 3 x 130 = 390-pixel halo, beyond the 288 rows of
+// the LDS image; they run as 2 x 64 blocks instead (halo 4 x 66 = 264), two per row band, 128-row tiles only.
 bool dconv_geometry(int h, int w, int* nseg, int* rps, int* halo_px, int mt = 128) {
+    if (w == 128) {
+        if (mt != 128 || h % 2) return false;
+        *nseg = 1;
+        *rps = 2;
+        *halo_px = 4 * dconv_pitch(w, mt);
+        return true;
+    }
     if (w != 8 && w != 16 && w != 32 && w != 64) return false;
     const int hw = h * w;
     if (hw >= mt) {
@@ -1727,6 +1750,13 @@ bool dconv_geometry(int h, int w, int* nseg, int* rps, int* halo_px, int mt = 12
     }
     *halo_px = *nseg * (*rps + 2) * dconv_pitch(w, mt);
     return *halo_px <= 9 * 32;
+}
+
+// Region width / regions per row band / row skip of a 3x3 limb convolution (after dconv_geometry)
+void dconv_regions(DConvArgs& a) {
+    a.cw = a.W == 128 ? 64 : a.W;
+    a.lg_xb = a.W == 128 ? 1 : 0;
+    a.xskip = a.W - a.cw;
 }
 
 // Tile height of a 3x3 limb convolution: 64-row tiles when 128-row tiles leave the grid short of 384 workgroups - the same
@@ -1798,6 +1828,7 @@ extern "C" int psld_conv3x3_split_f32(const float* x1, int c1, const float* x2, 
     const int mt = dconv_tile_rows(a, h, w);
     dconv_geometry(h, w, &a.nseg, &a.rps, &halo_px, mt);
     a.pitch = dconv_pitch(w, mt);
+    dconv_regions(a);
     a.zero = psld_detail_zero_page("psld_conv3x3_split_f32");
     if (!a.zero) return PSLD_ERR_LAUNCH;
     PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw == h * w && e.gn_hw % 64 == 0 && !e.accumulate),
@@ -1855,6 +1886,7 @@ extern "C" int psld_conv3x3_limb_f32(const void* x1, int c1, const void* x2, int
     const int mt = dconv_tile_rows(a, h, w);
     dconv_geometry(h, w, &a.nseg, &a.rps, &halo_px, mt);
     a.pitch = dconv_pitch(w, mt);
+    dconv_regions(a);
     a.zero = psld_detail_zero_page("psld_conv3x3_limb_f32");
     if (!a.zero) return PSLD_ERR_LAUNCH;
     PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw == h * w && e.gn_hw % 64 == 0 && !e.accumulate),
@@ -1878,7 +1910,7 @@ extern "C" int psld_conv3x3_limb_f32(const void* x1, int c1, const void* x2, int
 
 extern "C" int psld_conv3x3_wgrad_split_supported(int cout, int cin, int batch, int h, int w) {
     return cout > 0 && cin > 0 && cout % 64 == 0 && cin % 64 == 0 && batch > 0 &&
-           (w == 8 || w == 16 || w == 32 || w == 64) && (h * w) % 32 == 0;
+           (w == 8 || w == 16 || w == 32 || w == 64 || w == 128) && (h * w) % 32 == 0;
 }
 
 extern "C" int psld_conv3x3_wgrad_split_cout_tile(int cout) { return cout % 128 ? 64 : 128; }

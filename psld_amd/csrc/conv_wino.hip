@@ -49,7 +49,7 @@ struct WinoArgs {
     float* C;
     int ldc;
     int nseg, rps;          // image segments per 128-pixel tile and output rows per segment (dconv_geometry, mt = 128)
-    int cw;                 // wino_conv8s_kernel: width of a workgroup's pixel block (W, or 32 on 64-wide maps: rps = 4)
+    int cw;                 // wino_conv8s_kernel: width of a workgroup's pixel block (W, or 32 on 64- and 128-wide maps: rps = 4)
     PsldEpilogue e;
     const float* zero;
     int nmajor;
@@ -201,7 +201,8 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     const int n0 = tile_n * 128;
 
     // Region of this workgroup: nseg images (maps smaller than 128 pixels) or one rps x cw block of an image - cw = W, or 32
-    // for 64-wide maps, whose full-width tile (2 rows x 64) would need a 264-pixel halo where the two raw images hold 256.
+    // for 64- and 128-wide maps, whose full-width tile (2 rows x 64, 1 row x 128) would need a 264- / 390-pixel halo where
+    // the two raw images hold 256.
     const int HW = a.H * a.W;
     const int W2 = a.cw + 2;
     const int tiles_x = a.cw >> 1;
@@ -543,6 +544,10 @@ int wino_cu_count() {
 }
 
 bool wino_geometry(int h, int w, int* nseg, int* rps, int* halo_px) {
+    if (w == 128) {     // 128-wide maps: 4 x 32 pixel blocks only (the 64-wide rule below, four blocks per row band)
+        *nseg = 1; *rps = 4; *halo_px = 6 * 34;
+        return h % 4 == 0;
+    }
     if (w != 8 && w != 16 && w != 32 && w != 64) return false;
     if (h % 2) return false;
     const int hw = h * w;
@@ -696,7 +701,7 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
     a.nmajor = 1;       // channel-tile-major: an XCD streams ONE 128-channel slice of U at a time (pixel-tile-major measured 1-2 % slower)
     const char* name = "psld_conv3x3_wino_f32";
     a.cw = w;
-    if (w == 64) {      // 4 x 32 pixel blocks: the 32x32 level's halo (6 x 34 = 204 pixels)
+    if (w >= 64) {      // 4 x 32 pixel blocks: the 32x32 level's halo (6 x 34 = 204 pixels); W / 32 blocks per row band
         a.cw = 32; a.rps = 4; a.nseg = 1;
         halo_px = 6 * 34;
     }

@@ -64,8 +64,9 @@ struct WWgradArgs {
     const float* x2;        // second source of a channel concatenation (or null): c_in tiles beyond cin read it
     int cin2;
     int H, W;
-    int lg_tw, th_mask, tw_mask;    // tiles per row = W / 2 = 1 << lg_tw; tile rows per image - 1; tiles per row - 1
+    int lg_tw, th_mask, tw_mask;    // tiles per K-tile row = min(W / 2, 32) = 1 << lg_tw; tile rows per image - 1; that - 1
     int rows_per_kt;        // tile rows of a K tile = 32 >> lg_tw
+    int lg_kpr, kpr_mask;   // 128-wide maps: a K tile is half a tile row - K tiles per tile row = 1 << lg_kpr (else 1, 0)
     int cout_tiles, cin_tiles;
     int ktiles, ktiles_per_split;       // the last split may be shorter (never empty)
     float* slabs;           // [split][16][cout][cin_total]
@@ -177,7 +178,7 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
         const int qx = pt & 31, kx0 = pt >> 5;
         unsigned xoff[4];       // byte offset of tile k's patch origin (pixel row 2 dR, column 2 tx) from the K tile's origin
         int xdr[4];             // tile row of the item inside the K tile
-        unsigned xcol[4];       // bit 0: column c1 inside the image, bit 1: column c2
+        unsigned xcol[4];       // bit 0: column c1 inside the image, bit 1: column c2 (for the K tiles at the row's edges)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int k = kx0 + 8 * i;
@@ -207,19 +208,21 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
             f32x4 sx[4][4];         // [item][r1c1, r1c2, r2c1, r2c2]
             f32x4 sy[NY][NL];
             auto load_tile = [&](int kt) {
-                const int R0 = kt * a.rows_per_kt;                   // global tile row (image * tile rows + ty) of the K tile
-                // pixel row 2 R0 - 1 + r, column -1 + c of the first tile: may lie before the tensor; never dereferenced there
-                const float* xb = xsrc + ((long long)(2 * R0 - 1) * a.W - 1) * xc + ci0;
+                const int kc = kt & a.kpr_mask;                      // column block of the K tile in its tile row (0 unless W = 128)
+                const int R0 = (kt >> a.lg_kpr) * a.rows_per_kt;     // global tile row (image * tile rows + ty) of the K tile
+                const int px0 = kc * 64;                             // its first pixel column
+                // pixel row 2 R0 - 1 + r, column px0 - 1 + c of the first tile: may lie before the tensor; never dereferenced there
+                const float* xb = xsrc + ((long long)(2 * R0 - 1) * a.W + px0 - 1) * xc + ci0;
                 const __amdgpu_buffer_rsrc_t r11 = brsrc(xb + (long long)(xr1 * a.W + xc1) * xc), r12 = brsrc(xb + (long long)(xr1 * a.W + xc2) * xc),
                                              r21 = brsrc(xb + (long long)(xr2 * a.W + xc1) * xc), r22 = brsrc(xb + (long long)(xr2 * a.W + xc2) * xc);
-                const float* yb = a.dy + ((long long)(2 * R0) * a.W) * a.lddy + co0;
+                const float* yb = a.dy + ((long long)(2 * R0) * a.W + px0) * a.lddy + co0;
                 const __amdgpu_buffer_rsrc_t q00 = brsrc(yb + (long long)(yr1 * a.W + yc1) * a.lddy), q01 = brsrc(yb + (long long)(yr1 * a.W + 1) * a.lddy),
                                              q10 = brsrc(yb + (long long)(a.W + yc1) * a.lddy), q11 = brsrc(yb + (long long)(a.W + 1) * a.lddy);
                 return [=, &sx, &sy](auto is_x, int i) {
                     if constexpr (decltype(is_x)::value) {
                         const int ty = (R0 + xdr[i]) & a.th_mask;
                         const bool row1 = !(need_top && ty == 0), row2 = !(need_bot && ty == a.th_mask);
-                        const bool c1 = (xcol[i] & 1u) != 0, c2 = (xcol[i] & 2u) != 0;
+                        const bool c1 = (xcol[i] & 1u) != 0 || kc != 0, c2 = (xcol[i] & 2u) != 0 || kc != a.kpr_mask;
                         sx[i][0] = bload(r11, (row1 && c1) ? xoff[i] : 0xffffffffu);
                         sx[i][1] = bload(r12, (row1 && c2) ? xoff[i] : 0xffffffffu);
                         sx[i][2] = bload(r21, (row2 && c1) ? xoff[i] : 0xffffffffu);
@@ -451,7 +454,7 @@ int ilog2(int v) {
 
 extern "C" int psld_conv3x3_wgrad_wino_supported(int cout, int cin, int cin2, int batch, int h, int w) {
     if (cout <= 0 || cin <= 0 || cin2 < 0 || batch <= 0 || cout % 128 || cin % WW_CI || cin2 % WW_CI) return 0;
-    if (h != w || !(w == 8 || w == 16 || w == 32 || w == 64)) return 0;
+    if (h != w || !(w == 8 || w == 16 || w == 32 || w == 64 || w == 128)) return 0;
     return ((long long)batch * h * w / 4) % 32 == 0;
 }
 
@@ -491,8 +494,11 @@ extern "C" int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, 
     WWgradArgs a{};
     a.dy = dy; a.lddy = lddy; a.x = x; a.cin = cin; a.x2 = x2; a.cin2 = cin2;
     a.H = h; a.W = w;
-    a.lg_tw = ilog2(w / 2); a.tw_mask = w / 2 - 1; a.th_mask = h / 2 - 1;
+    // a K tile = 32 Winograd tiles: whole tile rows up to 64-wide maps, half a tile row (32 tiles = 64 pixel columns) at 128
+    const int tw = w / 2 < 32 ? w / 2 : 32;
+    a.lg_tw = ilog2(tw); a.tw_mask = tw - 1; a.th_mask = h / 2 - 1;
     a.rows_per_kt = 32 >> a.lg_tw;
+    a.lg_kpr = ilog2(w / 2 / tw); a.kpr_mask = w / 2 / tw - 1;
     const int co_tile = ww_co_tile(cout);
     a.cout_tiles = cout / co_tile; a.cin_tiles = (cin + cin2) / WW_CI;
     a.ktiles = (int)ktiles; a.ktiles_per_split = (int)per_split;
