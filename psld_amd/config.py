@@ -12,7 +12,8 @@ Key names and default values follow main/configs/dataset/cifar10/cifar10_psld.ya
 scripts_psld/sota/uncond/cifar10/train_uncond_psld.sh:6-21 and ``celeba64_sota``
 those of scripts_psld/sota/uncond/celeba64/train_uncond_psld.sh:7-20; ``afhqv2_128`` is
 main/configs/dataset/afhqv2/afhqv2128_psld.yaml with the overrides of
-scripts_psld/ablations/uncond/afhqv2/train_uncond_psld.sh.
+scripts_psld/ablations/uncond/afhqv2/train_uncond_psld.sh, and ``afhqv2_128_inpaint`` adds those of
+scripts_psld/sota/cond/afhqv2/sample_inpaint_psld.sh.
 """
 from __future__ import annotations
 
@@ -155,6 +156,29 @@ def afhqv2_128() -> Config:
     c.training.optimizer.lr = 1e-4
     c.training.optimizer.warmup = 5000
     c.training.batch_size = 8
+    return c
+
+
+def afhqv2_128_inpaint() -> Config:
+    """The SOTA AFHQv2-128 inpainting network: ``afhqv2_128`` with the score-net, SDE and evaluation overrides of
+    scripts_psld/sota/cond/afhqv2/sample_inpaint_psld.sh (nf = 160, gamma = 0, 250 quadratic ip_em_sde steps)."""
+    c = afhqv2_128()
+    sf = c.model.score_fn
+    sf.in_ch, sf.out_ch = 6, 3
+    sf.nf = 160
+    sf.ch_mult = [1, 2, 2, 3, 3]
+    sf.num_res_blocks = 2
+    sf.attn_resolutions = [8, 16]
+    sf.dropout = 0.2
+    sde = c.model.sde
+    sde.beta_min, sde.beta_max = 8.0, 8.0
+    sde.nu, sde.gamma, sde.kappa, sde.decomp_mode = 4.0, 0.0, 0.04, "lower"
+    ev = c.evaluation
+    ev.sampler.name = "ip_em_sde"
+    ev.stride_type = "quadratic"
+    ev.n_discrete_steps = 250
+    ev.batch_size = 16
+    ev.sample_from = "target"
     return c
 
 

@@ -43,8 +43,8 @@ struct WinoArgs {
     const float* x2;
     int C1, C2;
     int B, H, W;
-    const u32x4* ufrag;     // [N/128][8 waves][chunk][16 pos][3 limbs][64 lanes]
-    int N, M;               // cout (multiple of 128), B*H*W
+    const u32x4* ufrag;     // [N/16 = 128-channel tile x 8 waves][chunk][16 pos][3 limbs][64 lanes] (a tail tile: fewer waves)
+    int N, M;               // cout (multiple of 128; TAIL: of 32, >= 128 - the last channel tile is cut short), B*H*W
     int chunks;             // (C1 + C2) / 32
     float* C;
     int ldc;
@@ -177,7 +177,10 @@ __global__ void wino_pack_batch_kernel(const long long* __restrict__ tab, int nt
 // front of every weight-fragment load of the half-phase, and the first s_waitcnt of the MFMA stream waits for them.
 // Issued behind the last fragment wait of the previous half-phase they have that phase's transform and the barrier to
 // land before anything younger is waited for.
-template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2>
+// TAIL (cout % 128 != 0 only): the last channel tile holds 32, 64 or 96 channels; the waves beyond cout take their share of the
+// staging and the transform (and the barriers) but load no fragments, issue no MFMAs and leave before the epilogue.  Every
+// live wave does exactly what it does in a full tile, so a channel's result does not depend on how many share its launch.
+template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false>
 __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NI = 4;                     // raw image: 256 halo pixels
@@ -187,7 +190,7 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tiles_n = a.N >> 7;
+    const int tiles_n = TAIL ? (a.N + 127) >> 7 : a.N >> 7;
     const int nsp = a.ksplit > 1 ? a.ksplit : 1;
     const int per_range = (int)gridDim.x / nsp;                  // workgroups of one channel-chunk range
     const int vb = xcd_remap(blockIdx.x, gridDim.x);
@@ -199,6 +202,7 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     const int tile_n = a.nmajor ? bid / tiles_m : bid % tiles_n;
     const int tile_m = a.nmajor ? bid - tile_n * tiles_m : bid / tiles_n;
     const int n0 = tile_n * 128;
+    const bool live = !TAIL || n0 + wave * 16 < a.N;             // wave-uniform; always true without TAIL
 
     // Region of this workgroup: nseg images (maps smaller than 128 pixels) or one rps x cw block of an image - cw = W, or 32
     // for 64- and 128-wide maps, whose full-width tile (2 rows x 64, 1 row x 128) would need a 264- / 390-pixel halo where
@@ -372,9 +376,11 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     if constexpr ((ABL & 4) == 0 && (ABL & 256) == 0) { if (vr != 0) __builtin_amdgcn_s_setprio(1); }
 
     load_raw(ch0);
-    load_b(0, bq[0]);
-    load_b(1, bq[1]);
-    if (LA > 2) load_b(2, bq[2]);
+    if (live) {
+        load_b(0, bq[0]);
+        load_b(1, bq[1]);
+        if (LA > 2) load_b(2, bq[2]);
+    }
     store_raw(0, ch0);
     if constexpr (ERAW) load_raw(ch0 + min(1, kch - 1));
     __syncthreads();
@@ -399,7 +405,7 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
         if (vr == 0 && !(ABL & 1)) transform(I1{}, I0{}, c & 1);             // waves 0-3: transform, then MFMAs
         __builtin_amdgcn_sched_barrier(0);
         if (vr == 0) stamp(c, 1);
-        mfma_half(I0{}, c);
+        if (live) mfma_half(I0{}, c);
         __builtin_amdgcn_sched_barrier(0);
         if (vr != 0) stamp(c, 1);
         if (vr != 0 && !(ABL & 1)) transform(I1{}, I1{}, c & 1);             // waves 4-7: MFMAs, then transform
@@ -412,7 +418,7 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
         if (vr == 0 && !(ABL & 1)) transform(I0{}, I0{}, (c + 1) & 1);
         __builtin_amdgcn_sched_barrier(0);
         if (vr == 0) stamp(c, 5);
-        mfma_half(I1{}, c);
+        if (live) mfma_half(I1{}, c);
         __builtin_amdgcn_sched_barrier(0);
         if (vr != 0) stamp(c, 5);
         if constexpr (ERAW) load_raw(ch0 + min(c + 2, kch - 1));
@@ -423,6 +429,7 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     }
 
     // ---- output transform + fused epilogue (as wino_conv_kernel) -----------------------------------------------------
+    if (!live) return;      // no barrier follows
     const PsldEpilogue& e = a.e;
     const int cn = n0 + wave * 16 + 4 * kq;
     const f32x4v zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -511,13 +518,13 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
 #include "conv_wino_abl.inc"
 #endif
 
-template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2>
+template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false>
 int launch_wino8s(const WinoArgs& a, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)VBYTES + 2 * (size_t)4 * 64 * 128;
     static_assert(LDS <= 163840, "LDS budget");
     static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv8s_kernel<ABL, GNF, ERAW, LA>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
         if (e != hipSuccess) {
             psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
@@ -525,8 +532,8 @@ int launch_wino8s(const WinoArgs& a, hipStream_t stream, const char* name) {
         }
         configured = true;
     }
-    dim3 grid((unsigned)(cdiv(a.M, 128) * (a.N / 128) * (a.ksplit > 1 ? a.ksplit : 1)));
-    hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA>), grid, dim3(WINO_THREADS), LDS, stream, a);
+    dim3 grid((unsigned)(cdiv(a.M, 128) * cdiv(a.N, 128) * (a.ksplit > 1 ? a.ksplit : 1)));
+    hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL>), grid, dim3(WINO_THREADS), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
 }
@@ -571,17 +578,18 @@ bool wino_geometry(int h, int w, int* nseg, int* rps, int* halo_px) {
 // + 16 KB: the kernels prefetch up to three positions (3 x 3 KB per 16-channel block) past the last fragment
 extern "C" long long psld_conv3x3_wino_frag_bytes(int cout, int cin) { return (long long)cout * cin * 16 * 6 + 16384; }
 
+// cout: a multiple of 128, or of 32 from 128 up (the last channel tile cut short: wino_conv8s_kernel<..., TAIL = true>)
 extern "C" int psld_conv3x3_wino_supported(int c1, int c2, int batch, int h, int w, int cout) {
     int nseg, rps, halo;
-    return c1 > 0 && c2 >= 0 && c1 % 32 == 0 && c2 % 32 == 0 && cout > 0 && cout % 128 == 0 && batch > 0 &&
+    return c1 > 0 && c2 >= 0 && c1 % 32 == 0 && c2 % 32 == 0 && cout >= 128 && cout % 32 == 0 && batch > 0 &&
            wino_geometry(h, w, &nseg, &rps, &halo);
 }
 
 extern "C" int psld_pack_conv3x3_wino(const float* w_oihw, void* ufrag, int cout, int cin, int dgrad, hipStream_t stream) {
     PSLD_CHECK_ARG(w_oihw && ufrag && aligned16(ufrag), "psld_pack_conv3x3_wino: null / unaligned pointer");
     const int n_out = dgrad ? cin : cout, k_in = dgrad ? cout : cin;
-    PSLD_CHECK_ARG(n_out > 0 && k_in > 0 && n_out % 128 == 0 && k_in % 32 == 0,
-                   "psld_pack_conv3x3_wino: needs out channels %%128 and in channels %%32 (got %d, %d)", n_out, k_in);
+    PSLD_CHECK_ARG(n_out >= 128 && k_in > 0 && n_out % 32 == 0 && k_in % 32 == 0,
+                   "psld_pack_conv3x3_wino: needs out channels %%32 (>= 128) and in channels %%32 (got %d, %d)", n_out, k_in);
     const long long items = (long long)(n_out / 16) * (k_in / 32) * 64;
     const int blocks = (int)((items + 63) / 64 < 16384 ? (items + 63) / 64 : 16384);
     if (dgrad) hipLaunchKernelGGL(wino_pack_kernel, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag),
@@ -625,7 +633,7 @@ extern "C" int psld_conv3x3_wino_f32(const float* x1, int c1, const float* x2, i
 // K splits a launch of this shape takes when it is given a workspace (1: none) and the bytes that workspace needs
 extern "C" int psld_conv3x3_wino_ksplit(int c1, int c2, int batch, int h, int w, int cout) {
     if (!psld_conv3x3_wino_supported(c1, c2, batch, h, w, cout)) return 1;
-    const int tiles = cdiv((long long)batch * h * w, 128) * (cout / 128), chunks = (c1 + c2) / 32;
+    const int tiles = cdiv((long long)batch * h * w, 128) * cdiv(cout, 128), chunks = (c1 + c2) / 32;
     const int cus = wino_cu_count();
     int ks = 1;
     // one workgroup per CU: a grid below half a round leaves CUs idle - split the channel chunks so that it fills one round
@@ -644,7 +652,8 @@ extern "C" int psld_conv3x3_wino_ws_f32(const float* x1, int c1, const float* x2
 }
 
 extern "C" int psld_conv3x3_wino_gn_supported(int c1, int c2, int batch, int h, int w, int cout) {
-    return psld_conv3x3_wino_supported(c1, c2, batch, h, w, cout) && h * w >= 128;      // one image per workgroup region
+    // one image per workgroup region; whole 128-channel tiles (no channel tail in the GroupNorm-fused staging)
+    return psld_conv3x3_wino_supported(c1, c2, batch, h, w, cout) && h * w >= 128 && cout % 128 == 0;
 }
 
 extern "C" int psld_conv3x3_wino_gn_f32(const float* x1, int c1, const float* scale1, const float* shift1, const float* x2,
@@ -691,8 +700,8 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
     wino_geometry(h, w, &a.nseg, &a.rps, &halo_px);
     a.e = make_epilogue(epi);
     const PsldEpilogue& e = a.e;
-    PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw == h * w && e.gn_hw % 64 == 0 && !e.accumulate),
-                   "psld_conv3x3_wino_f32: gn_part needs gn_hw = h*w, a multiple of 64, and no accumulation");
+    PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw == h * w && e.gn_hw % 64 == 0 && !e.accumulate && cout % 128 == 0),
+                   "psld_conv3x3_wino_f32: gn_part needs gn_hw = h*w, a multiple of 64, no accumulation and cout %% 128 == 0");
     PSLD_CHECK_ARG(ldy % 4 == 0 && aligned16(y) && (!e.res || (e.ldres % 4 == 0 && aligned16(e.res))) &&
                        (!e.bias || aligned16(e.bias)) && (!e.rowbias || (e.ld_rowbias % 4 == 0 && aligned16(e.rowbias))),
                    "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
@@ -720,11 +729,13 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
         s.C = reinterpret_cast<float*>(workspace);
         s.ldc = cout;
         s.e = make_epilogue(nullptr);
-        const int rc = gn ? launch_wino8s<0, true>(s, stream, "psld_conv3x3_wino_gn_f32") : launch_wino8s<0>(s, stream, name);
+        const int rc = gn ? launch_wino8s<0, true>(s, stream, "psld_conv3x3_wino_gn_f32")
+                          : (cout % 128 ? launch_wino8s<0, false, false, 2, true>(s, stream, name) : launch_wino8s<0>(s, stream, name));
         if (rc != PSLD_OK) return rc;
         return psld_detail_conv_reduce_epilogue(s.C, ks, a.M, cout, y, ldy, e, stream);
     }
     if (gn) return launch_wino8s<0, true>(a, stream, "psld_conv3x3_wino_gn_f32");
+    if (cout % 128) return launch_wino8s<0, false, false, 2, true>(a, stream, name);      // last channel tile cut short
 #ifdef PSLD_ABLATIONS      // libpsld_hip_abl.so only: the variants of conv_wino_abl.inc and the timing-only ablations (wrong results)
 #include "conv_wino_abl_dispatch.inc"
 #endif

@@ -136,7 +136,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t brsrc(const float* p) {
 // rows with the 64-byte granules swizzled by row & 3 for its 4-row transposed reads) passed the parity tests on the eight
 // shapes: 372.5 -> 364.8 us on 256->256 @32, 713 -> 712 on 512->256 @32, 461 -> 437 on 128->128 @64, +-0 on the 16x16 level
 // (profiles/r06/wwgrad_mfma32.txt) - the issue port alone is not the lever; removed again.
-template <int ABL = 0, int CO = 256>
+// TAIL (cout or c_in not a multiple of 128, multiples of 32 from 128 up): the last c_out / c_in tile is cut short.  The producers
+// load nothing for the channels beyond the tensor (masked buffer loads return zeros) and the consumers skip their slab rows and
+// columns; every channel that exists goes through the same loads, splits and MFMAs as in a full tile.
+template <int ABL = 0, int CO = 256, bool TAIL = false>
 __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
     using G = WWGeom<CO>;
     constexpr int WW_CO = CO, WW_RSA = G::RSA, WW_ALIMB = G::ALIMB, WW_IMG = G::IMG, NY = G::NY, CB = G::CB;
@@ -186,6 +189,9 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
             xoff[i] = (unsigned)((((2 * dr) * a.W + 2 * tx) * xc + qx * 4) * 4);
             xdr[i] = dr;
             xcol[i] = ((xc1 == 0 && tx == 0) ? 0u : 1u) | ((xc2 == 3 && tx == a.tw_mask) ? 0u : 2u);
+            if constexpr (TAIL) {
+                if (ci0 + 4 * qx >= xc) xoff[i] = 0xffffffffu;       // channel quad beyond its source: every load masked
+            }
         }
         // dY items: channel quad pt & (CO / 4 - 1), tile row k = pt / (CO / 4) + (32 / NY) i
         constexpr int QY = CO / 4, KSTEP = 32 / NY;
@@ -196,6 +202,9 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
             const int k = ky0 + KSTEP * i;
             const int tx = k & a.tw_mask, dr = k >> a.lg_tw;
             yoff[i] = (unsigned)((((2 * dr) * a.W + 2 * tx) * a.lddy + qy * 4) * 4);
+            if constexpr (TAIL) {
+                if (co0 + 4 * qy >= a.cout) yoff[i] = 0xffffffffu;   // channel quad beyond cout
+            }
         }
         const int lds_x = kx0 * WW_RSB + qx * 8, lds_y = ky0 * WW_RSA + qy * 8;
 
@@ -395,7 +404,8 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 const int co = co0 + wr * (CO / 2) + cb * 16 + 4 * g + v;
-                S[(long long)co * a.cin_total + ci_out + wc * 64 + nb * 16 + i16] = acc[cb][nb][v];
+                if (!TAIL || (co < a.cout && ci_out + wc * 64 + nb * 16 + i16 < a.cin_total))
+                    S[(long long)co * a.cin_total + ci_out + wc * 64 + nb * 16 + i16] = acc[cb][nb][v];
             }
 }
 
@@ -452,16 +462,20 @@ int ilog2(int v) {
 
 }  // namespace
 
+// cout, cin: multiples of 128, or of 32 from 128 up (wwgrad_ws_kernel<..., TAIL = true>); a second source starts on a c_in
+// tile (cin % 128 == 0) and is, like cin, a multiple of 32 from 128 up
+static bool ww_width_ok(int c) { return c >= 128 && c % 32 == 0; }
+
 extern "C" int psld_conv3x3_wgrad_wino_supported(int cout, int cin, int cin2, int batch, int h, int w) {
-    if (cout <= 0 || cin <= 0 || cin2 < 0 || batch <= 0 || cout % 128 || cin % WW_CI || cin2 % WW_CI) return 0;
+    if (batch <= 0 || cin2 < 0 || !ww_width_ok(cout) || !ww_width_ok(cin) || (cin2 && (cin % WW_CI || !ww_width_ok(cin2)))) return 0;
     if (h != w || !(w == 8 || w == 16 || w == 32 || w == 64 || w == 128)) return 0;
     return ((long long)batch * h * w / 4) % 32 == 0;
 }
 
 // K splits that fill the chip with one round of one-workgroup-per-CU tiles (0: shape not taken)
 extern "C" int psld_conv3x3_wgrad_wino_nsplit(int cout, int cin_total, int batch, int h, int w) {
-    if (cout % 128 || cin_total % WW_CI) return 0;
-    const int units = 16 * (cout / ww_co_tile(cout)) * (cin_total / WW_CI);
+    if (!ww_width_ok(cout) || !ww_width_ok(cin_total)) return 0;
+    const int units = 16 * (int)cdiv(cout, ww_co_tile(cout)) * (int)cdiv(cin_total, WW_CI);     // a tail tile counts as a tile
     const long long ktiles = (long long)batch * h * w / 4 / 32;
     static int cus[PSLD_MAX_DEVICES] = {};
     int& n = cus[psld_device_slot()];
@@ -500,7 +514,8 @@ extern "C" int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, 
     a.rows_per_kt = 32 >> a.lg_tw;
     a.lg_kpr = ilog2(w / 2 / tw); a.kpr_mask = w / 2 / tw - 1;
     const int co_tile = ww_co_tile(cout);
-    a.cout_tiles = cout / co_tile; a.cin_tiles = (cin + cin2) / WW_CI;
+    a.cout_tiles = (int)cdiv(cout, co_tile); a.cin_tiles = (int)cdiv(cin + cin2, WW_CI);
+    const bool tail = cout % co_tile || (cin + cin2) % WW_CI;
     a.ktiles = (int)ktiles; a.ktiles_per_split = (int)per_split;
     a.slabs = slabs; a.cout = cout; a.cin_total = cin + cin2;
     a.pos_override = -1;
@@ -517,7 +532,7 @@ extern "C" int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, 
         launched = true;                                                                                                            \
         break;
     bool launched = false;
-    switch (co_tile == 256 ? abl : 0) {
+    switch (co_tile == 256 && !tail ? abl : 0) {
         WW_ABL_CASE(1) WW_ABL_CASE(2) WW_ABL_CASE(3) WW_ABL_CASE(4) WW_ABL_CASE(8) WW_ABL_CASE(12) WW_ABL_CASE(16) WW_ABL_CASE(32) WW_ABL_CASE(64)
         default: break;
     }
@@ -530,13 +545,21 @@ extern "C" int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, 
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WWGeom<256>::LDS);
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WWGeom<128>::LDS);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WWGeom<128>::LDS);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WWGeom<256>::LDS);
         if (e != hipSuccess) {
             psld_set_error("psld_conv3x3_wgrad_wino_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
             return PSLD_ERR_LAUNCH;
         }
         configured = true;
     }
-    if (co_tile == 256)
+    if (tail && co_tile == 256)         // c_in tail only (cout % 256 == 0)
+        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 256, true>), grid, dim3(512), WWGeom<256>::LDS, stream, a);
+    else if (tail)
+        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 128, true>), grid, dim3(512), WWGeom<128>::LDS, stream, a);
+    else if (co_tile == 256)
         hipLaunchKernelGGL((wwgrad_ws_kernel<0, 256>), grid, dim3(512), WWGeom<256>::LDS, stream, a);
     else
         hipLaunchKernelGGL((wwgrad_ws_kernel<0, 128>), grid, dim3(512), WWGeom<128>::LDS, stream, a);

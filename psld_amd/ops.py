@@ -237,9 +237,11 @@ def conv3x3_wino_wanted(c1: int, c2: int, b: int, h: int, w: int, cout: int, spl
         return False
     if mode == 2:
         return True
-    tiles = (b * h * w // 128) * (cout // 128)
+    tiles = (b * h * w // 128) * -(-cout // 128)          # a channel tail (cout % 128, csrc/conv_wino.hip) counts as a tile
     ks = int(lib().psld_conv3x3_wino_ksplit(c1, c2, b, h, w, cout)) if split_ok else 1
-    return tiles * ks >= 256
+    # below one round the direct limb kernels win - where they take the shape; channel tails they do not take, and the
+    # alternative there is the fp32 tile engine
+    return tiles * ks >= 256 or (cout % 128 != 0 and not conv3x3_split_supported(c1, c2, b, h, w, cout))
 
 
 @functools.lru_cache(maxsize=None)
@@ -483,6 +485,8 @@ def conv3x3_wgrad_wino_wanted(cout: int, cin: int, cin2: int, b: int, h: int, w:
         return False
     if mode == 2:
         return True
+    if not (conv3x3_wgrad_split_supported(cout, cin, b, h, w) and (cin2 == 0 or conv3x3_wgrad_split_supported(cout, cin2, b, h, w))):
+        return True         # channel widths the direct kernels do not take (multiples of 32, not of 64): the tile engine is the alternative
     ns, _ = conv3x3_wgrad_wino_plan(cout, cin + cin2, b, h, w)
     return (b * h * w // 128) // ns >= 8
 
