@@ -38,9 +38,16 @@ const char* psld_last_error(void);
  *   PSLD_MATH_BF16X6 every operand is split exactly into three bf16 limbs (hi + mid + lo == x, all 24 mantissa
  *                    bits) and each product is the six leading limb products on v_mfma_f32_32x32x16_bf16; the three
  *                    dropped terms are < 2^-23 of the product, i.e. below fp32 rounding of the product itself.
- * Process-wide; the initial value comes from the environment variable PSLD_MATH ("f32" | "bf16x6"). */
+ *   PSLD_MATH_BF16X3 reduced-precision inference: bf16x6 for every launch, and the *_x3 entry points below (Winograd 3x3
+ *                    forward, pointwise forward GEMM) keep the first TWO limbs of each operand (hi = rne_bf16(x), lo =
+ *                    rne_bf16(x - hi): limbs 0 and 1 of the three-limb split, bit for bit) and the three products
+ *                    hi*hi + (hi*lo + lo*hi); the dropped terms are each < 2^-16 of the product (rel-L2 ~1e-5 on a whole
+ *                    network forward).  The library only stores this value: which launches use the two-limb entry
+ *                    points is the caller's choice (psld_amd: forwards that record no backward pass).
+ * Process-wide; the initial value comes from the environment variable PSLD_MATH ("f32" | "bf16x6" | "bf16x3"). */
 #define PSLD_MATH_F32 0
 #define PSLD_MATH_BF16X6 1
+#define PSLD_MATH_BF16X3 2
 int psld_set_math_mode(int mode);
 int psld_get_math_mode(void);
 
@@ -188,6 +195,22 @@ int psld_conv3x3_wino_gn_ws_f32(const float* x1, int c1, const float* scale1, co
                                 const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
                                 void* workspace, long long ws_bytes, hipStream_t stream);
 
+/* Two-limb (PSLD_MATH_BF16X3) forms of the Winograd forward: fragments of two limb planes [...][16 pos][2 limbs][64 lanes]
+ * (cout*cin*16*4 bytes + the same prefetch pad; the planes are the hi and mid planes of psld_pack_conv3x3_wino, forward
+ * orientation only; psld_pack_wino_batch_x3 takes psld_pack_wino_batch's table), V split in two limbs, three products per
+ * accumulator.  Shapes: psld_conv3x3_wino_supported / psld_conv3x3_wino_gn_supported; workspace: NULL, or
+ * psld_conv3x3_wino_ws_bytes bytes (the launches psld_conv3x3_wino_ksplit splits, split the same way).  Epilogue as above. */
+long long psld_conv3x3_wino_frag_bytes_x3(int cout, int cin);
+int psld_pack_conv3x3_wino_x3(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream);
+int psld_pack_wino_batch_x3(const long long* table_dev, int entries, long long total_items, hipStream_t stream);
+int psld_conv3x3_wino_x3_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
+                             const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
+                             void* workspace, long long ws_bytes, hipStream_t stream);
+int psld_conv3x3_wino_gn_x3_f32(const float* x1, int c1, const float* scale1, const float* shift1, const float* x2,
+                                int c2, const float* scale2, const float* shift2, int act, int batch, int h, int w,
+                                const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
+                                void* workspace, long long ws_bytes, hipStream_t stream);
+
 /* "Limb planes": an NHWC activation [rows][c] (c a multiple of 32) stored already decomposed, as bf16
  * [rows][c/32 chunks][3 limbs hi|mid|lo][32 channels] (6 bytes per element; hi + mid + lo == x bit for bit).  The
  * producers of a 3x3 convolution's input write this form (psld_gn_apply_nhwc_f32 with y_limb) so that the convolution
@@ -213,6 +236,18 @@ int psld_pack_gemm_frag(const float* b, void* bfrag, int n, int k, long long str
 int psld_gemm_split_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
                         float* y, int ldy, const psld_epilogue_t* epi, void* workspace, long long ws_bytes,
                         hipStream_t stream);
+/* Two-limb (PSLD_MATH_BF16X3) form of the forward GEMM: fragments of the hi and mid planes only (n*k*4 bytes;
+ * psld_pack_frag_batch_x3 takes psld_pack_frag_batch's table, taps = 1), rows split in two limbs, three products per
+ * accumulator, every epilogue of psld_gemm_split_f32.  Always the eight-wave kernel of 128 x 256 tiles: shapes of
+ * psld_gemm_split_supported with n a multiple of 256 (psld_gemm_split_f32 takes that kernel from 128 tiles on - below, its
+ * four-wave kernel with split K fills the chip better); anything else stays on psld_gemm_split_f32. */
+long long psld_gemm_frag_bytes_x3(int n, int k);
+int psld_gemm_split_x3_supported(int k1, int k2, int m, int n);
+int psld_pack_gemm_frag_x3(const float* b, void* bfrag, int n, int k, long long stride_n, long long stride_k,
+                           hipStream_t stream);
+int psld_pack_frag_batch_x3(const long long* table_dev, int entries, long long total_items, hipStream_t stream);
+int psld_gemm_split_x3_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
+                           float* y, int ldy, const psld_epilogue_t* epi, hipStream_t stream);
 
 /* Fused single-head spatial self-attention, forward: o[b][i][:] = sum_j softmax_j(scale * q[b][i] . k[b][j]) v[b][j][:] in
  * one kernel, the hw x hw score matrix never written (unless p != NULL: the probabilities [batch][hw][hw] fp32, what the

@@ -99,6 +99,11 @@ SIGNATURES = {
     "psld_conv3x3_wino_gn_supported": (I, [I, I, I, I, I, I]),
     "psld_conv3x3_wino_gn_f32": (I, [P, I, P, P, P, I, P, P, I, I, I, I, P, I, P, I, EP, P]),
     "psld_conv3x3_wino_gn_ws_f32": (I, [P, I, P, P, P, I, P, P, I, I, I, I, P, I, P, I, EP, P, LL, P]),
+    "psld_conv3x3_wino_frag_bytes_x3": (LL, [I, I]),
+    "psld_pack_conv3x3_wino_x3": (I, [P, P, I, I, P]),
+    "psld_pack_wino_batch_x3": (I, [P, I, LL, P]),
+    "psld_conv3x3_wino_x3_f32": (I, [P, I, P, I, I, I, I, P, I, P, I, EP, P, LL, P]),
+    "psld_conv3x3_wino_gn_x3_f32": (I, [P, I, P, P, P, I, P, P, I, I, I, I, P, I, P, I, EP, P, LL, P]),
     "psld_gn_apply_limb_nhwc": (I, [P, P, P, P, I, I, I, I, F, C.c_ulonglong, P, P]),
     "psld_limb_bytes": (LL, [LL, I]),
     "psld_f32_to_limb": (I, [P, LL, I, P, P]),
@@ -108,6 +113,11 @@ SIGNATURES = {
     "psld_gemm_split_supported": (I, [I, I, I, I]),
     "psld_pack_gemm_frag": (I, [P, P, I, I, LL, LL, P]),
     "psld_gemm_split_f32": (I, [P, I, P, I, I, P, I, P, I, EP, P, LL, P]),
+    "psld_gemm_frag_bytes_x3": (LL, [I, I]),
+    "psld_gemm_split_x3_supported": (I, [I, I, I, I]),
+    "psld_pack_gemm_frag_x3": (I, [P, P, I, I, LL, LL, P]),
+    "psld_pack_frag_batch_x3": (I, [P, I, LL, P]),
+    "psld_gemm_split_x3_f32": (I, [P, I, P, I, I, P, I, P, I, EP, P]),
     "psld_conv3x3_wgrad_split_supported": (I, [I, I, I, I, I]),
     "psld_conv3x3_wgrad_split_cout_tile": (I, [I]),
     "psld_conv3x3_wgrad_split_f32": (I, [P, I, I, P, I, P, I, I, I, I, P, I, I, I, P]),

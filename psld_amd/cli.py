@@ -499,6 +499,10 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--mask", default="synthetic", help="inpaint: uint8 [N,H,W,3] .npy (1 = keep) or 'synthetic'")
         p.add_argument("--clf-config", default="clf_c10", choices=["clf_c10", "clf_afhqv2_128", "clf_default", "tiny_clf"])
         p.add_argument("--labels", default="synthetic", help="train_clf: int [N] .npy or 'synthetic'")
+        if name in ("sample", "cc_sample", "inpaint"):
+            p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32"],
+                           help="arithmetic of the network evaluations (ops.set_math_mode; default: the process's mode, "
+                                "PSLD_MATH); bf16x3 = two-limb reduced-precision inference")
     return ap
 
 
@@ -506,6 +510,9 @@ def main(argv=None):
     args, overrides = build_parser().parse_known_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("psld_amd needs an MI355X: there is no CPU fallback")
+    if getattr(args, "math", None):         # before the network is built
+        from psld_amd import ops
+        ops.set_math_mode(args.math)
     {"train": train, "sample": sample, "inpaint": inpaint, "train_clf": train_clf,
      "cc_sample": cc_sample}[args.cmd](args, overrides)
 

@@ -34,7 +34,7 @@ int g_math_mode = -1;
 inline int math_mode() {
     if (g_math_mode < 0) {
         const char* e = getenv("PSLD_MATH");
-        g_math_mode = (e && !strcmp(e, "f32")) ? PSLD_MATH_F32 : PSLD_MATH_BF16X6;
+        g_math_mode = (e && !strcmp(e, "f32")) ? PSLD_MATH_F32 : (e && !strcmp(e, "bf16x3")) ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
     }
     return g_math_mode;
 }
@@ -56,6 +56,8 @@ __device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, cons
 // limbs at once.
 // chunk0 / chunks_total: the tensor fills the 32-wide K chunks chunk0 .. chunk0 + k_in/32 of a fragment set whose K
 // dimension has chunks_total chunks (several parameters concatenated along K: the attention q | k | v data gradient).
+// NL = 2 (PSLD_MATH_BF16X3): the hi and mid limbs only ([...][nb][2 limbs][lane]), bit for bit planes 0 and 1 of NL = 3.
+template <int NL = 3>
 __device__ __forceinline__ void pack_frag_item(const float* __restrict__ w, u32x4* __restrict__ out, long long item,
                                                int k_in, int taps, long long sn, long long sk, long long st, int flip,
                                                int chunk0 = 0, int chunks_total = 0) {
@@ -76,24 +78,29 @@ __device__ __forceinline__ void pack_frag_item(const float* __restrict__ w, u32x
         const float* p = src + (flip ? taps - 1 - tap : tap) * st;
         unsigned hi[4], mid[4], lo[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) split3(p[(2 * j) * sk], p[(2 * j + 1) * sk], hi[j], mid[j], lo[j]);
-        u32x4* o = out + (((base + tap) * 4 + nb) * 3) * 64 + lane;
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (NL == 3) split3(p[(2 * j) * sk], p[(2 * j + 1) * sk], hi[j], mid[j], lo[j]);
+            else split2(p[(2 * j) * sk], p[(2 * j + 1) * sk], hi[j], mid[j]);
+        }
+        u32x4* o = out + (((base + tap) * 4 + nb) * NL) * 64 + lane;
         o[0] = u32x4{hi[0], hi[1], hi[2], hi[3]};
         o[64] = u32x4{mid[0], mid[1], mid[2], mid[3]};
-        o[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        if constexpr (NL == 3) o[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
     }
 }
 
+template <int NL = 3>
 __global__ void pack_frag_kernel(const float* __restrict__ w, u32x4* __restrict__ out, int n_out, int k_in, int taps,
                                  long long sn, long long sk, long long st, int flip) {
     const long long items = (long long)n_out * (k_in / 32) * 4;     // n_out/128 * 2 * chunks * 4 * 64
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (long long)gridDim.x * blockDim.x)
-        pack_frag_item(w, out, i, k_in, taps, sn, sk, st, flip);
+        pack_frag_item<NL>(w, out, i, k_in, taps, sn, sk, st, flip);
 }
 
 // Many weight tensors in one launch.  tab[8*i ..]: src pointer, dst pointer, n_out, k_in | chunk0 << 20 | chunks_total << 40,
 // taps | flip << 32, sn, sk, first work item of tensor i in the launch-wide numbering (st = 1; a tensor has
 // n_out * k_in / 8 items; chunk0 = chunks_total = 0: the tensor is the whole K dimension of its fragment set).
+template <int NL = 3>
 __global__ void pack_frag_batch_kernel(const long long* __restrict__ tab, int ntab, long long total) {
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
@@ -103,17 +110,18 @@ __global__ void pack_frag_batch_kernel(const long long* __restrict__ tab, int nt
             if (tab[8 * mid + 7] <= idx) lo = mid; else hi = mid - 1;
         }
         const long long* d = tab + 8 * lo;
-        pack_frag_item(reinterpret_cast<const float*>(d[0]), reinterpret_cast<u32x4*>(d[1]), idx - d[7], (int)(d[3] & 0xfffff),
+        pack_frag_item<NL>(reinterpret_cast<const float*>(d[0]), reinterpret_cast<u32x4*>(d[1]), idx - d[7], (int)(d[3] & 0xfffff),
                        (int)(d[4] & 0xffffffffLL), d[5], d[6], 1, (int)(d[4] >> 32), (int)((d[3] >> 20) & 0xfffff),
                        (int)((d[3] >> 40) & 0xfffff));
     }
 }
 
+template <int NL = 3>
 int launch_pack(const float* w, void* out, int n_out, int k_in, int taps, long long sn, long long sk, long long st,
                 int flip, hipStream_t stream, const char* name) {
     const long long total = (long long)n_out * (k_in / 32) * 4;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(pack_frag_kernel, dim3(blocks), dim3(256), 0, stream, w, reinterpret_cast<u32x4*>(out), n_out,
+    hipLaunchKernelGGL(pack_frag_kernel<NL>, dim3(blocks), dim3(256), 0, stream, w, reinterpret_cast<u32x4*>(out), n_out,
                        k_in, taps, sn, sk, st, flip);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
@@ -1448,10 +1456,13 @@ int launch_bgemm(const BGemmArgs& a, int batch, hipStream_t stream) {
 // two 16-channel blocks of its 32 channels.
 constexpr int PW8_ROWS = 256;                       // LDS pixel rows per image: 128 rows x 2 chunks
 constexpr int PW8_LIMB = PW8_ROWS * ROWB;           // bytes per limb of one image
-constexpr int PW8_IMG = 3 * PW8_LIMB;
-template <int ABL = 0>      // timing-only ablations (PSLD_PW8_ABL): 1 no staging after the prologue, 2 weights loaded once, 4 no epilogue
+// NL = 2 (PSLD_MATH_BF16X3): rows and weights keep their first two limbs (split2), three products per accumulator instead of
+// six (hi*hi + (hi*lo + lo*hi), smallest first), images of two limb planes, fragments of psld_pack_gemm_frag_x3.
+template <int ABL = 0, int NL = 3>      // timing-only ablations (PSLD_PW8_ABL): 1 no staging after the prologue, 2 weights loaded once, 4 no epilogue
 __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int IMG = NL * PW8_LIMB;          // bytes of one image
+    constexpr int TAPU = 4 * NL * 64;           // TAP_U4 of NL limbs
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int c4 = tid & 7;
@@ -1496,47 +1507,53 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             unsigned h0, m0_, l0, h1, m1, l1;
-            split3(hv[i][0], hv[i][1], h0, m0_, l0);
-            split3(hv[i][2], hv[i][3], h1, m1, l1);
+            if constexpr (NL == 3) {
+                split3(hv[i][0], hv[i][1], h0, m0_, l0);
+                split3(hv[i][2], hv[i][3], h1, m1, l1);
+            } else {
+                split2(hv[i][0], hv[i][1], h0, m0_);
+                split2(hv[i][2], hv[i][3], h1, m1);
+            }
             const int prow = (tid >> 3) + 64 * i;
-            unsigned char* q = smem + img * PW8_IMG + prow * ROWB + (((c4 >> 1) ^ lds_swz(prow)) << 4) + (c4 & 1) * 8;
+            unsigned char* q = smem + img * IMG + prow * ROWB + (((c4 >> 1) ^ lds_swz(prow)) << 4) + (c4 & 1) * 8;
             *reinterpret_cast<u32x2*>(q) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(q + PW8_LIMB) = u32x2{m0_, m1};
-            *reinterpret_cast<u32x2*>(q + 2 * PW8_LIMB) = u32x2{l0, l1};
+            if constexpr (NL == 3) *reinterpret_cast<u32x2*>(q + 2 * PW8_LIMB) = u32x2{l0, l1};
         }
     };
 
     const int r16 = lane & 15, kq = lane >> 4;
-    const long long tile_u4 = (long long)a.chunks * 2 * TAP_U4;                  // fragments of one 64-channel half tile
-    const u32x4* wbase = a.wfrag + (long long)(wave >> 1) * tile_u4 + lane + (wave & 1) * 2 * 3 * 64;
-    u32x4 bq[2][2][3];
-    auto load_b = [&](const u32x4* p, u32x4 (&dst)[2][3]) {
+    const long long tile_u4 = (long long)a.chunks * 2 * TAPU;                  // fragments of one 64-channel half tile
+    const u32x4* wbase = a.wfrag + (long long)(wave >> 1) * tile_u4 + lane + (wave & 1) * 2 * NL * 64;
+    u32x4 bq[2][2][NL];
+    auto load_b = [&](const u32x4* p, u32x4 (&dst)[2][NL]) {
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-            for (int l = 0; l < 3; ++l) dst[nb][l] = p[(nb * 3 + l) * 64];
+            for (int l = 0; l < NL; ++l) dst[nb][l] = p[(nb * NL + l) * 64];
     };
     f32x4v acc[8][2];
 
     // A stage = 2 K steps (chunks) x 4 quarters of the 128 rows (two 16-row blocks each): 24 MFMAs per quarter.  The A
     // fragments of quarter j + 1 are read from LDS before the MFMAs of quarter j are issued (rolling two-deep buffer).
     // Per accumulator the six limb products keep their order, smallest first.
-    u32x4 fa[2][2][3];
-    auto read_q = [&](int img, int j, u32x4 (&dst)[2][3]) {          // quarter j of the stage: chunk j >> 2, blocks 2 (j & 3), +1
+    u32x4 fa[2][2][NL];
+    auto read_q = [&](int img, int j, u32x4 (&dst)[2][NL]) {          // quarter j of the stage: chunk j >> 2, blocks 2 (j & 3), +1
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
             const int prow = (j >> 2) * 128 + ((j & 3) * 2 + mb) * 16 + r16;
-            const unsigned char* q = smem + img * PW8_IMG + prow * ROWB + ((kq ^ lds_swz(prow)) << 4);
+            const unsigned char* q = smem + img * IMG + prow * ROWB + ((kq ^ lds_swz(prow)) << 4);
 #pragma unroll
-            for (int l = 0; l < 3; ++l) dst[mb][l] = *reinterpret_cast<const u32x4*>(q + l * PW8_LIMB);
+            for (int l = 0; l < NL; ++l) dst[mb][l] = *reinterpret_cast<const u32x4*>(q + l * PW8_LIMB);
         }
     };
     auto mfma_q = [&](auto J) {
         constexpr int j = decltype(J)::value;
         constexpr int pp = j >> 2, b0 = (j & 3) * 2;
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+        constexpr int NP = NL == 3 ? 6 : 3;         // two limbs: A_lo B_hi, A_hi B_lo, A_hi B_hi
+        constexpr int PA[6] = {NL == 3 ? 2 : 1, 0, NL == 3 ? 1 : 0, 1, 0, 0}, PB[6] = {0, NL == 3 ? 2 : 1, NL == 3 ? 1 : 0, 0, 1, 0};
 #pragma unroll
-        for (int t = 0; t < 6; ++t)
+        for (int t = 0; t < NP; ++t)
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -1566,7 +1583,7 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
         const u32x4* wp_next = wbase + (long long)ntn * 4 * tile_u4;
         for (int st = 0; st < S; ++st, ++g) {
             const int img = g & 1;
-            if (!(ABL & 2)) load_b(wp + (long long)(2 * st + 1) * TAP_U4, bq[1]);
+            if (!(ABL & 2)) load_b(wp + (long long)(2 * st + 1) * TAPU, bq[1]);
             // SIMD partners (waves w, w + 4) would split / store the next image at the same moment and leave the matrix
             // pipe idle together: waves 4-7 do it at the head of the stage, waves 0-3 between the two K steps (512 -> 256
             // @32x32 B=128: 213 -> 201 us; the smaller shapes do not move)
@@ -1587,7 +1604,7 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
                 if (g + 2 < G) load_rows();
             }
             // the first chunk's weights are done with: the next stage's first chunk (of the next tile after the last stage)
-            if (!(ABL & 2)) load_b(st + 1 < S ? wp + (long long)(2 * st + 2) * TAP_U4 : wp_next, bq[0]);
+            if (!(ABL & 2)) load_b(st + 1 < S ? wp + (long long)(2 * st + 2) * TAPU : wp_next, bq[0]);
             __builtin_amdgcn_sched_barrier(0);
             PW8_Q(4) PW8_Q(5) PW8_Q(6) PW8_Q(7)
 #undef PW8_Q
@@ -1605,12 +1622,12 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
     }
 }
 
-template <int ABL = 0>
+template <int ABL = 0, int NL = 3>
 int launch_pw8(const DConvArgs& a, hipStream_t stream, const char* name) {
-    constexpr size_t LDS = (size_t)2 * PW8_IMG;
+    constexpr size_t LDS = (size_t)2 * NL * PW8_LIMB;
     static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw8_kernel<ABL>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw8_kernel<ABL, NL>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)LDS);
         if (e != hipSuccess) {
             psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
@@ -1619,7 +1636,7 @@ int launch_pw8(const DConvArgs& a, hipStream_t stream, const char* name) {
         configured = true;
     }
     const int total = cdiv(a.M, 128) * (a.N / 256);
-    hipLaunchKernelGGL(pw8_kernel<ABL>, dim3((unsigned)(total < 256 ? total : 256)), dim3(512), LDS, stream, a);
+    hipLaunchKernelGGL((pw8_kernel<ABL, NL>), dim3((unsigned)(total < 256 ? total : 256)), dim3(512), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
 }
@@ -1775,7 +1792,7 @@ int dconv_tile_rows(const DConvArgs& a, int h, int w) {
 // C ABI
 // ---------------------------------------------------------------------------------------
 extern "C" int psld_set_math_mode(int mode) {
-    PSLD_CHECK_ARG(mode == PSLD_MATH_F32 || mode == PSLD_MATH_BF16X6, "psld_set_math_mode: unknown mode %d", mode);
+    PSLD_CHECK_ARG(mode == PSLD_MATH_F32 || mode == PSLD_MATH_BF16X6 || mode == PSLD_MATH_BF16X3, "psld_set_math_mode: unknown mode %d", mode);
     g_math_mode = mode;
     return PSLD_OK;
 }
@@ -1803,7 +1820,7 @@ extern "C" int psld_pack_conv3x3_frag(const float* w_oihw, void* wfrag, int cout
 extern "C" int psld_pack_frag_batch(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
     PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_frag_batch: bad args");
     const long long want = (total_items + 255) / 256;
-    hipLaunchKernelGGL(pack_frag_batch_kernel, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(pack_frag_batch_kernel<3>, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream,
                        table_dev, entries, total_items);
     PSLD_CHECK_LAUNCH("psld_pack_frag_batch");
     return PSLD_OK;
@@ -2099,4 +2116,50 @@ extern "C" int psld_gemm_split_f32(const float* a1, int k1, const float* a2, int
     if (st != PSLD_OK) return st;
     if (ns >= 2) return psld_detail_conv_reduce_epilogue(a.C, ns, m, n, y, ldy, e, stream);
     return PSLD_OK;
+}
+
+// ---- two limbs (PSLD_MATH_BF16X3): the eight-wave pointwise kernel on hi / mid fragments ----------------------------
+// Always pw8_kernel (128 x 256 tiles, n a multiple of 256); psld_gemm_split_f32 sends only launches of at least 128 tiles there.
+extern "C" long long psld_gemm_frag_bytes_x3(int n, int k) { return (long long)n * k * 4; }
+
+extern "C" int psld_gemm_split_x3_supported(int k1, int k2, int m, int n) {
+    return psld_gemm_split_supported(k1, k2, m, n) && n % 256 == 0;
+}
+
+extern "C" int psld_pack_gemm_frag_x3(const float* b, void* bfrag, int n, int k, long long stride_n, long long stride_k,
+                                      hipStream_t stream) {
+    PSLD_CHECK_ARG(b && bfrag, "psld_pack_gemm_frag_x3: null pointer");
+    PSLD_CHECK_ARG(n > 0 && k > 0 && n % 128 == 0 && k % 64 == 0, "psld_pack_gemm_frag_x3: needs n %%128 and k %%64 (got %d, %d)", n, k);
+    return launch_pack<2>(b, bfrag, n, k, 1, stride_n, stride_k, 0, 0, stream, "psld_pack_gemm_frag_x3");
+}
+
+extern "C" int psld_pack_frag_batch_x3(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
+    PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_frag_batch_x3: bad args");
+    const long long want = (total_items + 255) / 256;
+    hipLaunchKernelGGL(pack_frag_batch_kernel<2>, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream,
+                       table_dev, entries, total_items);
+    PSLD_CHECK_LAUNCH("psld_pack_frag_batch_x3");
+    return PSLD_OK;
+}
+
+extern "C" int psld_gemm_split_x3_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
+                                      float* y, int ldy, const psld_epilogue_t* epi, hipStream_t stream) {
+    PSLD_CHECK_ARG(a1 && bfrag && y && (k2 == 0 || a2), "psld_gemm_split_x3_f32: null pointer");
+    PSLD_CHECK_ARG(psld_gemm_split_x3_supported(k1, k2, m, n), "psld_gemm_split_x3_f32: unsupported shape k1=%d k2=%d m=%d n=%d", k1, k2, m, n);
+    PSLD_CHECK_ARG(aligned16(a1) && (!a2 || aligned16(a2)) && aligned16(bfrag), "psld_gemm_split_x3_f32: unaligned pointer");
+    DConvArgs a{};
+    a.x1 = a1; a.x2 = a2; a.C1 = k1; a.C2 = k2;
+    a.B = 1; a.H = 1; a.W = 1;
+    a.wfrag = reinterpret_cast<const u32x4*>(bfrag);
+    a.N = n; a.M = m;
+    a.chunks = (k1 + k2) / 64;
+    a.nseg = 1; a.rps = 1; a.pitch = a.W + 2;
+    a.zero = psld_detail_zero_page("psld_gemm_split_x3_f32");
+    if (!a.zero) return PSLD_ERR_LAUNCH;
+    const PsldEpilogue e = make_epilogue(epi);
+    PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw > 0 && e.gn_hw % 64 == 0 && m % e.gn_hw == 0 && !e.accumulate),
+                   "psld_gemm_split_x3_f32: gn_part needs gn_hw (rows per image) a multiple of 64 dividing m, and no accumulation");
+    plan_split(a, e, y, ldy, nullptr, 0);
+    PSLD_CHECK_ARG(a.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
+    return launch_pw8<0, 2>(a, stream, "psld_gemm_split_x3_f32");
 }

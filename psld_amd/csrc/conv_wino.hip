@@ -35,7 +35,7 @@ namespace {
 
 constexpr int WT = 32;                    // tiles per workgroup
 constexpr int VPLANE = WT * ROWB;         // bytes of one (position, limb) plane of the V image: 32 tiles x 64 B
-constexpr int VBYTES = 16 * 3 * VPLANE;   // 98,304
+constexpr int VBYTES = 16 * 3 * VPLANE;   // 98,304 (three limbs; two: 65,536)
 constexpr int WINO_THREADS = 512;
 
 struct WinoArgs {
@@ -77,6 +77,8 @@ __device__ __forceinline__ int raw_off(int hp, int q) {
 // ---- weights -> transformed limb fragments -----------------------------------------------------------------
 // One work item = lane slot (nt, wave, chunk, lane): n = nt*128 + wave*16 + (lane & 15), k = chunk*32 + (lane >> 4)*8 + j.
 // dgrad = 0: g = w[co = n][ci = k][:, :]; dgrad = 1: g = w[co = k][ci = n] rotated by 180 degrees (conv_split.hip).
+// NL = 2 (PSLD_MATH_BF16X3): the hi and mid limbs only, [...][16 pos][2 limbs][64 lanes] - bit for bit planes 0 and 1 of NL = 3.
+template <int NL = 3>
 __device__ __forceinline__ void wino_pack_item(const float* __restrict__ w, u32x4* __restrict__ out, long long it, int k_in,
                                                long long sn, long long sk, int flip) {
     const int chunks = k_in / 32;
@@ -111,27 +113,32 @@ __device__ __forceinline__ void wino_pack_item(const float* __restrict__ w, u32x
             U[j][a * 4 + 3] = t4[a][2];
         }
     }
-    u32x4* o = out + ((long long)nblk * chunks + chunk) * (16 * 3 * 64) + lane;
+    u32x4* o = out + ((long long)nblk * chunks + chunk) * (16 * NL * 64) + lane;
 #pragma unroll
     for (int p = 0; p < 16; ++p) {
         unsigned hi[4], mid[4], lo[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) split3(U[2 * j][p], U[2 * j + 1][p], hi[j], mid[j], lo[j]);
-        o[(p * 3 + 0) * 64] = u32x4{hi[0], hi[1], hi[2], hi[3]};
-        o[(p * 3 + 1) * 64] = u32x4{mid[0], mid[1], mid[2], mid[3]};
-        o[(p * 3 + 2) * 64] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (NL == 3) split3(U[2 * j][p], U[2 * j + 1][p], hi[j], mid[j], lo[j]);
+            else split2(U[2 * j][p], U[2 * j + 1][p], hi[j], mid[j]);
+        }
+        o[(p * NL + 0) * 64] = u32x4{hi[0], hi[1], hi[2], hi[3]};
+        o[(p * NL + 1) * 64] = u32x4{mid[0], mid[1], mid[2], mid[3]};
+        if constexpr (NL == 3) o[(p * 3 + 2) * 64] = u32x4{lo[0], lo[1], lo[2], lo[3]};
     }
 }
 
+template <int NL = 3>
 __global__ void wino_pack_kernel(const float* __restrict__ w, u32x4* __restrict__ out, int n_out, int k_in,
                                  long long sn, long long sk, int flip) {
     const long long items = (long long)(n_out / 16) * (k_in / 32) * 64;
     for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (long long)gridDim.x * blockDim.x)
-        wino_pack_item(w, out, it, k_in, sn, sk, flip);
+        wino_pack_item<NL>(w, out, it, k_in, sn, sk, flip);
 }
 
 // Many weight tensors in one launch (as pack_frag_batch_kernel of conv_split.hip).  tab[8*i ..]: src pointer, dst
 // pointer, n_out, k_in, flip, sn, sk, first work item of tensor i (a tensor has n_out * k_in / 8 items).
+template <int NL = 3>
 __global__ void wino_pack_batch_kernel(const long long* __restrict__ tab, int ntab, long long total) {
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
@@ -141,7 +148,7 @@ __global__ void wino_pack_batch_kernel(const long long* __restrict__ tab, int nt
             if (tab[8 * mid + 7] <= idx) lo = mid; else hi = mid - 1;
         }
         const long long* d = tab + 8 * lo;
-        wino_pack_item(reinterpret_cast<const float*>(d[0]), reinterpret_cast<u32x4*>(d[1]), idx - d[7], (int)d[3], d[5], d[6],
+        wino_pack_item<NL>(reinterpret_cast<const float*>(d[0]), reinterpret_cast<u32x4*>(d[1]), idx - d[7], (int)d[3], d[5], d[6],
                        (int)d[4]);
     }
 }
@@ -180,13 +187,16 @@ __global__ void wino_pack_batch_kernel(const long long* __restrict__ tab, int nt
 // TAIL (cout % 128 != 0 only): the last channel tile holds 32, 64 or 96 channels; the waves beyond cout take their share of the
 // staging and the transform (and the barriers) but load no fragments, issue no MFMAs and leave before the epilogue.  Every
 // live wave does exactly what it does in a full tile, so a channel's result does not depend on how many share its launch.
-template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false>
+// NL = 2 (PSLD_MATH_BF16X3, forward only): V and U keep their first two limbs (split2) and a product is the three limb
+// products hi*hi + (hi*lo + lo*hi): V image [pos][2][tile][32 ch] (64 KB), fragments [...][16 pos][2 limbs][64 lanes], per
+// chunk and wave 16 positions x (4 ds_read_b128 + 2 fragment loads + 6 MFMAs).  Everything else is the NL = 3 kernel.
+template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3>
 __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NI = 4;                     // raw image: 256 halo pixels
     constexpr int RAWB = NI * 64 * 128;
     unsigned char* Vs = smem;
-    unsigned char* Rs = smem + VBYTES;        // two raw images
+    unsigned char* Rs = smem + VBYTES / 3 * NL;        // two raw images
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -299,12 +309,17 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
         for (int j = 0; j < 4; ++j) {
             const f32x4 v = j == 0 ? r[0] - r[2] : j == 1 ? r[1] + r[2] : j == 2 ? r[2] - r[1] : r[1] - r[3];
             unsigned h0, m0_, l0, h1, m1, l1;
-            split3(v[0], v[1], h0, m0_, l0);
-            split3(v[2], v[3], h1, m1, l1);
-            unsigned char* q = Vs + (vrow * 4 + j) * 3 * VPLANE + t_dst;
+            if constexpr (NL == 3) {
+                split3(v[0], v[1], h0, m0_, l0);
+                split3(v[2], v[3], h1, m1, l1);
+            } else {
+                split2(v[0], v[1], h0, m0_);
+                split2(v[2], v[3], h1, m1);
+            }
+            unsigned char* q = Vs + (vrow * 4 + j) * NL * VPLANE + t_dst;
             *reinterpret_cast<u32x2*>(q) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(q + VPLANE) = u32x2{m0_, m1};
-            *reinterpret_cast<u32x2*>(q + 2 * VPLANE) = u32x2{l0, l1};
+            if constexpr (NL == 3) *reinterpret_cast<u32x2*>(q + 2 * VPLANE) = u32x2{l0, l1};
         }
     };
 
@@ -317,22 +332,22 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
         aoff[tb] = row * ROWB + ((kq ^ lds_swz(row)) << 4);
     }
     // ABL & 128 (timing only, wrong results): SIMD partners w, w + 4 stream the SAME fragments - what the L1 merges
-    const u32x4* ub = a.ufrag + ((long long)(tile_n * 8 + ((ABL & 128) ? (wave & 3) : wave)) * a.chunks + ch0) * (16 * 3 * 64);      // wave-uniform
-    u32x4 bq[4][3];
-    auto load_b = [&](int sigma, u32x4 (&dst)[3]) {
-        const u32x4* p = ub + (long long)sigma * (3 * 64);
+    const u32x4* ub = a.ufrag + ((long long)(tile_n * 8 + ((ABL & 128) ? (wave & 3) : wave)) * a.chunks + ch0) * (16 * NL * 64);      // wave-uniform
+    u32x4 bq[4][NL];
+    auto load_b = [&](int sigma, u32x4 (&dst)[NL]) {
+        const u32x4* p = ub + (long long)sigma * (NL * 64);
 #pragma unroll
-        for (int l = 0; l < 3; ++l) dst[l] = p[l * 64 + lane];
+        for (int l = 0; l < NL; ++l) dst[l] = p[l * 64 + lane];
     };
     f32x4v acc[16][2];
 #pragma unroll
     for (int p = 0; p < 16; ++p)
 #pragma unroll
         for (int tb = 0; tb < 2; ++tb) acc[p][tb] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    u32x4 fa[3][2];          // [limb hi | mid | lo][tile block]
+    u32x4 fa[NL][2];         // [limb hi | mid | lo][tile block]
     auto read_a = [&](int p, int l) {
 #pragma unroll
-        for (int tb = 0; tb < 2; ++tb) fa[l][tb] = *reinterpret_cast<const u32x4*>(Vs + (p * 3 + l) * VPLANE + aoff[tb]);
+        for (int tb = 0; tb < 2; ++tb) fa[l][tb] = *reinterpret_cast<const u32x4*>(Vs + (p * NL + l) * VPLANE + aoff[tb]);
     };
     auto mm = [&](int p, int la, int lb) {
 #pragma unroll
@@ -344,7 +359,8 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     auto mfma_half = [&](auto HH, int c) {
         constexpr int h = decltype(HH)::value;
         if constexpr ((ABL & 256) != 0) __builtin_amdgcn_s_setprio(2);       // experiment: the multiplying wave outranks its partner
-        read_a(8 * h, 2);
+        // NL = 2: three products, small terms first - V_lo U_hi, V_hi U_lo, V_hi U_hi
+        if constexpr (NL == 3) read_a(8 * h, 2);
         read_a(8 * h, 1);
         read_a(8 * h, 0);
 #pragma unroll
@@ -352,16 +368,18 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
             const int p = 8 * h + i;
             if (!(ABL & 2)) load_b(c * 16 + p + LA, bq[(p + LA) & 3]);
             __builtin_amdgcn_sched_barrier(0);
-            mm(p, 2, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (i < 7) read_a(p + 1, 2);
-            __builtin_amdgcn_sched_barrier(0);
-            mm(p, 1, 1);
+            if constexpr (NL == 3) {
+                mm(p, 2, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (i < 7) read_a(p + 1, 2);
+                __builtin_amdgcn_sched_barrier(0);
+                mm(p, 1, 1);
+            }
             mm(p, 1, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (i < 7) read_a(p + 1, 1);
             __builtin_amdgcn_sched_barrier(0);
-            mm(p, 0, 2);
+            if constexpr (NL == 3) mm(p, 0, 2);
             mm(p, 0, 1);
             mm(p, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -518,13 +536,13 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
 #include "conv_wino_abl.inc"
 #endif
 
-template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false>
+template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3>
 int launch_wino8s(const WinoArgs& a, hipStream_t stream, const char* name) {
-    constexpr size_t LDS = (size_t)VBYTES + 2 * (size_t)4 * 64 * 128;
+    constexpr size_t LDS = (size_t)VBYTES / 3 * NL + 2 * (size_t)4 * 64 * 128;
     static_assert(LDS <= 163840, "LDS budget");
     static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
         if (e != hipSuccess) {
             psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
@@ -533,7 +551,7 @@ int launch_wino8s(const WinoArgs& a, hipStream_t stream, const char* name) {
         configured = true;
     }
     dim3 grid((unsigned)(cdiv(a.M, 128) * cdiv(a.N, 128) * (a.ksplit > 1 ? a.ksplit : 1)));
-    hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL>), grid, dim3(WINO_THREADS), LDS, stream, a);
+    hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>), grid, dim3(WINO_THREADS), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
 }
@@ -577,6 +595,8 @@ bool wino_geometry(int h, int w, int* nseg, int* rps, int* halo_px) {
 
 // + 16 KB: the kernels prefetch up to three positions (3 x 3 KB per 16-channel block) past the last fragment
 extern "C" long long psld_conv3x3_wino_frag_bytes(int cout, int cin) { return (long long)cout * cin * 16 * 6 + 16384; }
+// two limbs (PSLD_MATH_BF16X3): 2/3 of the payload, the same pad
+extern "C" long long psld_conv3x3_wino_frag_bytes_x3(int cout, int cin) { return (long long)cout * cin * 16 * 4 + 16384; }
 
 // cout: a multiple of 128, or of 32 from 128 up (the last channel tile cut short: wino_conv8s_kernel<..., TAIL = true>)
 extern "C" int psld_conv3x3_wino_supported(int c1, int c2, int batch, int h, int w, int cout) {
@@ -592,18 +612,39 @@ extern "C" int psld_pack_conv3x3_wino(const float* w_oihw, void* ufrag, int cout
                    "psld_pack_conv3x3_wino: needs out channels %%32 (>= 128) and in channels %%32 (got %d, %d)", n_out, k_in);
     const long long items = (long long)(n_out / 16) * (k_in / 32) * 64;
     const int blocks = (int)((items + 63) / 64 < 16384 ? (items + 63) / 64 : 16384);
-    if (dgrad) hipLaunchKernelGGL(wino_pack_kernel, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag),
+    if (dgrad) hipLaunchKernelGGL(wino_pack_kernel<3>, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag),
                                   n_out, k_in, 9LL, (long long)cin * 9, 1);
-    else hipLaunchKernelGGL(wino_pack_kernel, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag),
+    else hipLaunchKernelGGL(wino_pack_kernel<3>, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag),
                             n_out, k_in, (long long)cin * 9, 9LL, 0);
     PSLD_CHECK_LAUNCH("psld_pack_conv3x3_wino");
+    return PSLD_OK;
+}
+
+extern "C" int psld_pack_conv3x3_wino_x3(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream) {
+    PSLD_CHECK_ARG(w_oihw && ufrag && aligned16(ufrag), "psld_pack_conv3x3_wino_x3: null / unaligned pointer");
+    PSLD_CHECK_ARG(cout >= 128 && cin > 0 && cout % 32 == 0 && cin % 32 == 0,
+                   "psld_pack_conv3x3_wino_x3: needs out channels %%32 (>= 128) and in channels %%32 (got %d, %d)", cout, cin);
+    const long long items = (long long)(cout / 16) * (cin / 32) * 64;
+    const int blocks = (int)((items + 63) / 64 < 16384 ? (items + 63) / 64 : 16384);
+    hipLaunchKernelGGL(wino_pack_kernel<2>, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag), cout, cin,
+                       (long long)cin * 9, 9LL, 0);
+    PSLD_CHECK_LAUNCH("psld_pack_conv3x3_wino_x3");
+    return PSLD_OK;
+}
+
+extern "C" int psld_pack_wino_batch_x3(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
+    PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_wino_batch_x3: bad args");
+    const long long want = (total_items + 63) / 64;
+    hipLaunchKernelGGL(wino_pack_batch_kernel<2>, dim3((unsigned)(want < 32768 ? want : 32768)), dim3(64), 0, stream,
+                       table_dev, entries, total_items);
+    PSLD_CHECK_LAUNCH("psld_pack_wino_batch_x3");
     return PSLD_OK;
 }
 
 extern "C" int psld_pack_wino_batch(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
     PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_wino_batch: bad args");
     const long long want = (total_items + 63) / 64;
-    hipLaunchKernelGGL(wino_pack_batch_kernel, dim3((unsigned)(want < 32768 ? want : 32768)), dim3(64), 0, stream,
+    hipLaunchKernelGGL(wino_pack_batch_kernel<3>, dim3((unsigned)(want < 32768 ? want : 32768)), dim3(64), 0, stream,
                        table_dev, entries, total_items);
     PSLD_CHECK_LAUNCH("psld_pack_wino_batch");
     return PSLD_OK;
@@ -621,7 +662,8 @@ struct WinoGn {
     int act;
 };
 int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w, const void* ufrag, int cout, float* y,
-              int ldy, const psld_epilogue_t* epi, const WinoGn* gn, void* workspace, long long ws_bytes, hipStream_t stream);
+              int ldy, const psld_epilogue_t* epi, const WinoGn* gn, void* workspace, long long ws_bytes, hipStream_t stream,
+              int nl = 3);
 }  // namespace
 
 extern "C" int psld_conv3x3_wino_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
@@ -682,9 +724,36 @@ extern "C" int psld_conv3x3_wino_gn_ws_f32(const float* x1, int c1, const float*
     return wino_conv(x1, c1, x2, c2, batch, h, w, ufrag, cout, y, ldy, epi, &gn, workspace, ws_bytes, stream);
 }
 
+// ---- two limbs (PSLD_MATH_BF16X3): the forward launches above on fragments of psld_pack_conv3x3_wino_x3 ----------------------
+extern "C" int psld_conv3x3_wino_x3_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
+                                        const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
+                                        void* workspace, long long ws_bytes, hipStream_t stream) {
+    return wino_conv(x1, c1, x2, c2, batch, h, w, ufrag, cout, y, ldy, epi, nullptr, workspace, ws_bytes, stream, 2);
+}
+
+extern "C" int psld_conv3x3_wino_gn_x3_f32(const float* x1, int c1, const float* scale1, const float* shift1, const float* x2,
+                                           int c2, const float* scale2, const float* shift2, int act, int batch, int h, int w,
+                                           const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
+                                           void* workspace, long long ws_bytes, hipStream_t stream) {
+    PSLD_CHECK_ARG(scale1 && shift1 && (c2 == 0 || (scale2 && shift2)), "psld_conv3x3_wino_gn_x3_f32: null scale / shift");
+    PSLD_CHECK_ARG(psld_conv3x3_wino_gn_supported(c1, c2, batch, h, w, cout),
+                   "psld_conv3x3_wino_gn_x3_f32: unsupported shape c1=%d c2=%d %dx%d cout=%d (needs h*w >= 128)", c1, c2, h, w, cout);
+    PSLD_CHECK_ARG(aligned16(scale1) && aligned16(shift1) && (c2 == 0 || (aligned16(scale2) && aligned16(shift2))),
+                   "psld_conv3x3_wino_gn_x3_f32: unaligned scale / shift");
+    const WinoGn gn{scale1, shift1, scale2, shift2, act};
+    return wino_conv(x1, c1, x2, c2, batch, h, w, ufrag, cout, y, ldy, epi, &gn, workspace, ws_bytes, stream, 2);
+}
+
 namespace {
+int wino_launch_x3(const WinoArgs& a, bool gn, hipStream_t stream) {
+    if (gn) return launch_wino8s<0, true, false, 2, false, 2>(a, stream, "psld_conv3x3_wino_gn_x3_f32");
+    if (a.N % 128) return launch_wino8s<0, false, false, 2, true, 2>(a, stream, "psld_conv3x3_wino_x3_f32");
+    return launch_wino8s<0, false, false, 2, false, 2>(a, stream, "psld_conv3x3_wino_x3_f32");
+}
+
 int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w, const void* ufrag, int cout, float* y,
-              int ldy, const psld_epilogue_t* epi, const WinoGn* gn, void* workspace, long long ws_bytes, hipStream_t stream) {
+              int ldy, const psld_epilogue_t* epi, const WinoGn* gn, void* workspace, long long ws_bytes, hipStream_t stream,
+              int nl) {
     PSLD_CHECK_ARG(x1 && ufrag && y && (c2 == 0 || x2), "psld_conv3x3_wino_f32: null pointer");
     PSLD_CHECK_ARG(psld_conv3x3_wino_supported(c1, c2, batch, h, w, cout),
                    "psld_conv3x3_wino_f32: unsupported shape c1=%d c2=%d %dx%d cout=%d", c1, c2, h, w, cout);
@@ -729,11 +798,13 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
         s.C = reinterpret_cast<float*>(workspace);
         s.ldc = cout;
         s.e = make_epilogue(nullptr);
-        const int rc = gn ? launch_wino8s<0, true>(s, stream, "psld_conv3x3_wino_gn_f32")
-                          : (cout % 128 ? launch_wino8s<0, false, false, 2, true>(s, stream, name) : launch_wino8s<0>(s, stream, name));
+        const int rc = nl == 2 ? wino_launch_x3(s, gn != nullptr, stream)
+                       : gn    ? launch_wino8s<0, true>(s, stream, "psld_conv3x3_wino_gn_f32")
+                               : (cout % 128 ? launch_wino8s<0, false, false, 2, true>(s, stream, name) : launch_wino8s<0>(s, stream, name));
         if (rc != PSLD_OK) return rc;
         return psld_detail_conv_reduce_epilogue(s.C, ks, a.M, cout, y, ldy, e, stream);
     }
+    if (nl == 2) return wino_launch_x3(a, gn != nullptr, stream);
     if (gn) return launch_wino8s<0, true>(a, stream, "psld_conv3x3_wino_gn_f32");
     if (cout % 128) return launch_wino8s<0, false, false, 2, true>(a, stream, name);      // last channel tile cut short
 #ifdef PSLD_ABLATIONS      // libpsld_hip_abl.so only: the variants of conv_wino_abl.inc and the timing-only ablations (wrong results)

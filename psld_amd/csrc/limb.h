@@ -33,6 +33,12 @@ __device__ __forceinline__ void split3(float x0, float x1, unsigned& hi, unsigne
     const float s0 = r0 - __uint_as_float(mid << 16), s1 = r1 - __uint_as_float(mid & 0xffff0000u);
     lo = cvt_pk_bf16(s0, s1);
 }
+// The first two limbs of split3, bit for bit (PSLD_MATH_BF16X3: a product is hi*hi + (hi*lo + lo*hi), the dropped terms
+// are each below 2^-16 of it).
+__device__ __forceinline__ void split2(float x0, float x1, unsigned& hi, unsigned& lo) {
+    hi = cvt_pk_bf16(x0, x1);
+    lo = cvt_pk_bf16(x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u));
+}
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 

@@ -125,12 +125,17 @@ def conv2d_nhwc(x1: Tensor, x2: Optional[Tensor], w_ohwi: Tensor, cout: int, kh:
 
 
 def set_math_mode(mode: str):
-    """'f32' (v_mfma_f32_32x32x2_f32) or 'bf16x6' (three-limb bf16 MFMA, fp32-equivalent); process-wide."""
-    check(lib().psld_set_math_mode({"f32": 0, "bf16x6": 1}[mode]), "psld_set_math_mode")
+    """'f32' (v_mfma_f32_32x32x2_f32), 'bf16x6' (three-limb bf16 MFMA, fp32-equivalent) or 'bf16x3' (reduced-precision
+    inference: forwards that record no backward pass run the two-limb ``*_x3`` launches, everything else runs as in
+    'bf16x6'); process-wide."""
+    check(lib().psld_set_math_mode(MATH_MODES.index(mode)), "psld_set_math_mode")
+
+
+MATH_MODES = ("f32", "bf16x6", "bf16x3")     # PSLD_MATH_* of include/psld_hip.h
 
 
 def math_mode() -> str:
-    return ("f32", "bf16x6")[lib().psld_get_math_mode()]
+    return MATH_MODES[lib().psld_get_math_mode()]
 
 
 @functools.lru_cache(maxsize=None)
@@ -207,6 +212,52 @@ def conv3x3_wino_frag_entry(w_oihw: Tensor, dgrad: bool, out: Tensor):
 def pack_wino_batch(table: Tensor, entries: int, total_items: int):
     """table rows: conv3x3_wino_frag_entry(...) + [first work item]; a tensor has cout*cin/8 work items."""
     check(lib().psld_pack_wino_batch(table.data_ptr(), entries, total_items, _stream()), "psld_pack_wino_batch")
+
+
+# ---- two limbs (math mode 'bf16x3'): forward orientation only, same shapes and tables as the three-limb forms ----------
+def conv3x3_wino_frag_bytes_x3(cout: int, cin: int) -> int:
+    return int(lib().psld_conv3x3_wino_frag_bytes_x3(cout, cin))
+
+
+def conv3x3_wino_frag_x3(w_oihw: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """conv3x3_wino_frag(w, False) with the hi and mid limb planes only (psld_conv3x3_wino_frag_bytes_x3 bytes)."""
+    co, ci = w_oihw.shape[0], w_oihw.shape[1]
+    if out is None:
+        out = torch.empty(conv3x3_wino_frag_bytes_x3(co, ci), dtype=torch.uint8, device=w_oihw.device)
+    check(lib().psld_pack_conv3x3_wino_x3(w_oihw.data_ptr(), out.data_ptr(), co, ci, _stream()), "psld_pack_conv3x3_wino_x3")
+    return out
+
+
+def pack_wino_batch_x3(table: Tensor, entries: int, total_items: int):
+    """pack_wino_batch into two-limb fragment buffers (rows: conv3x3_wino_frag_entry(w, False, out) + [first work item])."""
+    check(lib().psld_pack_wino_batch_x3(table.data_ptr(), entries, total_items, _stream()), "psld_pack_wino_batch_x3")
+
+
+def conv3x3_wino_x3(x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: Tensor,
+                    epi: Optional[Epilogue] = None, ldy: Optional[int] = None, allow_split: bool = False):
+    """conv3x3_wino on two-limb fragments (conv3x3_wino_frag_x3): V and U keep two limbs, three products each."""
+    b, h, w, c1 = x1.shape
+    c2 = x2.shape[-1] if x2 is not None else 0
+    wsb = conv3x3_wino_ws_bytes(c1, c2, b, h, w, cout) if allow_split else 0
+    ws = workspace(wsb, x1.device).data_ptr() if wsb else None
+    check(lib().psld_conv3x3_wino_x3_f32(x1.data_ptr(), c1, _p(x2), c2, b, h, w, ufrag.data_ptr(), cout, y.data_ptr(),
+                                         ldy if ldy is not None else cout, C.byref(epi) if epi is not None else None,
+                                         ws, wsb, _stream()), "psld_conv3x3_wino_x3_f32")
+
+
+def conv3x3_wino_gn_x3(x1: Tensor, st1: "GNStats", x2: Optional[Tensor], st2: Optional["GNStats"], act: bool, ufrag: Tensor,
+                       cout: int, y: Tensor, epi: Optional[Epilogue] = None, allow_split: bool = False):
+    """conv3x3_wino_gn on two-limb fragments (conv3x3_wino_frag_x3)."""
+    b, h, w, c1 = x1.shape
+    c2 = x2.shape[-1] if x2 is not None else 0
+    wsb = conv3x3_wino_ws_bytes(c1, c2, b, h, w, cout) if allow_split else 0
+    ws = workspace(wsb, x1.device).data_ptr() if wsb else None
+    check(lib().psld_conv3x3_wino_gn_x3_f32(x1.data_ptr(), c1, st1.scale.data_ptr(), st1.shift.data_ptr(), _p(x2), c2,
+                                            st2.scale.data_ptr() if st2 is not None else None,
+                                            st2.shift.data_ptr() if st2 is not None else None, 1 if act else 0, b, h, w,
+                                            ufrag.data_ptr(), cout, y.data_ptr(), y.shape[-1],
+                                            C.byref(epi) if epi is not None else None, ws, wsb, _stream()),
+          "psld_conv3x3_wino_gn_x3_f32")
 
 
 _WINO_MODE = None     # 0: never, 1: where it pays (default), 2: wherever the kernel takes the shape (tests)
@@ -391,6 +442,46 @@ def gemm_split(a1: Tensor, a2: Optional[Tensor], m: int, bfrag: Tensor, n: int, 
     check(lib().psld_gemm_split_f32(a1.data_ptr(), k1, _p(a2), k2, m, bfrag.data_ptr(), n, y.data_ptr(),
                                     ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
                                     ws, wsb, _stream()), "psld_gemm_split_f32")
+
+
+# ---- two limbs (math mode 'bf16x3'): the forward GEMMs the eight-wave pointwise kernel takes -------------------------
+@functools.lru_cache(maxsize=None)
+def gemm_split_x3_supported(k1: int, k2: int, m: int, n: int) -> bool:
+    return bool(lib().psld_gemm_split_x3_supported(k1, k2, m, n))
+
+
+def gemm_split_x3_wanted(k1: int, k2: int, m: int, n: int) -> bool:
+    """Policy of math mode 'bf16x3': the forward GEMMs that gemm_split runs on the eight-wave kernel (at least 128 tiles of
+    128 x 256) run its two-limb form; smaller launches stay on gemm_split's four-wave split-K kernel."""
+    return gemm_split_x3_supported(k1, k2, m, n) and -(-m // 128) * (n // 256) >= 128
+
+
+def gemm_frag_bytes_x3(n: int, k: int) -> int:
+    return int(lib().psld_gemm_frag_bytes_x3(n, k))
+
+
+def gemm_frag_x3(b: Tensor, n: int, k: int, stride_n: int, stride_k: int, out: Optional[Tensor] = None) -> Tensor:
+    """gemm_frag with the hi and mid limb planes only (psld_gemm_frag_bytes_x3 bytes)."""
+    if out is None:
+        out = torch.empty(gemm_frag_bytes_x3(n, k), dtype=torch.uint8, device=b.device)
+    check(lib().psld_pack_gemm_frag_x3(b.data_ptr(), out.data_ptr(), n, k, stride_n, stride_k, _stream()),
+          "psld_pack_gemm_frag_x3")
+    return out
+
+
+def pack_frag_batch_x3(table: Tensor, entries: int, total_items: int):
+    """pack_frag_batch into two-limb fragment buffers (pointwise rows: taps = 1)."""
+    check(lib().psld_pack_frag_batch_x3(table.data_ptr(), entries, total_items, _stream()), "psld_pack_frag_batch_x3")
+
+
+def gemm_split_x3(a1: Tensor, a2: Optional[Tensor], m: int, bfrag: Tensor, n: int, y: Tensor,
+                  epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
+    """gemm_split on two-limb fragments (gemm_frag_x3), for the shapes gemm_split_x3_supported takes."""
+    k1 = a1.shape[-1]
+    k2 = a2.shape[-1] if a2 is not None else 0
+    check(lib().psld_gemm_split_x3_f32(a1.data_ptr(), k1, _p(a2), k2, m, bfrag.data_ptr(), n, y.data_ptr(),
+                                       ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
+                                       _stream()), "psld_gemm_split_x3_f32")
 
 
 @functools.lru_cache(maxsize=None)

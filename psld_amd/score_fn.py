@@ -241,7 +241,11 @@ class _Exec:
         self.side_queue = []        # (fn, tensors) waiting for the next fork
         self.side_group = net.side_group
         self.want_dx = False        # gradient w.r.t. the network input requested (x.requires_grad)
-        self.split = ops.math_mode() == "bf16x6"   # 3x3 convs on the bf16 limb kernels (csrc/conv_split.hip)
+        mode = ops.math_mode()
+        self.split = mode in ("bf16x6", "bf16x3")   # 3x3 convs on the bf16 limb kernels (csrc/conv_split.hip)
+        # 'bf16x3' (reduced-precision inference): a forward that records no backward pass runs the two-limb form of every
+        # Winograd-forward / pointwise-forward launch that has one; a recording pass is the 'bf16x6' one, launch for launch
+        self.x3 = mode == "bf16x3" and not record
         import os as _os
         self.limb_planes = _os.environ.get("PSLD_LIMB_PLANES", "1") != "0"    # A/B switch for tools/bench_sample.py
         # forward attention in one kernel (attention.hip) wherever it takes the shape (B=128: 8x8 maps 17 vs 54 us of the
@@ -555,11 +559,30 @@ class _Exec:
         c2 = x2.shape[-1] if x2 is not None else 0
         cout = conv.weight.shape[0]
         if self.split and not isinstance(x, ops.LimbPlanes) and self.wino_wanted(c, c2, b, h, w, cout):
-            ops.conv3x3_wino(x, x2, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)   # Winograd F(2x2, 3x3)
+            if self.x3:
+                ops.conv3x3_wino_x3(x, x2, self.net._wfrag_x3(conv), cout, out, epi, allow_split=True)
+            else:
+                ops.conv3x3_wino(x, x2, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)   # Winograd F(2x2, 3x3)
         elif self.split and ops.conv3x3_split_supported(c, c2, b, h, w, cout):
             ops.conv3x3_split(x, x2, self.net._frag(conv, False), cout, out, epi)
         else:
             ops.conv2d_nhwc(x, x2, self.net._packed(conv), cout, 3, 3, 1, 1, 1, h, w, out, epi)
+
+    def conv3_gn(self, x: Tensor, st, x2: Optional[Tensor], st2, conv: _Affine, out: Tensor, epi):
+        """SiLU(GroupNorm(.)) + 3x3 convolution in one launch (ops.conv3x3_wino_gn; inference forward only)."""
+        cout = conv.weight.shape[0]
+        if self.x3:
+            ops.conv3x3_wino_gn_x3(x, st, x2, st2, True, self.net._wfrag_x3(conv), cout, out, epi, allow_split=True)
+        else:
+            ops.conv3x3_wino_gn(x, st, x2, st2, True, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)
+
+    def gemm_fwd(self, a1: Tensor, a2: Optional[Tensor], m: int, n: int, y: Tensor, epi, frag, frag_x3):
+        """Forward pointwise GEMM on the limb kernels; ``frag()`` / ``frag_x3()``: its three- / two-limb fragments."""
+        k1, k2 = a1.shape[-1], a2.shape[-1] if a2 is not None else 0
+        if self.x3 and ops.gemm_split_x3_wanted(k1, k2, m, n):
+            ops.gemm_split_x3(a1, a2, m, frag_x3(), n, y, epi)
+        else:
+            ops.gemm_split(a1, a2, m, frag(), n, y, epi)
 
     # -- few-channel 3x3 convolutions (6-channel stem / first pyramid level in, 6-channel head out) as K = 64 GEMMs ----
     # K = 9*6 = 54 does not fit the tile engine's 32-channel chunking, so these convolutions used its scalar-gather
@@ -799,8 +822,7 @@ class _Exec:
         h1p = self.part_for(b, ho * wo, cout, h1.device, ops.conv3x3_split_supported(c1, c2_, b, ho, wo, cout))
         epi0 = ops.epilogue(bias=mod.Conv_0.bias, rowbias=tp, rows_per_img=ho * wo, ld_rowbias=tp_ld, gn_part=h1p, gn_hw=ho * wo)
         if fuse0:
-            ops.conv3x3_wino_gn(x.v, st0, xb.v if xb is not None else None, st0b, True, net._wfrag(mod.Conv_0, False), cout,
-                                h1, epi0, allow_split=True)
+            self.conv3_gn(x.v, st0, xb.v if xb is not None else None, st0b, mod.Conv_0, h1, epi0)
         else:
             self.conv3(a0r, mod.Conv_0, h1, epi0, x2=a0b)
         st1 = self.node_stats(_Node(h1, h1p), gn1.weight, gn1.bias)
@@ -816,8 +838,9 @@ class _Exec:
         if mod.has_shortcut:
             c2 = mod.Conv_2
             if self.split and ops.gemm_split_supported(c1, cin - c1, b * ho * wo, cout):
-                fr = net._pfrag(c2.weight, "fwd", cout, cin, cin, 1)
-                ops.gemm_split(xr, xb.v if xb is not None else None, b * ho * wo, fr, cout, out, ops.epilogue(bias=c2.bias))
+                self.gemm_fwd(xr, xb.v if xb is not None else None, b * ho * wo, cout, out, ops.epilogue(bias=c2.bias),
+                              lambda: net._pfrag(c2.weight, "fwd", cout, cin, cin, 1),
+                              lambda: net._pfrag(c2.weight, "fwd_x3", cout, cin, cin, 1))
             else:
                 ops.conv2d_nhwc(xr, xb.v if xb is not None else None, c2.weight, cout, 1, 1, 1, 0, 1, ho, wo, out,
                                 ops.epilogue(bias=c2.bias))
@@ -827,7 +850,7 @@ class _Exec:
         outp = self.part_for(b, ho * wo, cout, out.device, ops.conv3x3_split_supported(cout, 0, b, ho, wo, cout))
         epi1 = ops.epilogue(bias=mod.Conv_1.bias, residual=res, ld_residual=cout, out_scale=s, gn_part=outp, gn_hw=ho * wo)
         if fuse1:
-            ops.conv3x3_wino_gn(h1, st1, None, None, True, net._wfrag(mod.Conv_1, False), cout, out, epi1, allow_split=True)
+            self.conv3_gn(h1, st1, None, None, mod.Conv_1, out, epi1)
         else:
             self.conv3(a1, mod.Conv_1, out, epi1)
         on = _Node(out, outp, want_gsum=True)       # Conv_1.bias (and Conv_2.bias) = s * column sums of its gradient
@@ -1005,7 +1028,7 @@ class _Exec:
         if fused:
             f_qkv, f_qkv_d, b_qkv = net._qkv_frags(mod)
             qkv = torch.empty((b, hw, 3 * c), device=dev, dtype=torch.float32)
-            ops.gemm_split(hn, None, m, f_qkv, 3 * c, qkv, ops.epilogue(bias=b_qkv))
+            self.gemm_fwd(hn, None, m, 3 * c, qkv, ops.epilogue(bias=b_qkv), lambda: f_qkv, lambda: net._qkv_frags_x3(mod))
             q, k, v = qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:]
             ld = 3 * c
         else:
@@ -1031,8 +1054,8 @@ class _Exec:
         outp = self.part_for(b, hw, c, dev, fused)
         epi_out = ops.epilogue(bias=n3.b, residual=x.v, ld_residual=c, out_scale=s, gn_part=outp, gn_hw=hw)
         if fused:
-            f_o = net._pfrag(n3.W, "fwd", c, c, 1, c)
-            ops.gemm_split(ho, None, m, f_o, c, out, epi_out)
+            self.gemm_fwd(ho, None, m, c, out, epi_out, lambda: net._pfrag(n3.W, "fwd", c, c, 1, c),
+                          lambda: net._pfrag(n3.W, "fwd_x3", c, c, 1, c))
         else:
             ops.gemm_raw(0, 0, m, c, c, ho, c, 0, n3.W, c, 0, out, c, 0, epi=epi_out)
         on = _Node(out, outp, want_gsum=True)       # NIN_3.b = s * column sums of its gradient
@@ -1150,9 +1173,11 @@ class _Exec:
             cols = self.small_in_conv(xf, conv, 2, 0, oh, ow, out, epi)
         elif limb:
             patches = ops.im2col3x3(xf, 2, 0, oh, ow)
-            fr = net._wcache.get(conv.weight, "s2fwd", _built_entry,
-                                 lambda prev: ops.gemm_frag(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev))
-            ops.gemm_split(patches, None, m, fr, cout, out, epi)
+            self.gemm_fwd(patches, None, m, cout, out, epi,
+                          lambda: net._wcache.get(conv.weight, "s2fwd", _built_entry,
+                                                  lambda prev: ops.gemm_frag(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev)),
+                          lambda: net._wcache.get(conv.weight, "s2fwd_x3", _built_entry,
+                                                  lambda prev: ops.gemm_frag_x3(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev)))
             del patches
         else:
             ops.conv2d_nhwc(xf, None, self.net._packed(conv), cout, 3, 3, 2, 0, 1, oh, ow, out, epi)
@@ -1514,19 +1539,29 @@ def _frag_entry(w: Tensor, dgrad: bool, wino: bool) -> Entry:
                  rows=lambda out: [(row(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
 
 
+def _wfrag_x3_entry(w: Tensor) -> Entry:
+    """Two-limb Winograd fragments (forward orientation): the 'wino' entries' sibling for math mode 'bf16x3'."""
+    return Entry(w, build=lambda prev: ops.conv3x3_wino_frag_x3(w.detach(), prev), family="wino_x3",
+                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, False, out), w.shape[0] * w.shape[1] // 8)], graph=True)
+
+
 def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor], chunk0: int,
                  chunks_total: int) -> Entry:
+    x3 = tag.endswith("_x3")        # two-limb fragments (math mode 'bf16x3'): their own packers and batch family
+    pack, pack_batch = (ops.gemm_frag_x3, ops.pack_frag_batch_x3) if x3 else (ops.gemm_frag, ops.pack_frag_batch)
+
     def rows(out):
         return [([p.data_ptr(), out.data_ptr(), n, k | (chunk0 << 20) | (chunks_total << 40), 1, sn, sk], n * k // 8)]
 
     def build(prev):
         if into is None:
-            return ops.gemm_frag(p.detach(), n, k, sn, sk, prev)
+            return pack(p.detach(), n, k, sn, sk, prev)
         # a one-entry table through the batched entry point (the only one that takes a K placement)
         (row, items), = rows(into)
-        ops.pack_frag_batch(torch.tensor(row + [0], dtype=torch.int64, device=p.device), 1, items)
+        pack_batch(torch.tensor(row + [0], dtype=torch.int64, device=p.device), 1, items)
         return into
-    return Entry(p, build=build, family="limb", rows=rows, graph=tag in ("fwd", "qkv_f"))
+    return Entry(p, build=build, family="limb_x3" if x3 else "limb", rows=rows,
+                 graph=tag in ("fwd", "qkv_f", "fwd_x3", "qkv_f_x3"))
 
 
 def _built_entry(owner: Tensor, build) -> Entry:
@@ -1687,6 +1722,7 @@ class NCSNpp(nn.Module):
         self._offsets = None
         # derived weights; a batched refresh needs two entries of a limb / Winograd family, one of a gathered copy
         self._wcache = WeightCache({"limb": (ops.pack_frag_batch, 2), "wino": (ops.pack_wino_batch, 2),
+                                    "limb_x3": (ops.pack_frag_batch_x3, 2), "wino_x3": (ops.pack_wino_batch_x3, 2),
                                     "qkv_bias": (ops.copy_batch, 1), "temb": (ops.copy_batch, 1)})
         self._anchor = None
         self._reducer = None
@@ -1836,12 +1872,16 @@ class NCSNpp(nn.Module):
         """Winograd-transformed bf16 limb fragments of a 3x3 weight (ops.conv3x3_wino_frag)."""
         return self._wcache.get(conv.weight, "dwfrag" if dgrad else "wfrag", _frag_entry, dgrad, True)
 
+    def _wfrag_x3(self, conv: _Affine) -> Tensor:
+        """Two-limb Winograd fragments of a 3x3 weight, forward orientation (ops.conv3x3_wino_frag_x3)."""
+        return self._wcache.get(conv.weight, "wfrag_x3", _wfrag_x3_entry)
+
     def _pfrag(self, owner: nn.Parameter, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor] = None,
                chunk0: int = 0, chunks_total: int = 0) -> Tensor:
         """Limb fragments (ops.gemm_frag) of the [n][k] view of ONE parameter (element (i, j) at i*sn + j*sk), refreshed
         together with the 3x3 fragments by the batched launch.  ``into``: the buffer to fill (several parameters that
         share one fragment set: q | k | v) - then ``chunk0`` / ``chunks_total`` place this parameter's K range inside the
-        set's K dimension (psld_pack_frag_batch)."""
+        set's K dimension (psld_pack_frag_batch).  A ``tag`` ending in ``_x3``: two-limb fragments (ops.gemm_frag_x3)."""
         return self._wcache.get(owner, tag, _pfrag_entry, tag, n, k, sn, sk, into, chunk0, chunks_total)
 
     def _qkv_frags(self, mod):
@@ -1861,6 +1901,17 @@ class NCSNpp(nn.Module):
             # data gradient: the three projections are concatenated along K
             self._pfrag(nin.W, "qkv_d", c, c, c, 1, into=pd, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
         return self._wcache.fresh(e)
+
+    def _qkv_frags_x3(self, mod):
+        """The forward q | k | v fragment set of _qkv_frags in two-limb form (math mode 'bf16x3')."""
+        n0 = mod.NIN_0
+        c = n0.W.shape[0]
+        fb = ops.gemm_frag_bytes_x3(c, c)
+        pf = self._wcache.entry(n0.W, "qkv_x3", lambda w: Entry(
+            w, out=torch.empty(3 * fb, dtype=torch.uint8, device=w.device), build=lambda prev: prev)).out
+        for i, nin in enumerate((n0, mod.NIN_1, mod.NIN_2)):
+            self._pfrag(nin.W, "qkv_f_x3", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
+        return pf
 
     def _temb_plan(self):
         """Gathered time-embedding projections ``(wcat, bcat, offsets)``: wcat [sum C_out][4*nf] and bcat [sum C_out]
@@ -2013,7 +2064,7 @@ class NCSNpp(nn.Module):
             self._graphs = {}
 
     def _graph_forward(self, x: Tensor, t: Tensor) -> Tensor:
-        key = (tuple(x.shape), x.device.index)
+        key = (tuple(x.shape), x.device.index, ops.math_mode())     # a capture replays the launches of its math mode
         ent = self._graphs.get(key)
         if ent is None:
             sx, st = x.clone(), t.clone()
