@@ -1,0 +1,98 @@
+"""Derived-weight entries of NCSNpp (weight_cache.py): ``make(owner, *args) -> Entry``, called on first use."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import ops
+from .score_modules import ResnetBlockBigGANpp
+from .weight_cache import Entry
+
+Tensor = torch.Tensor
+
+
+def _packed_entry(w: Tensor, dgrad: bool) -> Entry:
+    co, ci, kh, kw = w.shape
+
+    def build(prev):
+        out = prev if prev is not None else \
+            torch.empty((ci, kh * kw, co) if dgrad else (co, kh * kw, ci), device=w.device, dtype=torch.float32)
+        (ops.pack_dgrad if dgrad else ops.pack_ohwi)(w.detach(), out)
+        return out
+    return Entry(w, build=build, graph=not dgrad)
+
+
+def _frag_entry(w: Tensor, dgrad: bool, wino: bool) -> Entry:
+    pack, row = (ops.conv3x3_wino_frag, ops.conv3x3_wino_frag_entry) if wino else \
+        (ops.conv3x3_frag, ops.conv3x3_frag_entry)
+    return Entry(w, build=lambda prev: pack(w.detach(), dgrad, prev), family="wino" if wino else "limb",
+                 rows=lambda out: [(row(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
+
+
+def _wfrag_x3_entry(w: Tensor) -> Entry:
+    """Two-limb Winograd fragments (forward orientation): the 'wino' entries' sibling for math mode 'bf16x3'."""
+    return Entry(w, build=lambda prev: ops.conv3x3_wino_frag_x3(w.detach(), prev), family="wino_x3",
+                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, False, out), w.shape[0] * w.shape[1] // 8)], graph=True)
+
+
+def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor], chunk0: int,
+                 chunks_total: int) -> Entry:
+    x3 = tag.endswith("_x3")        # two-limb fragments (math mode 'bf16x3'): their own packers and batch family
+    pack, pack_batch = (ops.gemm_frag_x3, ops.pack_frag_batch_x3) if x3 else (ops.gemm_frag, ops.pack_frag_batch)
+
+    def rows(out):
+        return [([p.data_ptr(), out.data_ptr(), n, k | (chunk0 << 20) | (chunks_total << 40), 1, sn, sk], n * k // 8)]
+
+    def build(prev):
+        if into is None:
+            return pack(p.detach(), n, k, sn, sk, prev)
+        # a one-entry table through the batched entry point (the only one that takes a K placement)
+        (row, items), = rows(into)
+        pack_batch(torch.tensor(row + [0], dtype=torch.int64, device=p.device), 1, items)
+        return into
+    return Entry(p, build=build, family="limb_x3" if x3 else "limb", rows=rows,
+                 graph=tag in ("fwd", "qkv_f", "fwd_x3", "qkv_f_x3"))
+
+
+def _built_entry(owner: Tensor, build) -> Entry:
+    """Fragments built by ``build(prev)`` from ``owner`` (and possibly sibling parameters)."""
+    return Entry(owner, build=build, graph=True)
+
+
+def _qkv_entry(b0: Tensor, mod: "AttnBlockpp") -> Entry:
+    """out: the forward and data-gradient q | k | v fragment sets (filled by the "qkv_f" / "qkv_d" entries) and the
+    gathered [b_q | b_k | b_v] (filled by the "qkv_bias" family's batched copy)."""
+    c = b0.numel()
+    fb = ops.gemm_frag_bytes(c, c)
+    out = (torch.empty(3 * fb, dtype=torch.uint8, device=b0.device),
+           torch.empty(3 * fb, dtype=torch.uint8, device=b0.device),
+           torch.empty(3 * c, dtype=torch.float32, device=b0.device))
+
+    def rows(out):
+        bq = out[2]
+        return [([nin.b.data_ptr(), bq.data_ptr() + 4 * i * c, c // 4], c // 4)
+                for i, nin in enumerate((mod.NIN_0, mod.NIN_1, mod.NIN_2))]
+    return Entry(b0, out=out, family="qkv_bias", rows=rows, graph=True)
+
+
+def _temb_entry(w0: Tensor, modules) -> Entry:
+    """out: (wcat, bcat, {block: first row}) of NCSNpp._temb_plan, filled by the "temb" family's batched copy."""
+    offsets, total = {}, 0
+    for m in modules:
+        if isinstance(m, ResnetBlockBigGANpp):
+            offsets[m] = total
+            total += m.Dense_0.weight.shape[0]
+    out = (torch.empty((total, w0.shape[1]), device=w0.device, dtype=torch.float32),
+           torch.empty((total,), device=w0.device, dtype=torch.float32), offsets)
+
+    def rows(out):
+        wcat, bcat, offsets = out
+        r = []
+        for m, o in offsets.items():
+            w, bias = m.Dense_0.weight, m.Dense_0.bias
+            for src, dst, n in ((w, wcat[o], w.numel()), (bias, bcat[o:], bias.numel())):
+                assert n % 4 == 0 and src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0
+                r.append(([src.data_ptr(), dst.data_ptr(), n // 4], n // 4))
+        return r
+    return Entry(w0, out=out, family="temb", rows=rows, graph=True)

@@ -25,7 +25,8 @@ sys.path.insert(0, ROOT)
 
 PEAK = 8.0e12
 SOURCES = ["psld_amd/csrc/norm_act.hip", "psld_amd/csrc/resample.hip", "psld_amd/csrc/pointwise.hip", "psld_amd/csrc/optim.hip",
-           "psld_amd/csrc/sde.hip", "psld_amd/csrc/wgrad_wino.hip", "psld_amd/csrc/common.h", "psld_amd/score_fn.py"]
+           "psld_amd/csrc/sde.hip", "psld_amd/csrc/wgrad_wino.hip", "psld_amd/csrc/common.h", "psld_amd/score_fn.py",
+           "psld_amd/score_exec.py", "psld_amd/score_tape.py", "psld_amd/score_routes.py"]
 
 # entry point -> (family, bytes(args))
 def _b(fam, fn):
