@@ -302,6 +302,41 @@ int psld_gemm_tn_split_supported(int m, int n, int k);
 int psld_gemm_tn_split_f32(int m, int n, int k, const float* a, int lda, const float* b, int ldb,
                            const float* b2, int ldb2, int n2, float* slabs, int ldc, int nsplit, hipStream_t stream);
 
+/* Pointwise limb GEMMs for channel widths in steps of 32 ("tail" shapes: the 160 / 320 / 480-wide levels of an nf = 160
+ * network), beside the entry points above, whose predicates and kernels are unchanged.
+ *
+ * Forward / data gradient: y[m][n] = epilogue(a[m][k] * B^T), one source.  psld_gemm_tail_supported: k % 32 == 0, n % 32 == 0,
+ * k >= 128, n >= 128, m > 0 and NOT a shape of psld_gemm_split_supported(k, 0, m, n) (so n % 128 != 0 or k % 64 != 0).
+ * Fragments: three limbs in psld_pack_gemm_frag's [n tile][half][chunk][block][limb][lane] layout with n rounded up to 128 and
+ * k to 64: psld_gemm_frag_bytes_tail(n, k) = roundup(n, 128) * roundup(k, 64) * 6 bytes.  The packer writes the rows and the
+ * K chunk beyond the tensor as zero limbs and reads b only inside [n][k].
+ * psld_pack_frag_batch_tail: many tensors in one launch, psld_pack_frag_batch's table (8 x int64 per tensor: source, fragment
+ * set, n, k, taps = 1, stride_n, stride_k, first work item) with the placement inside a shared set in the high bits of the n
+ * and k fields: n | n0 << 20 | n_total << 40 (the tensor is rows n0 .. n0 + n of a set of n_total rows) and
+ * k | chunk0 << 20 | chunks_total << 40 (it is the 32-wide K chunks chunk0 .. chunk0 + k/32 of chunks_total); zeros: the
+ * tensor is the whole dimension.  The tensor that ends a dimension writes that dimension's zero padding, so the tensors of a
+ * set write every byte of its psld_gemm_frag_bytes_tail(n_total, 32 * chunks_total).  A tensor has
+ * psld_pack_frag_tail_items(n, n0, n_total, k, chunk0, chunks_total) work items.
+ * psld_gemm_split_tail_f32: the four-wave kernel of psld_gemm_split_f32 on 128 x 128 tiles with the last column tile cut
+ * short; every epilogue of psld_gemm_split_f32 (bias, row bias, residual, alpha, out_scale, accumulate, strided ldy) and
+ * its split-K through the workspace for small m - except gn_part, which is refused (PSLD_ERR_ARG, nothing written).  Reads
+ * exactly a[m][k] and columns [0, n) of residual / bias / row bias / y; on a launch without split-K every output element is
+ * bit for bit column < n of psld_gemm_split_f32 on the same data zero-padded to roundup(n, 128) x roundup(k, 64).
+ *
+ * Weight gradient: psld_gemm_tn_split_f32's slabs (one B source) for m, n multiples of 32 from 128 up that are not both
+ * multiples of 128, k % 32 == 0; loads beyond column m of a / n of b are masked, slab rows / columns beyond them not stored. */
+int psld_gemm_tail_supported(int k, int m, int n);
+long long psld_gemm_frag_bytes_tail(int n, int k);
+int psld_pack_gemm_frag_tail(const float* b, void* bfrag, int n, int k, long long stride_n, long long stride_k,
+                             hipStream_t stream);
+long long psld_pack_frag_tail_items(int n, int n0, int n_total, int k, int chunk0, int chunks_total);
+int psld_pack_frag_batch_tail(const long long* table_dev, int entries, long long total_items, hipStream_t stream);
+int psld_gemm_split_tail_f32(const float* a, int k, int m, const void* bfrag, int n, float* y, int ldy,
+                             const psld_epilogue_t* epi, void* workspace, long long ws_bytes, hipStream_t stream);
+int psld_gemm_tn_split_tail_supported(int m, int n, int k);
+int psld_gemm_tn_split_tail_f32(int m, int n, int k, const float* a, int lda, const float* b, int ldb, float* slabs,
+                                int ldc, int nsplit, hipStream_t stream);
+
 /* Batched GEMM on the limb kernels with BOTH operands fp32 activations (split inside the kernel):
  * c[b][i][j] = alpha * sum_p A(i,p) B(p,j);  ta: a is stored [k][m] (else [m][k]); tb: b is stored [n][k] (else [k][n]);
  * same operand conventions as psld_gemm_f32, not both transposed.  m, n multiples of 128, k of 32.  Replaces the

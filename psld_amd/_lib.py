@@ -128,6 +128,14 @@ SIGNATURES = {
     "psld_conv3x3_wgrad_wino_f32": (I, [P, I, I, P, I, P, I, I, I, I, P, I, P, I, F, P]),
     "psld_gemm_tn_split_supported": (I, [I, I, I]),
     "psld_gemm_tn_split_f32": (I, [I, I, I, P, I, P, I, P, I, I, P, I, I, P]),
+    "psld_gemm_tail_supported": (I, [I, I, I]),
+    "psld_gemm_frag_bytes_tail": (LL, [I, I]),
+    "psld_pack_gemm_frag_tail": (I, [P, P, I, I, LL, LL, P]),
+    "psld_pack_frag_tail_items": (LL, [I, I, I, I, I, I]),
+    "psld_pack_frag_batch_tail": (I, [P, I, LL, P]),
+    "psld_gemm_split_tail_f32": (I, [P, I, I, P, I, P, I, EP, P, LL, P]),
+    "psld_gemm_tn_split_tail_supported": (I, [I, I, I]),
+    "psld_gemm_tn_split_tail_f32": (I, [I, I, I, P, I, P, I, P, I, I, P]),
     "psld_bgemm_split_supported": (I, [I, I, I, I, I]),
     "psld_bgemm_split_f32": (I, [I, I, I, I, I, P, I, LL, P, I, LL, P, I, LL, I, F, P]),
     "psld_reduce_slabs_f32": (I, [P, I, LL, P, I, I, I, I, F, P]),

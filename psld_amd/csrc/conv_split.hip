@@ -116,6 +116,69 @@ __global__ void pack_frag_batch_kernel(const long long* __restrict__ tab, int nt
     }
 }
 
+// ---- pointwise fragments of tensors that are no whole number of tiles ("tail": n, k multiples of 32) ----------------------
+// Same [nt][wc][chunk][nb][limb][lane] layout, three limbs, taps = 1.  The fragment set has pad128(n_total) rows and
+// pad2(chunks_total) K chunks (the pointwise kernel stages two chunks at a time); the tensor [n_in][k_in] fills rows n0 ..
+// n0 + n_in and chunks chunk0 .. chunk0 + k_in / 32 of it.  The tensor that ends the set's rows (n0 + n_in == n_total) also
+// writes the rows up to the next multiple of 128, the one that ends its K dimension also writes the odd chunk behind it - as
+// ZERO limbs, without reading its source there - so the tensors of a set together write every byte of it.
+__host__ __device__ inline int tail_rows(int n_in, int n0, int n_total) {
+    return n0 + n_in == n_total ? ((n_total + 127) & ~127) - n0 : n_in;
+}
+__host__ __device__ inline int tail_chunks(int k_in, int chunk0, int chunks_total) {
+    return chunk0 + k_in / 32 == chunks_total ? ((chunks_total + 1) & ~1) - chunk0 : k_in / 32;
+}
+
+// One work item = one lane slot (16-row block, chunk, lane) of the tensor's extended region, all three limbs.
+__device__ __forceinline__ void pack_tail_item(const float* __restrict__ w, u32x4* __restrict__ out, long long item, int n_in,
+                                               int n0, int n_total, int k_in, int chunk0, int chunks_total, long long sn,
+                                               long long sk) {
+    if (n_total == 0) n_total = n_in;
+    if (chunks_total == 0) chunks_total = k_in / 32;
+    const int kc = tail_chunks(k_in, chunk0, chunks_total), ct = (chunks_total + 1) & ~1;
+    long long t = item;
+    const int lane = (int)(t & 63); t >>= 6;
+    const int chunk = (int)(t % kc); t /= kc;
+    const int r = (int)t * 16 + (lane & 15);        // row of the tensor
+    const int n = n0 + r;                           // row of the set
+    const int k0 = chunk * 32 + (lane >> 4) * 8;
+    unsigned hi[4] = {0, 0, 0, 0}, mid[4] = {0, 0, 0, 0}, lo[4] = {0, 0, 0, 0};
+    if (r < n_in && k0 < k_in) {
+        const float* p = w + r * sn + k0 * sk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) split3(p[(2 * j) * sk], p[(2 * j + 1) * sk], hi[j], mid[j], lo[j]);
+    }
+    const int nt = n >> 7, wc = (n >> 6) & 1, nb = (n >> 4) & 3;
+    u32x4* o = out + ((((long long)(nt * 2 + wc) * ct + chunk0 + chunk) * 4 + nb) * 3) * 64 + lane;
+    o[0] = u32x4{hi[0], hi[1], hi[2], hi[3]};
+    o[64] = u32x4{mid[0], mid[1], mid[2], mid[3]};
+    o[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+}
+
+__global__ void pack_tail_kernel(const float* __restrict__ w, u32x4* __restrict__ out, int n, int k, long long sn,
+                                 long long sk, long long items) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (long long)gridDim.x * blockDim.x)
+        pack_tail_item(w, out, i, n, 0, 0, k, 0, 0, sn, sk);
+}
+
+// pack_frag_batch_kernel's table; the row placement rides in the n field like the K placement in the k field:
+// tab[8*i + 2] = n_in | n0 << 20 | n_total << 40, tab[8*i + 3] = k_in | chunk0 << 20 | chunks_total << 40, taps = 1, no flip.
+// A tensor has tail_rows(..) * tail_chunks(..) * 4 items.
+__global__ void pack_tail_batch_kernel(const long long* __restrict__ tab, int ntab, long long total) {
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        int lo = 0, hi = ntab - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (tab[8 * mid + 7] <= idx) lo = mid; else hi = mid - 1;
+        }
+        const long long* d = tab + 8 * lo;
+        pack_tail_item(reinterpret_cast<const float*>(d[0]), reinterpret_cast<u32x4*>(d[1]), idx - d[7], (int)(d[2] & 0xfffff),
+                       (int)((d[2] >> 20) & 0xfffff), (int)((d[2] >> 40) & 0xfffff), (int)(d[3] & 0xfffff),
+                       (int)((d[3] >> 20) & 0xfffff), (int)((d[3] >> 40) & 0xfffff), d[5], d[6]);
+    }
+}
+
 template <int NL = 3>
 int launch_pack(const float* w, void* out, int n_out, int k_in, int taps, long long sn, long long sk, long long st,
                 int flip, hipStream_t stream, const char* name) {
@@ -317,23 +380,30 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
 // wave; the 2 x 2 arrangement of 64 x 64 tiles of round 1 loaded every fragment twice).
 // MT: pixel rows per workgroup tile, 128 or - 3x3 only - 64 (wave tile 64 x 32): twice the workgroups for output
 // grids too small to fill the chip, instead of (or with a shallower) split of the K range.
-template <int NH, int TAPS, bool PW, int MT = 128>
+// TAIL (pointwise, one source; psld_gemm_split_tail_f32): N and C1 are multiples of 32, not of 128 / 64.  The last column
+// tile is cut short - a wave whose 32 channels lie at or beyond N stages its share of A and keeps the barriers, but loads no
+// fragments, issues no MFMAs and has no epilogue - and the items of a chunk at or beyond C1 (the odd chunk behind the last
+// one) read the zero page.  The fragment set is padded to whole tiles and an even chunk count with zero limbs
+// (pack_tail_item), so every output element sees the chunks and limb products of a full-tile launch on zero-padded data.
+template <int NH, int TAPS, bool PW, int MT = 128, bool TAIL = false>
 __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
     static_assert(MT == 128 || (MT == 64 && !PW), "64-row tiles exist for the 3x3 kernels");
+    static_assert(!TAIL || PW, "cut tiles exist for the pointwise kernel");
     constexpr int MBK = MT / 16, NBK = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int LIMB = NH * 32 * ROWB;
     static_assert(!PW || NH == 4 * TAPS, "pointwise staging: 128 rows x 8 quads per 32-channel chunk");
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = TAIL ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int wc = wave >> 1;
     const int c4 = tid & 7;
 
-    const int tiles_n = a.N >> 7;
+    const int tiles_n = TAIL ? (a.N + 127) >> 7 : a.N >> 7;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_m = bid / tiles_n, tile_n = bid - tile_m * tiles_n;
     const int m0 = dconv_tile_m0(a, tile_m, MT), n0 = tile_n * 128;
+    const bool live = !TAIL || n0 + wave * 32 < a.N;            // wave-uniform; always true without TAIL
     const int split = blockIdx.y;
     const int c_beg = split * a.chunks_per_split;               // stages: chunks (conv) or groups of TAPS chunks (PW)
     const int c_end = min(a.chunks, c_beg + a.chunks_per_split);
@@ -375,7 +445,8 @@ __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
             const float* src = second ? a.x2 : a.x1;
             const int cs = second ? a.C2 : a.C1;
             const int cc = (second ? c0 - a.C1 : c0) + c4 * 4;
-            hv[i] = ld4(hoff[i] >= 0 ? src + ((long long)hoff[i] * cs + cc) : zp);
+            if constexpr (TAIL) hv[i] = ld4(hoff[i] >= 0 && c0 < a.C1 ? a.x1 + ((long long)hoff[i] * a.C1 + c0 + c4 * 4) : zp);
+            else hv[i] = ld4(hoff[i] >= 0 ? src + ((long long)hoff[i] * cs + cc) : zp);
         }
     };
     auto store_halo = [&]() {
@@ -430,7 +501,7 @@ __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
         for (int j = 0; j < NBK; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
     load_halo(c_beg);
-    load_b(sig_beg, bq[0]);
+    if (live) load_b(sig_beg, bq[0]);
     store_halo();
     __syncthreads();
 
@@ -441,26 +512,28 @@ __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
         constexpr int pp = decltype(PP)::value;
         const bool more = (c + 1) < c_end;
         if (tap == PREFETCH_TAP && more) load_halo(c + 1);
-        load_b(sigma + 1, bq[pp ^ 1]);
-        u32x4 fa[MBK][3];
+        if (live) {                     // (a compile-time true without TAIL)
+            load_b(sigma + 1, bq[pp ^ 1]);
+            u32x4 fa[MBK][3];
 #pragma unroll
-        for (int mb = 0; mb < MBK; ++mb) {
-            const int prow = abase[mb] + tap_off;
-            const unsigned char* q = smem + prow * ROWB + ((kq ^ lds_swz(prow)) << 4);
+            for (int mb = 0; mb < MBK; ++mb) {
+                const int prow = abase[mb] + tap_off;
+                const unsigned char* q = smem + prow * ROWB + ((kq ^ lds_swz(prow)) << 4);
 #pragma unroll
-            for (int l = 0; l < 3; ++l) fa[mb][l] = *reinterpret_cast<const u32x4*>(q + l * LIMB);
+                for (int l = 0; l < 3; ++l) fa[mb][l] = *reinterpret_cast<const u32x4*>(q + l * LIMB);
+            }
+            // limb products, smallest first: (lo,hi) (hi,lo) (mid,mid) (mid,hi) (hi,mid) (hi,hi)
+            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int mb = 0; mb < MBK; ++mb)
+#pragma unroll
+                    for (int nb = 0; nb < NBK; ++nb)
+                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(       // weights first: D^T (see dconv_epilogue_n32)
+                            __builtin_bit_cast(bf16x8, bq[pp][nb][PB[t]]), __builtin_bit_cast(bf16x8, fa[mb][PA[t]]),
+                            acc[mb][nb], 0, 0, 0);
         }
-        // limb products, smallest first: (lo,hi) (hi,lo) (mid,mid) (mid,hi) (hi,mid) (hi,hi)
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-            for (int mb = 0; mb < MBK; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < NBK; ++nb)
-                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(       // weights first: D^T (see dconv_epilogue_n32)
-                        __builtin_bit_cast(bf16x8, bq[pp][nb][PB[t]]), __builtin_bit_cast(bf16x8, fa[mb][PA[t]]),
-                        acc[mb][nb], 0, 0, 0);
         if (++tap == TAPS) {            // stage done: swap in the next image
             tap = 0; tap_off = 0; kx = 0;
             __syncthreads();
@@ -480,7 +553,7 @@ __global__ void __launch_bounds__(256, 2) dconv_kernel(const DConvArgs a) {
         if (sigma + 1 < sig_end) step(sigma + 1, std::integral_constant<int, 1>{});
     }
 
-    dconv_epilogue_n32<MBK>(a, acc, m0, n0 + wave * 32, lane, split);
+    if (live) dconv_epilogue_n32<MBK>(a, acc, m0, n0 + wave * 32, lane, split);
 }
 
 // ---- forward / data-gradient on pre-split activations ("limb planes") ----------------------------------------------
@@ -1154,8 +1227,10 @@ int launch_dwgrad_ws(const DWgradArgs& a, int nsplit, hipStream_t stream) {
 struct PWgradArgs {
     const float* a;
     int lda;
-    const float* b;
+    int m;                  // TAIL: rows of C (a multiple of 32): the last tile row is cut short.  (m and n sit in what was padding:
+    const float* b;         // the argument block of the full-tile instance is byte for byte what it was)
     int ldb;
+    int n;                  // TAIL: columns of C
     const float* b2;        // second source of a column concatenation of B (or null): columns >= n1 read it
     int ldb2, n1;
     int tiles_i, tiles_j;
@@ -1165,6 +1240,9 @@ struct PWgradArgs {
     long long slab_stride;
 };
 
+// TAIL (psld_gemm_tn_split_tail_f32; one B source): the channel quads of the last tiles that lie beyond m / n are loaded with the
+// all-ones offset - a raw buffer load out of range returns zeros, nothing is read - and their slab rows / columns are not stored.
+template <bool TAIL = false>
 __global__ void __launch_bounds__(256, 2) pwgrad_kernel(const PWgradArgs a) {
     constexpr int RS = 288;                      // 128 channels bf16 + 32 pad
     constexpr int LIMB = 32 * RS;
@@ -1203,6 +1281,10 @@ __global__ void __launch_bounds__(256, 2) pwgrad_kernel(const PWgradArgs a) {
         aoff[i] = (unsigned)((r * a.lda + c * 4) * 4);
         boff[i] = (unsigned)((r * ldb + c * 4) * 4);
         soff[i] = r * RS + c * 8;
+        if constexpr (TAIL) {
+            if (i0 + c * 4 >= a.m) aoff[i] = 0xffffffffu;
+            if (j0 + c * 4 >= a.n) boff[i] = 0xffffffffu;
+        }
     }
     f32x4 va[4], vb[4];
     auto load_tile = [&](int kt) {
@@ -1271,6 +1353,9 @@ __global__ void __launch_bounds__(256, 2) pwgrad_kernel(const PWgradArgs a) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 const int i = i0 + wr * 64 + cb * 16 + 4 * g + v;
+                if constexpr (TAIL) {
+                    if (i >= a.m || j0 + wc * 64 + nb * 16 + i16 >= a.n) continue;
+                }
                 S[(long long)i * a.ldc + j0 + wc * 64 + nb * 16 + i16] = acc[cb][nb][v];
             }
 }
@@ -1660,12 +1745,12 @@ int launch_dwgrad(const DWgradArgs& a, int nsplit, hipStream_t stream) {
     return PSLD_OK;
 }
 
-template <int NH, int TAPS, bool PW, int MT = 128>
+template <int NH, int TAPS, bool PW, int MT = 128, bool TAIL = false>
 int launch_dconv(const DConvArgs& a, int nsplit, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)3 * NH * 32 * ROWB;
     static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dconv_kernel<NH, TAPS, PW, MT>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dconv_kernel<NH, TAPS, PW, MT, TAIL>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
         if (e != hipSuccess) {
             psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
@@ -1673,8 +1758,8 @@ int launch_dconv(const DConvArgs& a, int nsplit, hipStream_t stream, const char*
         }
         configured = true;
     }
-    dim3 grid((unsigned)(cdiv(a.M, MT) * (a.N / 128)), (unsigned)nsplit);
-    hipLaunchKernelGGL((dconv_kernel<NH, TAPS, PW, MT>), grid, dim3(256), LDS, stream, a);
+    dim3 grid((unsigned)(cdiv(a.M, MT) * cdiv(a.N, 128)), (unsigned)nsplit);
+    hipLaunchKernelGGL((dconv_kernel<NH, TAPS, PW, MT, TAIL>), grid, dim3(256), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
 }
@@ -1701,7 +1786,7 @@ int launch_dconv_lp(const DConvArgs& a, int nsplit, hipStream_t stream, const ch
 // split the K stages over extra workgroups when the output grid cannot fill 256 CUs x 2 slots; returns the number
 // of slabs (1 = write the output directly) and fills the slab fields of `a`
 int plan_split(DConvArgs& a, const PsldEpilogue& e, float* y, int ldy, void* workspace, long long ws_bytes, int mt = 128) {
-    const long long tiles = (long long)cdiv(a.M, mt) * (a.N / 128);
+    const long long tiles = (long long)cdiv(a.M, mt) * cdiv(a.N, 128);      // (N % 128 != 0: the cut-tile pointwise launch)
     int ns = 1;
     if (workspace && tiles < 384 && (!e.gn_part || psld_detail_conv_reduce_gn_ok(a.M, a.N, e)) && ldy % 4 == 0 && aligned16(y) && (!e.bias || aligned16(e.bias)) &&
         (!e.rowbias || (aligned16(e.rowbias) && e.ld_rowbias % 4 == 0)) && (!e.res || (aligned16(e.res) && e.ldres % 4 == 0))) {
@@ -2024,7 +2109,7 @@ extern "C" int psld_gemm_tn_split_f32(int m, int n, int k, const float* a, int l
     constexpr size_t LDS = (size_t)2 * 3 * 32 * 288;
     static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwgrad_kernel),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwgrad_kernel<>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
         if (e != hipSuccess) {
             psld_set_error("psld_gemm_tn_split_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
@@ -2032,8 +2117,44 @@ extern "C" int psld_gemm_tn_split_f32(int m, int n, int k, const float* a, int l
         }
         configured = true;
     }
-    hipLaunchKernelGGL(pwgrad_kernel, dim3((unsigned)(p.tiles_i * p.tiles_j * nsplit)), dim3(256), LDS, stream, p);
+    hipLaunchKernelGGL(pwgrad_kernel<>, dim3((unsigned)(p.tiles_i * p.tiles_j * nsplit)), dim3(256), LDS, stream, p);
     PSLD_CHECK_LAUNCH("psld_gemm_tn_split_f32");
+    return PSLD_OK;
+}
+
+// m, n: multiples of 32 from 128 up, not both multiples of 128 (those are psld_gemm_tn_split_f32's)
+extern "C" int psld_gemm_tn_split_tail_supported(int m, int n, int k) {
+    return m >= 128 && n >= 128 && k > 0 && m % 32 == 0 && n % 32 == 0 && k % 32 == 0 && !psld_gemm_tn_split_supported(m, n, k);
+}
+
+extern "C" int psld_gemm_tn_split_tail_f32(int m, int n, int k, const float* a, int lda, const float* b, int ldb,
+                                           float* slabs, int ldc, int nsplit, hipStream_t stream) {
+    PSLD_CHECK_ARG(a && b && slabs && nsplit >= 1, "psld_gemm_tn_split_tail_f32: bad args");
+    PSLD_CHECK_ARG(psld_gemm_tn_split_tail_supported(m, n, k), "psld_gemm_tn_split_tail_f32: unsupported shape m=%d n=%d k=%d", m, n, k);
+    PSLD_CHECK_ARG(aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0 && lda >= m && ldb >= n && ldc >= n,
+                   "psld_gemm_tn_split_tail_f32: unaligned operand or short row stride");
+    PWgradArgs p{};
+    p.a = a; p.lda = lda; p.b = b; p.ldb = ldb; p.n1 = n;
+    p.m = m; p.n = n;
+    p.tiles_i = cdiv(m, 128); p.tiles_j = cdiv(n, 128);
+    p.ktiles = k / 32;
+    p.ktiles_per_split = cdiv(p.ktiles, nsplit);
+    PSLD_CHECK_ARG(cdiv(p.ktiles, p.ktiles_per_split) == nsplit, "psld_gemm_tn_split_tail_f32: nsplit %d leaves empty slabs", nsplit);
+    p.slabs = slabs; p.ldc = ldc;
+    p.slab_stride = (long long)m * ldc;
+    constexpr size_t LDS = (size_t)2 * 3 * 32 * 288;
+    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
+    if (!configured) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwgrad_kernel<true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+        if (e != hipSuccess) {
+            psld_set_error("psld_gemm_tn_split_tail_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+            return PSLD_ERR_LAUNCH;
+        }
+        configured = true;
+    }
+    hipLaunchKernelGGL(pwgrad_kernel<true>, dim3((unsigned)(p.tiles_i * p.tiles_j * nsplit)), dim3(256), LDS, stream, p);
+    PSLD_CHECK_LAUNCH("psld_gemm_tn_split_tail_f32");
     return PSLD_OK;
 }
 
@@ -2162,4 +2283,68 @@ extern "C" int psld_gemm_split_x3_f32(const float* a1, int k1, const float* a2, 
     plan_split(a, e, y, ldy, nullptr, 0);
     PSLD_CHECK_ARG(a.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
     return launch_pw8<0, 2>(a, stream, "psld_gemm_split_x3_f32");
+}
+
+// ---- pointwise, channel widths in steps of 32 ("tail": the shapes psld_gemm_split_supported refuses for n % 128 or k % 64) ----
+// The four-wave kernel on 128 x 128 tiles with the last column tile cut short (dconv_kernel<8, 2, true, 128, TAIL = true>); one
+// source, three limbs, no GroupNorm partial sums.
+extern "C" int psld_gemm_tail_supported(int k, int m, int n) {
+    return k >= 128 && n >= 128 && k % 32 == 0 && n % 32 == 0 && m > 0 && !psld_gemm_split_supported(k, 0, m, n);
+}
+
+extern "C" long long psld_gemm_frag_bytes_tail(int n, int k) {
+    return (long long)((n + 127) & ~127) * ((k + 63) & ~63) * 6;
+}
+
+extern "C" int psld_pack_gemm_frag_tail(const float* b, void* bfrag, int n, int k, long long stride_n, long long stride_k,
+                                        hipStream_t stream) {
+    PSLD_CHECK_ARG(b && bfrag && aligned16(bfrag), "psld_pack_gemm_frag_tail: null or unaligned pointer");
+    PSLD_CHECK_ARG(n > 0 && k > 0 && n % 32 == 0 && k % 32 == 0 && n < (1 << 20) && k < (1 << 20),
+                   "psld_pack_gemm_frag_tail: needs n %%32 and k %%32 (got %d, %d)", n, k);
+    const long long items = (long long)tail_rows(n, 0, n) * tail_chunks(k, 0, k / 32) * 4;
+    const int blocks = (int)((items + 255) / 256 < 8192 ? (items + 255) / 256 : 8192);
+    hipLaunchKernelGGL(pack_tail_kernel, dim3(blocks), dim3(256), 0, stream, b, reinterpret_cast<u32x4*>(bfrag), n, k, stride_n,
+                       stride_k, items);
+    PSLD_CHECK_LAUNCH("psld_pack_gemm_frag_tail");
+    return PSLD_OK;
+}
+
+extern "C" long long psld_pack_frag_tail_items(int n, int n0, int n_total, int k, int chunk0, int chunks_total) {
+    if (n_total == 0) n_total = n;
+    if (chunks_total == 0) chunks_total = k / 32;
+    return (long long)tail_rows(n, n0, n_total) * tail_chunks(k, chunk0, chunks_total) * 4;
+}
+
+extern "C" int psld_pack_frag_batch_tail(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
+    PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_frag_batch_tail: bad args");
+    const long long want = (total_items + 255) / 256;
+    hipLaunchKernelGGL(pack_tail_batch_kernel, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream, table_dev,
+                       entries, total_items);
+    PSLD_CHECK_LAUNCH("psld_pack_frag_batch_tail");
+    return PSLD_OK;
+}
+
+extern "C" int psld_gemm_split_tail_f32(const float* a, int k, int m, const void* bfrag, int n, float* y, int ldy,
+                                        const psld_epilogue_t* epi, void* workspace, long long ws_bytes, hipStream_t stream) {
+    PSLD_CHECK_ARG(a && bfrag && y, "psld_gemm_split_tail_f32: null pointer");
+    PSLD_CHECK_ARG(psld_gemm_tail_supported(k, m, n), "psld_gemm_split_tail_f32: unsupported shape k=%d m=%d n=%d", k, m, n);
+    PSLD_CHECK_ARG(aligned16(a) && aligned16(bfrag), "psld_gemm_split_tail_f32: unaligned pointer");
+    PSLD_CHECK_ARG(ldy >= n, "psld_gemm_split_tail_f32: ldy %d < n %d", ldy, n);
+    const PsldEpilogue e = make_epilogue(epi);
+    PSLD_CHECK_ARG(!e.gn_part, "psld_gemm_split_tail_f32: no GroupNorm partial sums on cut tiles (take the statistics in a pass of their own)");
+    DConvArgs d{};
+    d.x1 = a; d.x2 = nullptr; d.C1 = k; d.C2 = 0;
+    d.B = 1; d.H = 1; d.W = 1;
+    d.wfrag = reinterpret_cast<const u32x4*>(bfrag);
+    d.N = n; d.M = m;
+    d.chunks = cdiv(k, 64);             // stages of two 32-channel chunks; the odd chunk behind k is zeros on both sides
+    d.nseg = 1; d.rps = 1; d.pitch = d.W + 2;
+    d.zero = psld_detail_zero_page("psld_gemm_split_tail_f32");
+    if (!d.zero) return PSLD_ERR_LAUNCH;
+    const int ns = plan_split(d, e, y, ldy, aligned16(workspace) ? workspace : nullptr, ws_bytes);
+    PSLD_CHECK_ARG(d.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
+    const int st = launch_dconv<8, 2, true, 128, true>(d, ns, stream, "psld_gemm_split_tail_f32");
+    if (st != PSLD_OK) return st;
+    if (ns >= 2) return psld_detail_conv_reduce_epilogue(d.C, ns, m, n, y, ldy, e, stream);
+    return PSLD_OK;
 }

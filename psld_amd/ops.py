@@ -502,6 +502,63 @@ def gemm_tn_split(M: int, N: int, K: int, A: Tensor, lda: int, B: Tensor, ldb: i
                                        ldc, nsplit, _stream()), "psld_gemm_tn_split_f32")
 
 
+# ---- pointwise limb GEMMs for channel widths in steps of 32 ("tail" shapes: what gemm_split / gemm_tn_split refuse) ------
+@functools.lru_cache(maxsize=None)
+def gemm_tail_supported(k: int, m: int, n: int) -> bool:
+    return bool(lib().psld_gemm_tail_supported(k, m, n))
+
+
+def gemm_frag_bytes_tail(n: int, k: int) -> int:
+    return int(lib().psld_gemm_frag_bytes_tail(n, k))
+
+
+def gemm_frag_tail(b: Tensor, n: int, k: int, stride_n: int, stride_k: int, out: Optional[Tensor] = None) -> Tensor:
+    """gemm_frag for n, k multiples of 32: the set is padded to whole 128-row tiles and 64-wide K stages with zero limbs."""
+    if out is None:
+        out = torch.empty(gemm_frag_bytes_tail(n, k), dtype=torch.uint8, device=b.device)
+    check(lib().psld_pack_gemm_frag_tail(b.data_ptr(), out.data_ptr(), n, k, stride_n, stride_k, _stream()),
+          "psld_pack_gemm_frag_tail")
+    return out
+
+
+def gemm_frag_tail_entry(b: Tensor, out: Tensor, n: int, k: int, stride_n: int, stride_k: int, n0: int = 0, n_total: int = 0,
+                         chunk0: int = 0, chunks_total: int = 0):
+    """(table row without the running index, work items) of ``pack_frag_batch_tail``: the [n][k] tensor as rows n0 .. n0 + n
+    and 32-wide K chunks chunk0 .. chunk0 + k/32 of a set of n_total rows and chunks_total chunks (0: the whole dimension)."""
+    return ([b.data_ptr(), out.data_ptr(), n | (n0 << 20) | (n_total << 40), k | (chunk0 << 20) | (chunks_total << 40), 1,
+             stride_n, stride_k], int(lib().psld_pack_frag_tail_items(n, n0, n_total, k, chunk0, chunks_total)))
+
+
+def pack_frag_batch_tail(table: Tensor, entries: int, total_items: int):
+    """table rows: gemm_frag_tail_entry(...)[0] + [first work item]."""
+    check(lib().psld_pack_frag_batch_tail(table.data_ptr(), entries, total_items, _stream()), "psld_pack_frag_batch_tail")
+
+
+def gemm_split_tail(a: Tensor, m: int, bfrag: Tensor, n: int, y: Tensor, epi: Optional[Epilogue] = None,
+                    ldy: Optional[int] = None, allow_split: bool = True):
+    """y[m][n] = epilogue(a @ B^T) for the shapes gemm_tail_supported takes (fragments: gemm_frag_tail); gemm_split's
+    workspace policy (``allow_split`` False: never a K split)."""
+    k = a.shape[-1]
+    ws, wsb = None, 0
+    if allow_split and m <= 32768:
+        wsb = 8 * m * n * 4
+        ws = workspace(wsb, a.device).data_ptr()
+    check(lib().psld_gemm_split_tail_f32(a.data_ptr(), k, m, bfrag.data_ptr(), n, y.data_ptr(),
+                                         ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
+                                         ws, wsb, _stream()), "psld_gemm_split_tail_f32")
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_tn_split_tail_supported(m: int, n: int, k: int) -> bool:
+    return bool(lib().psld_gemm_tn_split_tail_supported(m, n, k))
+
+
+def gemm_tn_split_tail(M: int, N: int, K: int, A: Tensor, lda: int, B: Tensor, ldb: int, slabs: Tensor, ldc: int, nsplit: int):
+    """gemm_tn_split (one B source) for M, N multiples of 32 from 128 up that are not both multiples of 128."""
+    check(lib().psld_gemm_tn_split_tail_f32(M, N, K, A.data_ptr(), lda, B.data_ptr(), ldb, slabs.data_ptr(), ldc, nsplit,
+                                            _stream()), "psld_gemm_tn_split_tail_f32")
+
+
 @functools.lru_cache(maxsize=None)
 def bgemm_split_supported(ta: int, tb: int, m: int, n: int, k: int) -> bool:
     return bool(lib().psld_bgemm_split_supported(ta, tb, m, n, k))

@@ -183,10 +183,11 @@ class _Exec(_ExecBase):
         out = torch.empty((b, ho, wo, cout), device=x.v.device, dtype=torch.float32)
         if mod.has_shortcut:
             c2 = mod.Conv_2
-            if self.split and ops.gemm_split_supported(c1, cin - c1, b * ho * wo, cout):
+            sc_route = R.pointwise_route(self.split, c1, cin - c1, b * ho * wo, cout)
+            if sc_route != R.TILE:
                 self.gemm_fwd(xr, xb.v if xb is not None else None, b * ho * wo, cout, out, ops.epilogue(bias=c2.bias),
                               lambda: net._pfrag(c2.weight, "fwd", cout, cin, cin, 1),
-                              lambda: net._pfrag(c2.weight, "fwd_x3", cout, cin, cin, 1))
+                              lambda: net._pfrag(c2.weight, "fwd_x3", cout, cin, cin, 1), route=sc_route)
             else:
                 ops.conv2d_nhwc(xr, xb.v if xb is not None else None, c2.weight, cout, 1, 1, 1, 0, 1, ho, wo, out,
                                 ops.epilogue(bias=c2.bias))
@@ -294,9 +295,10 @@ class _Exec(_ExecBase):
                 c2 = mod.Conv_2
                 m = b * ho * wo
                 def shortcut_dgrad(dst, epi):
-                    if self.split and ops.gemm_split_supported(cout, 0, m, cin):
+                    route = R.pointwise_route(self.split, cout, 0, m, cin)
+                    if route != R.TILE:
                         fr = net._pfrag(c2.weight, "dgrad", cin, cout, 1, cin)
-                        ops.gemm_split(dout, None, m, fr, cin, dst, epi)
+                        self.gemm_limb(route, dout, m, fr, cin, dst, epi)
                     else:
                         ops.gemm_raw(0, 0, m, cin, cout, dout, cout, 0, c2.weight, cin, 0, dst, cin, 0, epi=epi)
 
@@ -369,12 +371,16 @@ class _Exec(_ExecBase):
         n0, n1, n2, n3 = mod.NIN_0, mod.NIN_1, mod.NIN_2, mod.NIN_3
         scale = float(int(c) ** (-0.5))
         # limb kernels: q|k|v come from ONE GEMM against the concatenated projections (N = 3c) into one buffer
-        fused = self.split and ops.gemm_split_supported(c, 0, m, c)
+        # (c -> c, c -> 3c and 3c -> c take the same route: 3c is a multiple of 128 exactly when c is)
+        route = R.pointwise_route(self.split, c, 0, m, c)
+        fused = route != R.TILE
         net = self.net
         if fused:
+            assert R.pointwise_route(self.split, c, 0, m, 3 * c) == route == R.pointwise_route(self.split, 3 * c, 0, m, c)
             f_qkv, f_qkv_d, b_qkv = net._qkv_frags(mod)
             qkv = torch.empty((b, hw, 3 * c), device=dev, dtype=torch.float32)
-            self.gemm_fwd(hn, None, m, 3 * c, qkv, ops.epilogue(bias=b_qkv), lambda: f_qkv, lambda: net._qkv_frags_x3(mod))
+            self.gemm_fwd(hn, None, m, 3 * c, qkv, ops.epilogue(bias=b_qkv), lambda: f_qkv, lambda: net._qkv_frags_x3(mod),
+                          route=route)
             q, k, v = qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:]
             ld = 3 * c
         else:
@@ -397,11 +403,11 @@ class _Exec(_ExecBase):
             ops.softmax_rows(p, p, b * hw, hw)
             self.bmm(0, 0, hw, c, hw, p, hw, hw * hw, v, ld, hw * ld, ho, c, hw * c, b)
         out = torch.empty_like(x.v)
-        outp = self.part_for(b, hw, c, dev, fused)
+        outp = self.part_for(b, hw, c, dev, route == R.LIMB)       # (the tail launch leaves no GroupNorm partial sums)
         epi_out = ops.epilogue(bias=n3.b, residual=x.v, ld_residual=c, out_scale=s, gn_part=outp, gn_hw=hw)
         if fused:
             self.gemm_fwd(ho, None, m, c, out, epi_out, lambda: net._pfrag(n3.W, "fwd", c, c, 1, c),
-                          lambda: net._pfrag(n3.W, "fwd_x3", c, c, 1, c))
+                          lambda: net._pfrag(n3.W, "fwd_x3", c, c, 1, c), route=route)
         else:
             ops.gemm_raw(0, 0, m, c, c, ho, c, 0, n3.W, c, 0, out, c, 0, epi=epi_out)
         on = _Node(out, outp, want_gsum=True)       # NIN_3.b = s * column sums of its gradient
@@ -410,10 +416,11 @@ class _Exec(_ExecBase):
 
         def nin_wgrad(a_in: Tensor, dy: Tensor, nin: NIN, alpha: float, ldd: int, bias: bool = True):
             # dW[in,out] = a_in^T dy  (K = B*HW -> split-K slabs); dy may be a column slice (row stride ldd)
-            if self.split and ops.gemm_tn_split_supported(c, c, m):
+            wroute = R.pointwise_wgrad_route(self.split, c, c, 0, m)
+            if wroute != R.TILE:
                 nsplit = R._tn_split(c, c, m)
                 slabs = self.slabs_for(4 * c * c * nsplit, dev)
-                ops.gemm_tn_split(c, c, m, a_in, c, dy, ldd, slabs, c, nsplit)
+                (ops.gemm_tn_split_tail if wroute == R.LIMB_TAIL else ops.gemm_tn_split)(c, c, m, a_in, c, dy, ldd, slabs, c, nsplit)
             else:
                 nsplit = _pick_nsplit(((c + 127) // 128) ** 2, m)
                 slabs = self.slabs_for(4 * c * c * nsplit, dev)
@@ -430,7 +437,7 @@ class _Exec(_ExecBase):
             dho = torch.empty_like(ho)
             if fused:
                 f_od = net._pfrag(n3.W, "dgrad", c, c, c, 1)
-                ops.gemm_split(dout, None, m, f_od, c, dho, ops.epilogue(alpha=s))
+                self.gemm_limb(route, dout, m, f_od, c, dho, ops.epilogue(alpha=s))
             else:
                 ops.gemm_raw(0, 1, m, c, c, dout, c, 0, n3.W, c, 0, dho, c, 0, epi=ops.epilogue(alpha=s))
             # dP = dho v^T ; dv = P^T dho
@@ -453,13 +460,14 @@ class _Exec(_ExecBase):
                 self.on_side(lambda: ops.bias_grad_seg(dqkv, 3 * c, b, hw, (self.g(n0.b), self.g(n1.b), self.g(n2.b)), c), dqkv)
             # ... and their weight gradients from ONE GEMM hn^T [dq | dk | dv] (N = 3c: hn is staged and split once instead
             # of three times); the batched slab reduction cuts the [c][3c] result into the three parameters
-            one_gemm = fused and self.defer and self.split and ops.gemm_tn_split_supported(c, 3 * c, m) and \
-                ops.slab_units(c * c, 2, c, 3 * c) > 0
+            qkv_wroute = R.pointwise_wgrad_route(self.split, c, 3 * c, 0, m)
+            one_gemm = fused and self.defer and qkv_wroute != R.TILE and ops.slab_units(c * c, 2, c, 3 * c) > 0
 
             def qkv_wgrad():
                 nsplit = R._tn_split(c, 3 * c, m)
                 slabs = self.slabs_for(4 * 3 * c * c * nsplit, dev).view(torch.float32)
-                ops.gemm_tn_split(c, 3 * c, m, hn, c, dqkv, 3 * c, slabs, 3 * c, nsplit)
+                (ops.gemm_tn_split_tail if qkv_wroute == R.LIMB_TAIL else ops.gemm_tn_split)(
+                    c, 3 * c, m, hn, c, dqkv, 3 * c, slabs, 3 * c, nsplit)
                 for i, nin in enumerate((n0, n1, n2)):
                     self.reduce_slabs(slabs[i * c:], nsplit, c * c, self.g(nin.W), layout=2, taps=c, cin=3 * c, more=i < 2)
 
@@ -472,7 +480,7 @@ class _Exec(_ExecBase):
                 for nin, d in ((n0, dq), (n1, dk), (n2, dv)):
                     self.on_side(lambda nin=nin, d=d: nin_wgrad(hn, d, nin, 1.0, ld, bias=not seg), hn, d)
             if fused:
-                ops.gemm_split(dqkv, None, m, f_qkv_d, c, dhn)
+                self.gemm_limb(route, dqkv, m, f_qkv_d, c, dhn)
             else:
                 first = True
                 for nin, d in ((n0, dq), (n1, dk), (n2, dv)):
@@ -513,17 +521,20 @@ class _Exec(_ExecBase):
         net = self.net
         m = b * oh * ow
         # many-channel levels on the limb kernels: explicit im2col (K order = the packed OHWI weights') + pointwise GEMM
-        limb = self.split and not small and cin % 4 == 0 and ops.gemm_split_supported(9 * cin, 0, m, cout) and \
-            ops.gemm_split_supported(cout, 0, m, 9 * cin)
+        r_fwd, r_bwd = R.pointwise_route(self.split, 9 * cin, 0, m, cout), R.pointwise_route(self.split, cout, 0, m, 9 * cin)
+        limb = not small and cin % 4 == 0 and r_fwd != R.TILE and r_bwd != R.TILE
+        pack = ops.gemm_frag_tail if r_fwd == R.LIMB_TAIL else ops.gemm_frag
+        pack_d = ops.gemm_frag_tail if r_bwd == R.LIMB_TAIL else ops.gemm_frag
         if small:
             cols = self.small_in_conv(xf, conv, 2, 0, oh, ow, out, epi)
         elif limb:
             patches = ops.im2col3x3(xf, 2, 0, oh, ow)
             self.gemm_fwd(patches, None, m, cout, out, epi,
                           lambda: net._wcache.get(conv.weight, "s2fwd", _built_entry,
-                                                  lambda prev: ops.gemm_frag(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev)),
+                                                  lambda prev: pack(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev)),
                           lambda: net._wcache.get(conv.weight, "s2fwd_x3", _built_entry,
-                                                  lambda prev: ops.gemm_frag_x3(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev)))
+                                                  lambda prev: ops.gemm_frag_x3(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev)),
+                          route=r_fwd)
             del patches
         else:
             ops.conv2d_nhwc(xf, None, self.net._packed(conv), cout, 3, 3, 2, 0, 1, oh, ow, out, epi)
@@ -551,9 +562,9 @@ class _Exec(_ExecBase):
                 if limb:
                     frd = net._wcache.get(
                         conv.weight, "s2dgrad", _built_entry,
-                        lambda prev: ops.gemm_frag(net._packed(conv), 9 * cin, cout, 1, 9 * cin, prev))
+                        lambda prev: pack_d(net._packed(conv), 9 * cin, cout, 1, 9 * cin, prev))
                     dpatches = torch.empty((m, 9 * cin), device=dout.device, dtype=torch.float32)
-                    ops.gemm_split(dout, None, m, frd, 9 * cin, dpatches, ops.epilogue(alpha=s))
+                    self.gemm_limb(r_bwd, dout, m, frd, 9 * cin, dpatches, ops.epilogue(alpha=s))
                     ops.col2im3x3(dpatches, xf.shape, 2, 0, oh, ow, out=dxf)
                     del dpatches
                 else:

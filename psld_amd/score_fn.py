@@ -35,7 +35,7 @@ from .score_modules import (NIN, AttnBlockpp, Downsample, GaussianFourierProject
                             _Affine, _conv, _groupnorm, _linear, default_init)
 from .score_routes import _pick_nsplit  # noqa: F401  (tests / tools import it from here)
 from .score_tape import _SLAB_FLUSH_BYTES, _CatNode, _Node  # noqa: F401
-from .score_weights import (_frag_entry, _packed_entry, _pfrag_entry, _qkv_entry, _temb_entry, _wfrag_x3_entry)
+from .score_weights import (_frag_entry, _packed_entry, _pfrag_entry, _qkv_entry, _temb_entry, _wfrag_x3_entry, pfrag_tail)
 from .weight_cache import Entry, WeightCache
 
 Tensor = torch.Tensor
@@ -230,7 +230,8 @@ class NCSNpp(nn.Module):
         self._flat_grad: Optional[Tensor] = None
         self._offsets = None
         # derived weights; a batched refresh needs two entries of a limb / Winograd family, one of a gathered copy
-        self._wcache = WeightCache({"limb": (ops.pack_frag_batch, 2), "wino": (ops.pack_wino_batch, 2),
+        self._wcache = WeightCache({"limb": (ops.pack_frag_batch, 2), "limb_tail": (ops.pack_frag_batch_tail, 2),
+                                    "wino": (ops.pack_wino_batch, 2),
                                     "limb_x3": (ops.pack_frag_batch_x3, 2), "wino_x3": (ops.pack_wino_batch_x3, 2),
                                     "qkv_bias": (ops.copy_batch, 1), "temb": (ops.copy_batch, 1)})
         self._anchor = None
@@ -386,12 +387,15 @@ class NCSNpp(nn.Module):
         return self._wcache.get(conv.weight, "wfrag_x3", _wfrag_x3_entry)
 
     def _pfrag(self, owner: nn.Parameter, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor] = None,
-               chunk0: int = 0, chunks_total: int = 0) -> Tensor:
+               chunk0: int = 0, chunks_total: int = 0, n0: int = 0, n_total: int = 0) -> Tensor:
         """Limb fragments (ops.gemm_frag) of the [n][k] view of ONE parameter (element (i, j) at i*sn + j*sk), refreshed
         together with the 3x3 fragments by the batched launch.  ``into``: the buffer to fill (several parameters that
         share one fragment set: q | k | v) - then ``chunk0`` / ``chunks_total`` place this parameter's K range inside the
-        set's K dimension (psld_pack_frag_batch).  A ``tag`` ending in ``_x3``: two-limb fragments (ops.gemm_frag_x3)."""
-        return self._wcache.get(owner, tag, _pfrag_entry, tag, n, k, sn, sk, into, chunk0, chunks_total)
+        set's K dimension (psld_pack_frag_batch).  A ``tag`` ending in ``_x3``: two-limb fragments (ops.gemm_frag_x3).
+        A set that is no whole number of 128 x 64 tiles (score_weights.pfrag_tail: channel widths in steps of 32) is packed
+        as padded three-limb tail fragments (ops.gemm_frag_tail); ``n0`` / ``n_total`` then place the parameter's rows
+        inside a shared set's N dimension."""
+        return self._wcache.get(owner, tag, _pfrag_entry, tag, n, k, sn, sk, into, chunk0, chunks_total, n0, n_total)
 
     def _qkv_frags(self, mod):
         """Fragments of an attention block's q | k | v projections as ONE GEMM operand each way - forward B[n][k] =
@@ -405,6 +409,11 @@ class NCSNpp(nn.Module):
         pf, pd = e.out[:2]
         fb = pf.numel() // 3
         for i, nin in enumerate((n0, mod.NIN_1, mod.NIN_2)):
+            if pfrag_tail(3 * c, c):
+                # c % 128 != 0: a projection's rows start inside a 128-row tile of the padded set
+                self._pfrag(nin.W, "qkv_f", c, c, 1, c, into=pf, n0=i * c, n_total=3 * c)
+                self._pfrag(nin.W, "qkv_d", c, c, c, 1, into=pd, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
+                continue
             # forward: rows n of the set are output channels -> each projection is a contiguous third of the set
             self._pfrag(nin.W, "qkv_f", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
             # data gradient: the three projections are concatenated along K

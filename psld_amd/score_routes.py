@@ -21,6 +21,7 @@ from . import ops
 WINO = "wino"           # Winograd F(2x2, 3x3): conv_wino.hip forward / data gradient, wgrad_wino.hip weight gradient
 LIMB = "limb"           # direct bf16 limb kernels (conv_split.hip); the only route that reads ops.LimbPlanes
 TILE = "tile"           # fp32 tile engine (ops.conv2d_nhwc / conv2d_wgrad_nhwc)
+LIMB_TAIL = "limb_tail"  # pointwise only: the limb kernels with the last channel tile cut short (widths in steps of 32)
 WINO_GN = "wino_gn"     # forward only: SiLU(GroupNorm(.)) applied inside the Winograd kernel's input staging
 NONE = "none"           # weight gradient only: a two-source shape no kernel takes
 
@@ -47,9 +48,10 @@ def _pick_nsplit(tiles: int, k: int, min_k: int = 256, resident: int = _RESIDENT
 
 
 def _tn_split(m: int, n: int, k: int) -> int:
-    """K ranges of a pointwise limb weight gradient (128x128 tiles, two workgroups resident per CU)."""
+    """K ranges of a pointwise limb weight gradient (128x128 tiles, the last ones cut short on the tail route; two
+    workgroups resident per CU)."""
     ktiles = k // 32
-    nsplit = _pick_nsplit((m // 128) * (n // 128), k, min_k=128, resident=512)
+    nsplit = _pick_nsplit(-(-m // 128) * -(-n // 128), k, min_k=128, resident=512)
     per = -(-ktiles // nsplit)
     return -(-ktiles // per)                       # every slab non-empty
 
@@ -99,6 +101,27 @@ def wgrad_route(split: bool, cout: int, c1: int, c2: int, b: int, h: int, w: int
             (c2 == 0 or ops.conv3x3_wgrad_split_supported(cout, c2, b, h, w)):
         return LIMB
     return NONE if c2 else TILE
+
+
+def pointwise_route(split: bool, k1: int, k2: int, m: int, n: int) -> str:
+    """Route of a pointwise contraction y[m][n] = [a1 | a2][m][k1 + k2] @ B^T - a 1x1 convolution, a NIN projection, the
+    stride-2 pyramid GEMM, forward or data gradient (then with the channel roles swapped).  The ONE place that asks
+    ops.gemm_split_supported / ops.gemm_tail_supported for the executor's GEMMs."""
+    if split and ops.gemm_split_supported(k1, k2, m, n):
+        return LIMB
+    if split and k2 == 0 and ops.gemm_tail_supported(k1, m, n):
+        return LIMB_TAIL
+    return TILE
+
+
+def pointwise_wgrad_route(split: bool, m: int, n: int, n2: int, k: int) -> str:
+    """Route of a pointwise weight gradient dW[m][n + n2] = A[k][m]^T [B | B2][k][n + n2] (k = pixels).  The ONE place that
+    asks ops.gemm_tn_split_supported / ops.gemm_tn_split_tail_supported for the executor's 1x1 / NIN weight gradients."""
+    if split and ops.gemm_tn_split_supported(m, n, k) and n2 % 128 == 0:
+        return LIMB
+    if split and n2 == 0 and ops.gemm_tn_split_tail_supported(m, n, k):
+        return LIMB_TAIL
+    return TILE
 
 
 def head_fewout(cin: int, cout: int) -> bool:

@@ -333,11 +333,14 @@ class _ExecBase:
             ops.conv3x3_wgrad_split(dy, cout, x, slabs, cin, 0, nsplit, x2)
             self.reduce_slabs(slabs, nsplit, n, self.g(conv.weight), layout=1, cout=cout, taps=taps, cin=cin, alpha=alpha)
             return
-        if self.split and k == 1 and stride == 1 and pad == 0 and ops.gemm_tn_split_supported(cout, c1, b * oh * ow) and \
-                c2 % 128 == 0:
+        pw = R.pointwise_wgrad_route(self.split, cout, c1, c2, b * oh * ow) if (k, stride, pad) == (1, 1, 0) else R.TILE
+        if pw != R.TILE:
             nsplit = R._tn_split(cout, cin, b * oh * ow)
             slabs = self.slabs_for(4 * n * nsplit, dy.device)
-            ops.gemm_tn_split(cout, c1, b * oh * ow, dy, cout, x, c1, slabs, cin, nsplit, x2, c2, c2)
+            if pw == R.LIMB_TAIL:
+                ops.gemm_tn_split_tail(cout, c1, b * oh * ow, dy, cout, x, c1, slabs, cin, nsplit)
+            else:
+                ops.gemm_tn_split(cout, c1, b * oh * ow, dy, cout, x, c1, slabs, cin, nsplit, x2, c2, c2)
             self.reduce_slabs(slabs, nsplit, n, self.g(conv.weight), alpha=alpha)
             return
         assert x2 is None, "unsupported two-source weight gradient"
@@ -422,10 +425,20 @@ class _ExecBase:
         else:
             ops.conv3x3_wino_gn(x, st, x2, st2, True, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)
 
-    def gemm_fwd(self, a1: Tensor, a2: Optional[Tensor], m: int, n: int, y: Tensor, epi, frag, frag_x3):
-        """Forward pointwise GEMM on the limb kernels; ``frag()`` / ``frag_x3()``: its three- / two-limb fragments."""
+    def gemm_limb(self, route: str, a: Tensor, m: int, frag: Tensor, n: int, y: Tensor, epi=None):
+        """One-source pointwise GEMM on ``route`` (score_routes.pointwise_route: LIMB or LIMB_TAIL), three limbs."""
+        if route == R.LIMB_TAIL:
+            ops.gemm_split_tail(a, m, frag, n, y, epi)
+        else:
+            ops.gemm_split(a, None, m, frag, n, y, epi)
+
+    def gemm_fwd(self, a1: Tensor, a2: Optional[Tensor], m: int, n: int, y: Tensor, epi, frag, frag_x3, route: str = R.LIMB):
+        """Forward pointwise GEMM on the limb kernels; ``frag()`` / ``frag_x3()``: its three- / two-limb fragments.
+        ``route`` LIMB_TAIL: the three-limb tail launch in every math mode (there is no two-limb tail form)."""
         k1, k2 = a1.shape[-1], a2.shape[-1] if a2 is not None else 0
-        if self.x3 and ops.gemm_split_x3_wanted(k1, k2, m, n):
+        if route == R.LIMB_TAIL:
+            ops.gemm_split_tail(a1, m, frag(), n, y, epi)
+        elif self.x3 and ops.gemm_split_x3_wanted(k1, k2, m, n):
             ops.gemm_split_x3(a1, a2, m, frag_x3(), n, y, epi)
         else:
             ops.gemm_split(a1, a2, m, frag(), n, y, epi)

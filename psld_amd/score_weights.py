@@ -36,8 +36,31 @@ def _wfrag_x3_entry(w: Tensor) -> Entry:
                  rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, False, out), w.shape[0] * w.shape[1] // 8)], graph=True)
 
 
+def pfrag_tail(n: int, k: int, n_total: int = 0, chunks_total: int = 0) -> bool:
+    """The fragment set of an [n_total or n][32 * chunks_total or k] matrix is no whole number of 128 x 64 tiles: it is
+    packed by the tail packers (ops.gemm_frag_tail) and read by ops.gemm_split_tail."""
+    return (n_total or n) % 128 != 0 or (32 * chunks_total or k) % 64 != 0
+
+
+def _pfrag_tail_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor], chunk0: int,
+                      chunks_total: int, n0: int, n_total: int) -> Entry:
+    """Three-limb fragments of a tail set ("limb_tail" family); ``into`` with the row / K placement of a shared set."""
+    def rows(out):
+        return [ops.gemm_frag_tail_entry(p, out, n, k, sn, sk, n0, n_total, chunk0, chunks_total)]
+
+    def build(prev):
+        if into is None:
+            return ops.gemm_frag_tail(p.detach(), n, k, sn, sk, prev)
+        (row, items), = rows(into)
+        ops.pack_frag_batch_tail(torch.tensor(row + [0], dtype=torch.int64, device=p.device), 1, items)
+        return into
+    return Entry(p, build=build, family="limb_tail", rows=rows, graph=tag in ("fwd", "qkv_f"))
+
+
 def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor], chunk0: int,
-                 chunks_total: int) -> Entry:
+                 chunks_total: int, n0: int = 0, n_total: int = 0) -> Entry:
+    if pfrag_tail(n, k, n_total, chunks_total):
+        return _pfrag_tail_entry(p, tag, n, k, sn, sk, into, chunk0, chunks_total, n0, n_total)
     x3 = tag.endswith("_x3")        # two-limb fragments (math mode 'bf16x3'): their own packers and batch family
     pack, pack_batch = (ops.gemm_frag_x3, ops.pack_frag_batch_x3) if x3 else (ops.gemm_frag, ops.pack_frag_batch)
 
@@ -64,9 +87,12 @@ def _qkv_entry(b0: Tensor, mod: "AttnBlockpp") -> Entry:
     """out: the forward and data-gradient q | k | v fragment sets (filled by the "qkv_f" / "qkv_d" entries) and the
     gathered [b_q | b_k | b_v] (filled by the "qkv_bias" family's batched copy)."""
     c = b0.numel()
-    fb = ops.gemm_frag_bytes(c, c)
-    out = (torch.empty(3 * fb, dtype=torch.uint8, device=b0.device),
-           torch.empty(3 * fb, dtype=torch.uint8, device=b0.device),
+    if pfrag_tail(3 * c, c):        # c % 128 != 0: padded sets (N = 3c forward, K = 3c data gradient)
+        fbf, fbd = ops.gemm_frag_bytes_tail(3 * c, c), ops.gemm_frag_bytes_tail(c, 3 * c)
+    else:
+        fbf = fbd = 3 * ops.gemm_frag_bytes(c, c)
+    out = (torch.empty(fbf, dtype=torch.uint8, device=b0.device),
+           torch.empty(fbd, dtype=torch.uint8, device=b0.device),
            torch.empty(3 * c, dtype=torch.float32, device=b0.device))
 
     def rows(out):

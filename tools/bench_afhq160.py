@@ -4,6 +4,8 @@
     python tools/bench_afhq160.py ROOT train 8       # forward + loss + backward
     python tools/bench_afhq160.py ROOT kernels 16    # one 3x3 forward launch per level, as the executor sends it, and the
                                                      # same launch with cout zero-padded to a multiple of 128
+    python tools/bench_afhq160.py ROOT pointwise 16  # one forward launch per distinct pointwise (m, k, n) of the network: the
+                                                     # limb route (tail launch) against the fp32 tile engine's GEMM
 
 ROOT may be another checkout of the project (built in place) so that two trees are timed on one box; the configuration is
 built from ``afhqv2_128`` with the inpainting script's network keys, which older trees without ``afhqv2_128_inpaint`` have too.
@@ -82,6 +84,47 @@ if what in ("eval", "train"):
     ms = ev(s, e) / iters
     print(json.dumps({"tree": root, "what": what, "B": B, "ms": round(ms, 3), "images_per_s": round(B / ms * 1e3, 1),
                       "wall_s": round(time.time() - t0, 2)}), flush=True)
+elif what == "pointwise":
+    # (k, n, map side) of the network's pointwise contractions, forward and data gradient: 1x1 shortcuts, attention
+    # projections (q|k|v as one N = 3c GEMM), stride-2 pyramid GEMMs.  Per shape: the launch the executor sends on this tree
+    # (ops.gemm_split_tail, or ops.gemm_split where the old kernels take the shape) and the tile-engine GEMM the parent sent.
+    shapes = [(160, 320, 64), (320, 160, 64), (320, 480, 16), (480, 320, 16),
+              (960, 480, 8), (480, 960, 8), (960, 480, 16), (480, 960, 16), (800, 480, 16), (480, 800, 16), (800, 320, 32),
+              (320, 800, 32), (640, 320, 32), (320, 640, 32), (640, 320, 64), (320, 640, 64), (480, 320, 64), (320, 480, 64),
+              (480, 160, 128), (160, 480, 128), (320, 160, 128), (160, 320, 128),
+              (480, 1440, 16), (480, 480, 16), (1440, 480, 16), (480, 1440, 8), (480, 480, 8), (1440, 480, 8),
+              (1440, 320, 64), (320, 1440, 64), (2880, 320, 32), (320, 2880, 32), (2880, 480, 16), (480, 2880, 16),
+              (4320, 480, 8), (480, 4320, 8)]
+    tail = hasattr(ops, "gemm_split_tail")
+    out = []
+    for k, n, side in shapes:
+        m = B * side * side
+        a = torch.randn(m, k, device=DEV)
+        w = torch.randn(n, k, device=DEV) * 0.05
+        bias = torch.randn(n, device=DEV)
+        y = torch.empty(m, n, device=DEV)
+        epi = ops.epilogue(bias=bias)
+        runs = {"tile": lambda: ops.gemm_raw(0, 1, m, n, k, a, k, 0, w, k, 0, y, n, 0, 1, epi)}
+        if tail and ops.gemm_tail_supported(k, m, n):
+            frag = ops.gemm_frag_tail(w, n, k, k, 1)
+            runs["limb_tail"] = lambda: ops.gemm_split_tail(a, m, frag, n, y, epi)
+        elif ops.gemm_split_supported(k, 0, m, n):
+            frag = ops.gemm_frag(w, n, k, k, 1)
+            runs["limb"] = lambda: ops.gemm_split(a, None, m, frag, n, y, epi)
+        res = {}
+        for tag, run in runs.items():
+            for _ in range(3):
+                run()
+            st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            st.record()
+            for _ in range(20):
+                run()
+            en.record()
+            us = ev(st, en) / 20 * 1e3
+            res[tag] = {"us": round(us, 1), "tflops": round(2 * m * k * n / us / 1e6, 1)}
+        out.append({"m": m, "k": k, "n": n, **res})
+        del a, w, y
+    print(json.dumps({"tree": root, "what": "pointwise", "B": B, "shapes": out}), flush=True)
 else:
     # one 3x3 forward launch per level of the network at batch B, as the executor sends it (new tree: Winograd with tails;
     # parent: the tile engine), plus the zero-padded-to-128 alternative on the Winograd kernel where the tree takes it
