@@ -226,16 +226,7 @@ __global__ void __launch_bounds__(64 * QW, 2) attn_fwd_kernel(const AttnArgs a) 
 template <int HW, int C, int QW>
 int launch_attn(const AttnArgs& a, int batch, hipStream_t stream) {
     constexpr size_t PH1 = (size_t)3 * (HW + 16 * QW) * ROWB, PH3 = (size_t)3 * 32 * (C * 2 + 32), LDS = PH1 > PH3 ? PH1 : PH3;
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<HW, C, QW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("psld_attn_fwd_split_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&attn_fwd_kernel<HW, C, QW>>(LDS, "psld_attn_fwd_split_f32")) return st;
     hipLaunchKernelGGL((attn_fwd_kernel<HW, C, QW>), dim3((unsigned)(batch * (HW / (16 * QW)))), dim3(64 * QW), LDS, stream, a);
     PSLD_CHECK_LAUNCH("psld_attn_fwd_split_f32");
     return PSLD_OK;

@@ -45,6 +45,29 @@ struct PsldPerDeviceFlag {
     bool& here() { return done[psld_device_slot()]; }
 };
 
+// Raise one kernel instance's dynamic-LDS limit to `lds` bytes, once per device (each instance holds a flag of its own);
+// `name` is the entry point the message speaks for.  For launchers that configure ONE instance and fail on a bad status.
+template <auto Kernel>
+int psld_lds_once(size_t lds, const char* name) {
+    static PsldPerDeviceFlag configured_;
+    bool& configured = configured_.here();
+    if (!configured) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
+            return PSLD_ERR_LAUNCH;
+        }
+        configured = true;
+    }
+    return PSLD_OK;
+}
+
+// Blocks of a grid-stride launch: one thread per item, at most `cap` blocks
+static inline unsigned psld_grid_blocks(long long items, int threads, long long cap) {
+    const long long want = (items + threads - 1) / threads;
+    return (unsigned)(want < cap ? want : cap);
+}
+
 // wave64 reductions (CDNA wavefront = 64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -1,5 +1,16 @@
-// 3x3 stride-1 convolutions (forward, data-gradient, weight-gradient) on bf16 MFMA with fp32 operands carried
-// as three bf16 limbs ("bf16x6": PSLD_MATH_BF16X6 in include/psld_hip.h).
+// The limb kernels: convolutions and GEMMs on bf16 MFMA with fp32 operands carried as three bf16 limbs ("bf16x6":
+// PSLD_MATH_BF16X6 in include/psld_hip.h; two limbs: PSLD_MATH_BF16X3).
+//
+// Map of the file, in its order: the weight packers (pack_frag_* / pack_tail_*: limb fragments in MFMA operand order, one
+// tensor or a table of them per launch); the 3x3 stride-1 forward / data-gradient kernel and its epilogue (dconv_kernel,
+// whose PW instances are the four-wave pointwise GEMM); the same on activations already split into limb planes, with the
+// fp32 <-> limb-plane conversion (dconv_lp_kernel, f32_to_limb / limb_to_f32); the 3x3 weight gradient (dwgrad_kernel,
+// dwgrad_ws_kernel); the pointwise weight gradient (pwgrad_kernel, a TN GEMM); the batched GEMM of the attention blocks
+// (bgemm_kernel); the eight-wave pointwise forward (pw8_kernel); then the host side - a launcher per kernel, plan_split
+// and the 3x3 geometry, one builder per kernel family, and the C ABI.  The kernels stay in one file because they share
+// DConvArgs, the epilogue and dconv_kernel<.., PW>.
+//
+// The rest of this comment is about the 3x3 convolutions, which the file began with.
 //
 // Why: v_mfma_f32_32x32x2_f32 tops out at ~136 TFLOP/s on this chip; v_mfma_f32_32x32x16_bf16 moves 16x the
 // k-depth per instruction.  Every fp32 value x is decomposed EXACTLY into hi + mid + lo (bf16 each, 8 significant
@@ -183,9 +194,19 @@ template <int NL = 3>
 int launch_pack(const float* w, void* out, int n_out, int k_in, int taps, long long sn, long long sk, long long st,
                 int flip, hipStream_t stream, const char* name) {
     const long long total = (long long)n_out * (k_in / 32) * 4;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(pack_frag_kernel<NL>, dim3(blocks), dim3(256), 0, stream, w, reinterpret_cast<u32x4*>(out), n_out,
-                       k_in, taps, sn, sk, st, flip);
+    hipLaunchKernelGGL(pack_frag_kernel<NL>, dim3(psld_grid_blocks(total, 256, 8192)), dim3(256), 0, stream, w,
+                       reinterpret_cast<u32x4*>(out), n_out, k_in, taps, sn, sk, st, flip);
+    PSLD_CHECK_LAUNCH(name);
+    return PSLD_OK;
+}
+
+// Many tensors in one launch (pack_frag_batch_kernel<NL> / pack_tail_batch_kernel over a device table)
+template <typename K>
+int launch_pack_batch(K kernel, const long long* table_dev, int entries, long long total_items, hipStream_t stream,
+                      const char* name) {
+    PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "%s: bad args", name);
+    hipLaunchKernelGGL(kernel, dim3(psld_grid_blocks(total_items, 256, 16384)), dim3(256), 0, stream, table_dev, entries,
+                       total_items);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
 }
@@ -1205,15 +1226,7 @@ __global__ void __launch_bounds__(512) dwgrad_ws_kernel(const DWgradArgs a) {
 
 int launch_dwgrad_ws(const DWgradArgs& a, int nsplit, hipStream_t stream) {
     constexpr size_t LDS = (size_t)2 * 3 * (WG_AROWS * (64 * 4 + 32) + WG_BLIMB);
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dwgrad_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("psld_conv3x3_wgrad_split_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&dwgrad_ws_kernel>(LDS, "psld_conv3x3_wgrad_split_f32")) return st;
     hipLaunchKernelGGL(dwgrad_ws_kernel, dim3((unsigned)(a.cout_tiles * a.cin_tiles * 3 * nsplit)), dim3(512), LDS, stream, a);
     PSLD_CHECK_LAUNCH("psld_conv3x3_wgrad_split_f32");
     return PSLD_OK;
@@ -1514,16 +1527,7 @@ __global__ void __launch_bounds__(256, 2) bgemm_kernel(const BGemmArgs a) {
 template <bool AT, bool BT>
 int launch_bgemm(const BGemmArgs& a, int batch, hipStream_t stream) {
     constexpr size_t LDS = (size_t)3 * ((AT ? 32 * 288 : 128 * ROWB) + (BT ? 128 * ROWB : 32 * 288));
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<AT, BT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("psld_bgemm_split_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&bgemm_kernel<AT, BT>>(LDS, "psld_bgemm_split_f32")) return st;
     hipLaunchKernelGGL((bgemm_kernel<AT, BT>), dim3((unsigned)(a.tiles_i * a.tiles_j * batch)), dim3(256), LDS, stream, a);
     PSLD_CHECK_LAUNCH("psld_bgemm_split_f32");
     return PSLD_OK;
@@ -1710,16 +1714,7 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
 template <int ABL = 0, int NL = 3>
 int launch_pw8(const DConvArgs& a, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)2 * NL * PW8_LIMB;
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw8_kernel<ABL, NL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&pw8_kernel<ABL, NL>>(LDS, name)) return st;
     const int total = cdiv(a.M, 128) * (a.N / 256);
     hipLaunchKernelGGL((pw8_kernel<ABL, NL>), dim3((unsigned)(total < 256 ? total : 256)), dim3(512), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
@@ -1729,16 +1724,7 @@ int launch_pw8(const DConvArgs& a, hipStream_t stream, const char* name) {
 template <int CB, bool XLP, int ABL = 0>
 int launch_dwgrad(const DWgradArgs& a, int nsplit, hipStream_t stream) {
     constexpr size_t LDS = (size_t)3 * (WG_AROWS * (64 * CB + 32) + WG_BLIMB);
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dwgrad_kernel<CB, XLP, ABL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("psld_conv3x3_wgrad_split_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&dwgrad_kernel<CB, XLP, ABL>>(LDS, "psld_conv3x3_wgrad_split_f32")) return st;
     hipLaunchKernelGGL((dwgrad_kernel<CB, XLP, ABL>), dim3((unsigned)(a.cout_tiles * a.cin_tiles * 3 * nsplit)), dim3(256), LDS,
                        stream, a);
     PSLD_CHECK_LAUNCH("psld_conv3x3_wgrad_split_f32");
@@ -1748,16 +1734,7 @@ int launch_dwgrad(const DWgradArgs& a, int nsplit, hipStream_t stream) {
 template <int NH, int TAPS, bool PW, int MT = 128, bool TAIL = false>
 int launch_dconv(const DConvArgs& a, int nsplit, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)3 * NH * 32 * ROWB;
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dconv_kernel<NH, TAPS, PW, MT, TAIL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&dconv_kernel<NH, TAPS, PW, MT, TAIL>>(LDS, name)) return st;
     dim3 grid((unsigned)(cdiv(a.M, MT) * cdiv(a.N, 128)), (unsigned)nsplit);
     hipLaunchKernelGGL((dconv_kernel<NH, TAPS, PW, MT, TAIL>), grid, dim3(256), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
@@ -1767,16 +1744,7 @@ int launch_dconv(const DConvArgs& a, int nsplit, hipStream_t stream, const char*
 template <int RG, bool DB, int MT = 128>
 int launch_dconv_lp(const DConvArgs& a, int nsplit, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)(DB ? 2 : 1) * 3 * RG * 16 * ROWB;
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dconv_lp_kernel<RG, DB, MT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&dconv_lp_kernel<RG, DB, MT>>(LDS, name)) return st;
     dim3 grid((unsigned)(cdiv(a.M, MT) * (a.N / 128)), (unsigned)nsplit);
     hipLaunchKernelGGL((dconv_lp_kernel<RG, DB, MT>), grid, dim3(256), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
@@ -1871,6 +1839,141 @@ int dconv_tile_rows(const DConvArgs& a, int h, int w) {
     return (tiles128 < 384 && a.M % 64 == 0 && dconv_geometry(h, w, &nseg, &rps, &halo, 64) && halo <= 160) ? 64 : 128;
 }
 
+// ---- what the entry points of a kernel family share ------------------------------------------------------------------
+// Each builder makes its entry points' checks in their order, with the entry's name in front of every message as the
+// launchers have it, and fills the kernel arguments; the extern "C" functions keep the choice of a kernel instance.
+
+// A forward launch on DConvArgs (3x3 or pointwise) between its checks and its kernel
+struct DConvPlan {
+    DConvArgs a;
+    PsldEpilogue e;         // the caller's epilogue (a.e is empty when the K ranges are summed by a second launch)
+    float* y;
+    int ldy;
+    int mt, halo_px;        // 3x3 only: rows of a tile (64 / 128) and pixel rows of its LDS halo image
+    int ns;                 // K ranges (plan_split)
+};
+
+// plan_split, and the alignment its answer has to meet
+int dconv_plan_split(DConvPlan& p, const PsldEpilogue& e, float* y, int ldy, void* workspace, long long ws_bytes, int mt) {
+    p.e = e; p.y = y; p.ldy = ldy;
+    p.ns = plan_split(p.a, e, y, ldy, workspace, ws_bytes, mt);
+    PSLD_CHECK_ARG(p.a.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
+    return PSLD_OK;
+}
+
+// The kernel's status, then the sum of the K ranges under the caller's epilogue where plan_split cut them
+int dconv_finish(int st, const DConvPlan& p, hipStream_t stream) {
+    if (st != PSLD_OK) return st;
+    if (p.ns >= 2) return psld_detail_conv_reduce_epilogue(p.a.C, p.ns, p.a.M, p.a.N, p.y, p.ldy, p.e, stream);
+    return PSLD_OK;
+}
+
+// 3x3 forward / data gradient: psld_conv3x3_split_f32 (fp32 sources) and psld_conv3x3_limb_f32 (limb planes)
+int dconv3x3_plan(DConvPlan& p, const char* name, const void* x1, int c1, const void* x2, int c2, int batch, int h, int w,
+                  const void* wfrag, int cout, float* y, int ldy, const psld_epilogue_t* epi, void* workspace,
+                  long long ws_bytes) {
+    PSLD_CHECK_ARG(x1 && wfrag && y && (c2 == 0 || x2), "%s: null pointer", name);
+    PSLD_CHECK_ARG(psld_conv3x3_split_supported(c1, c2, batch, h, w, cout), "%s: unsupported shape c1=%d c2=%d %dx%d cout=%d",
+                   name, c1, c2, h, w, cout);
+    PSLD_CHECK_ARG(aligned16(x1) && (!x2 || aligned16(x2)) && aligned16(wfrag), "%s: unaligned pointer", name);
+    DConvArgs& a = p.a;
+    a = DConvArgs{};
+    a.x1 = reinterpret_cast<const float*>(x1); a.x2 = reinterpret_cast<const float*>(x2); a.C1 = c1; a.C2 = c2;
+    a.B = batch; a.H = h; a.W = w;
+    a.wfrag = reinterpret_cast<const u32x4*>(wfrag);
+    a.N = cout; a.M = batch * h * w;
+    a.chunks = (c1 + c2) / 32;
+    const PsldEpilogue e = make_epilogue(epi);
+    p.mt = dconv_tile_rows(a, h, w);
+    p.halo_px = 0;
+    dconv_geometry(h, w, &a.nseg, &a.rps, &p.halo_px, p.mt);
+    a.pitch = dconv_pitch(w, p.mt);
+    dconv_regions(a);
+    a.zero = psld_detail_zero_page(name);
+    if (!a.zero) return PSLD_ERR_LAUNCH;
+    PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw == h * w && e.gn_hw % 64 == 0 && !e.accumulate),
+                   "%s: gn_part needs gn_hw = h*w, a multiple of 64, and no accumulation", name);
+    return dconv_plan_split(p, e, y, ldy, workspace, ws_bytes, p.mt);
+}
+
+// Pointwise forward (an NT GEMM on the pre-split B of psld_pack_gemm_frag*): psld_gemm_split_f32, its two-limb form and
+// the cut-tile form.  `supported`: the entry's own shape predicate.  `workspace`: null where the entry takes no K ranges.
+// `tail`: one source (a2 null, k2 = 0), rows of y no shorter than n, no GroupNorm partial sums.
+int pw_plan(DConvPlan& p, const char* name, bool tail, int supported, const float* a1, int k1, const float* a2, int k2, int m,
+            const void* bfrag, int n, float* y, int ldy, const psld_epilogue_t* epi, void* workspace, long long ws_bytes) {
+    PSLD_CHECK_ARG(a1 && bfrag && y && (k2 == 0 || a2), "%s: null pointer", name);
+    if (tail) PSLD_CHECK_ARG(supported, "%s: unsupported shape k=%d m=%d n=%d", name, k1, m, n);
+    else PSLD_CHECK_ARG(supported, "%s: unsupported shape k1=%d k2=%d m=%d n=%d", name, k1, k2, m, n);
+    PSLD_CHECK_ARG(aligned16(a1) && (!a2 || aligned16(a2)) && aligned16(bfrag), "%s: unaligned pointer", name);
+    if (tail) PSLD_CHECK_ARG(ldy >= n, "%s: ldy %d < n %d", name, ldy, n);
+    const PsldEpilogue e = make_epilogue(epi);
+    if (tail) PSLD_CHECK_ARG(!e.gn_part, "%s: no GroupNorm partial sums on cut tiles (take the statistics in a pass of their own)", name);
+    DConvArgs& a = p.a;
+    a = DConvArgs{};
+    a.x1 = a1; a.x2 = a2; a.C1 = k1; a.C2 = k2;
+    a.B = 1; a.H = 1; a.W = 1;
+    a.wfrag = reinterpret_cast<const u32x4*>(bfrag);
+    a.N = n; a.M = m;
+    a.chunks = cdiv(k1 + k2, 64);       // stages of two 32-channel chunks; tail: the odd chunk behind k is zeros on both sides
+    a.nseg = 1; a.rps = 1; a.pitch = a.W + 2;
+    a.zero = psld_detail_zero_page(name);
+    if (!a.zero) return PSLD_ERR_LAUNCH;
+    if (!tail) PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw > 0 && e.gn_hw % 64 == 0 && m % e.gn_hw == 0 && !e.accumulate),
+                              "%s: gn_part needs gn_hw (rows per image) a multiple of 64 dividing m, and no accumulation", name);
+    p.mt = 128; p.halo_px = 0;
+    return dconv_plan_split(p, e, y, ldy, workspace, ws_bytes, 128);
+}
+
+// 3x3 weight gradient: psld_conv3x3_wgrad_split_f32 (x in fp32) and psld_conv3x3_wgrad_xlimb_f32 (x in limb planes)
+int dwgrad_plan(DWgradArgs& a, const char* name, const float* dy, int lddy, int cout, const void* x, int cin, const void* x2,
+                int cin2, int batch, int h, int w, float* slabs, int cin_total, int col0, int nsplit) {
+    PSLD_CHECK_ARG(dy && x && slabs && nsplit >= 1 && cin2 >= 0 && (cin2 == 0 || x2), "%s: bad args", name);
+    PSLD_CHECK_ARG(psld_conv3x3_wgrad_split_supported(cout, cin, batch, h, w) &&
+                       (cin2 == 0 || psld_conv3x3_wgrad_split_supported(cout, cin2, batch, h, w)),
+                   "%s: unsupported shape cout=%d cin=%d+%d %dx%d", name, cout, cin, cin2, h, w);
+    PSLD_CHECK_ARG(aligned16(dy) && aligned16(x) && (cin2 == 0 || aligned16(x2)) && lddy % 4 == 0, "%s: unaligned operand", name);
+    a = DWgradArgs{};
+    a.dy = dy; a.lddy = lddy; a.x = reinterpret_cast<const float*>(x); a.cin = cin;
+    a.x2 = reinterpret_cast<const float*>(x2); a.cin2 = cin2;
+    a.B = batch; a.H = h; a.W = w;
+    a.cout_tiles = cout / psld_conv3x3_wgrad_split_cout_tile(cout); a.cin_tiles = (cin + cin2) / 64;
+    a.ktiles = batch * h * w / 32;
+    a.ktiles_per_split = cdiv(a.ktiles, nsplit);
+    PSLD_CHECK_ARG(cdiv(a.ktiles, a.ktiles_per_split) == nsplit, "%s: nsplit %d leaves empty slabs", name, nsplit);
+    a.slabs = slabs + col0;
+    a.ld_tap = cin_total;
+    a.slab_stride = (long long)cout * 9 * cin_total;
+    a.hw_w = (w < 32 ? w : 32) + 2;
+    a.hrows = w >= 32 ? 1 : 32 / w;
+    return PSLD_OK;
+}
+
+// Pointwise weight gradient: psld_gemm_tn_split_f32 and, TAIL, its cut-tile form (one B source: b2 null, n2 = 0)
+template <bool TAIL>
+int launch_pwgrad(const char* name, int m, int n, int k, const float* a, int lda, const float* b, int ldb, const float* b2,
+                  int ldb2, int n2, float* slabs, int ldc, int nsplit, hipStream_t stream) {
+    PSLD_CHECK_ARG(a && b && slabs && nsplit >= 1 && n2 >= 0 && (n2 == 0 || b2), "%s: bad args", name);
+    if (TAIL) PSLD_CHECK_ARG(psld_gemm_tn_split_tail_supported(m, n, k), "%s: unsupported shape m=%d n=%d k=%d", name, m, n, k);
+    else PSLD_CHECK_ARG(psld_gemm_tn_split_supported(m, n, k) && n2 % 128 == 0, "%s: unsupported shape m=%d n=%d+%d k=%d", name, m, n, n2, k);
+    PSLD_CHECK_ARG(aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0 && lda >= m && ldb >= n && ldc >= n + n2 &&
+                       (n2 == 0 || (aligned16(b2) && ldb2 % 4 == 0 && ldb2 >= n2)),
+                   "%s: unaligned operand or short row stride", name);
+    PWgradArgs p{};
+    p.a = a; p.lda = lda; p.b = b; p.ldb = ldb; p.b2 = b2; p.ldb2 = ldb2; p.n1 = n;
+    if (TAIL) { p.m = m; p.n = n; }
+    p.tiles_i = cdiv(m, 128); p.tiles_j = cdiv(n + n2, 128);
+    p.ktiles = k / 32;
+    p.ktiles_per_split = cdiv(p.ktiles, nsplit);
+    PSLD_CHECK_ARG(cdiv(p.ktiles, p.ktiles_per_split) == nsplit, "%s: nsplit %d leaves empty slabs", name, nsplit);
+    p.slabs = slabs; p.ldc = ldc;
+    p.slab_stride = (long long)m * ldc;
+    constexpr size_t LDS = (size_t)2 * 3 * 32 * 288;
+    if (int st = psld_lds_once<&pwgrad_kernel<TAIL>>(LDS, name)) return st;
+    hipLaunchKernelGGL(pwgrad_kernel<TAIL>, dim3((unsigned)(p.tiles_i * p.tiles_j * nsplit)), dim3(256), LDS, stream, p);
+    PSLD_CHECK_LAUNCH(name);
+    return PSLD_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------
@@ -1903,69 +2006,39 @@ extern "C" int psld_pack_conv3x3_frag(const float* w_oihw, void* wfrag, int cout
 }
 
 extern "C" int psld_pack_frag_batch(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
-    PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_frag_batch: bad args");
-    const long long want = (total_items + 255) / 256;
-    hipLaunchKernelGGL(pack_frag_batch_kernel<3>, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream,
-                       table_dev, entries, total_items);
-    PSLD_CHECK_LAUNCH("psld_pack_frag_batch");
-    return PSLD_OK;
+    return launch_pack_batch(pack_frag_batch_kernel<3>, table_dev, entries, total_items, stream, "psld_pack_frag_batch");
 }
 
 extern "C" int psld_conv3x3_split_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
                                       const void* wfrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
                                       void* workspace, long long ws_bytes, hipStream_t stream) {
-    PSLD_CHECK_ARG(x1 && wfrag && y && (c2 == 0 || x2), "psld_conv3x3_split_f32: null pointer");
-    PSLD_CHECK_ARG(psld_conv3x3_split_supported(c1, c2, batch, h, w, cout),
-                   "psld_conv3x3_split_f32: unsupported shape c1=%d c2=%d %dx%d cout=%d", c1, c2, h, w, cout);
-    PSLD_CHECK_ARG(aligned16(x1) && (!x2 || aligned16(x2)) && aligned16(wfrag), "psld_conv3x3_split_f32: unaligned pointer");
-    DConvArgs a{};
-    a.x1 = x1; a.x2 = x2; a.C1 = c1; a.C2 = c2;
-    a.B = batch; a.H = h; a.W = w;
-    a.wfrag = reinterpret_cast<const u32x4*>(wfrag);
-    a.N = cout; a.M = batch * h * w;
-    a.chunks = (c1 + c2) / 32;
-    int halo_px = 0;
-    const PsldEpilogue e = make_epilogue(epi);
-    a.e = e;
-    const int mt = dconv_tile_rows(a, h, w);
-    dconv_geometry(h, w, &a.nseg, &a.rps, &halo_px, mt);
-    a.pitch = dconv_pitch(w, mt);
-    dconv_regions(a);
-    a.zero = psld_detail_zero_page("psld_conv3x3_split_f32");
-    if (!a.zero) return PSLD_ERR_LAUNCH;
-    PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw == h * w && e.gn_hw % 64 == 0 && !e.accumulate),
-                   "psld_conv3x3_split_f32: gn_part needs gn_hw = h*w, a multiple of 64, and no accumulation");
-    const int ns = plan_split(a, e, y, ldy, workspace, ws_bytes, mt);
-    PSLD_CHECK_ARG(a.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
-    const int nh = cdiv((long long)halo_px * 8, 256);
     const char* name = "psld_conv3x3_split_f32";
+    DConvPlan p;
+    if (int st = dconv3x3_plan(p, name, x1, c1, x2, c2, batch, h, w, wfrag, cout, y, ldy, epi, workspace, ws_bytes)) return st;
+    const int nh = cdiv((long long)p.halo_px * 8, 256);
     int st;
-    if (mt == 64) st = nh <= 4 ? launch_dconv<4, 9, false, 64>(a, ns, stream, name)
-                               : launch_dconv<5, 9, false, 64>(a, ns, stream, name);
-    else if (nh <= 6) st = launch_dconv<6, 9, false>(a, ns, stream, name);
-    else if (nh <= 7) st = launch_dconv<7, 9, false>(a, ns, stream, name);
-    else st = launch_dconv<9, 9, false>(a, ns, stream, name);
-    if (st != PSLD_OK) return st;
-    if (ns >= 2) return psld_detail_conv_reduce_epilogue(a.C, ns, a.M, cout, y, ldy, e, stream);
-    return PSLD_OK;
+    if (p.mt == 64) st = nh <= 4 ? launch_dconv<4, 9, false, 64>(p.a, p.ns, stream, name)
+                                 : launch_dconv<5, 9, false, 64>(p.a, p.ns, stream, name);
+    else if (nh <= 6) st = launch_dconv<6, 9, false>(p.a, p.ns, stream, name);
+    else if (nh <= 7) st = launch_dconv<7, 9, false>(p.a, p.ns, stream, name);
+    else st = launch_dconv<9, 9, false>(p.a, p.ns, stream, name);
+    return dconv_finish(st, p, stream);
 }
 
 extern "C" long long psld_limb_bytes(long long rows, int c) { return rows * (long long)c * LP_PIX_BYTES_PER_CH; }
 
 extern "C" int psld_f32_to_limb(const float* x, long long rows, int c, void* y, hipStream_t stream) {
     PSLD_CHECK_ARG(x && y && rows > 0 && c > 0 && c % 32 == 0 && aligned16(x) && aligned16(y), "psld_f32_to_limb: bad args");
-    const long long n4 = rows * (c / 4);
-    const int blocks = (int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
-    hipLaunchKernelGGL(f32_to_limb_kernel, dim3(blocks), dim3(256), 0, stream, x, rows, c, reinterpret_cast<unsigned char*>(y));
+    hipLaunchKernelGGL(f32_to_limb_kernel, dim3(psld_grid_blocks(rows * (c / 4), 256, 16384)), dim3(256), 0, stream, x, rows, c,
+                       reinterpret_cast<unsigned char*>(y));
     PSLD_CHECK_LAUNCH("psld_f32_to_limb");
     return PSLD_OK;
 }
 
 extern "C" int psld_limb_to_f32(const void* y, long long rows, int c, float* x, hipStream_t stream) {
     PSLD_CHECK_ARG(x && y && rows > 0 && c > 0 && c % 32 == 0, "psld_limb_to_f32: bad args");
-    const long long n = rows * c;
-    const int blocks = (int)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
-    hipLaunchKernelGGL(limb_to_f32_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const unsigned char*>(y), rows, c, x);
+    hipLaunchKernelGGL(limb_to_f32_kernel, dim3(psld_grid_blocks(rows * c, 256, 16384)), dim3(256), 0, stream,
+                       reinterpret_cast<const unsigned char*>(y), rows, c, x);
     PSLD_CHECK_LAUNCH("psld_limb_to_f32");
     return PSLD_OK;
 }
@@ -1973,41 +2046,19 @@ extern "C" int psld_limb_to_f32(const void* y, long long rows, int c, float* x, 
 extern "C" int psld_conv3x3_limb_f32(const void* x1, int c1, const void* x2, int c2, int batch, int h, int w,
                                      const void* wfrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
                                      void* workspace, long long ws_bytes, hipStream_t stream) {
-    PSLD_CHECK_ARG(x1 && wfrag && y && (c2 == 0 || x2), "psld_conv3x3_limb_f32: null pointer");
-    PSLD_CHECK_ARG(psld_conv3x3_split_supported(c1, c2, batch, h, w, cout),
-                   "psld_conv3x3_limb_f32: unsupported shape c1=%d c2=%d %dx%d cout=%d", c1, c2, h, w, cout);
-    PSLD_CHECK_ARG(aligned16(x1) && (!x2 || aligned16(x2)) && aligned16(wfrag), "psld_conv3x3_limb_f32: unaligned pointer");
-    DConvArgs a{};
-    a.x1 = reinterpret_cast<const float*>(x1); a.x2 = reinterpret_cast<const float*>(x2); a.C1 = c1; a.C2 = c2;
-    a.B = batch; a.H = h; a.W = w;
-    a.wfrag = reinterpret_cast<const u32x4*>(wfrag);
-    a.N = cout; a.M = batch * h * w;
-    a.chunks = (c1 + c2) / 32;
-    int halo_px = 0;
-    const PsldEpilogue e = make_epilogue(epi);
-    const int mt = dconv_tile_rows(a, h, w);
-    dconv_geometry(h, w, &a.nseg, &a.rps, &halo_px, mt);
-    a.pitch = dconv_pitch(w, mt);
-    dconv_regions(a);
-    a.zero = psld_detail_zero_page("psld_conv3x3_limb_f32");
-    if (!a.zero) return PSLD_ERR_LAUNCH;
-    PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw == h * w && e.gn_hw % 64 == 0 && !e.accumulate),
-                   "psld_conv3x3_limb_f32: gn_part needs gn_hw = h*w, a multiple of 64, and no accumulation");
-    const int ns = plan_split(a, e, y, ldy, workspace, ws_bytes, mt);
-    PSLD_CHECK_ARG(a.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
-    const int rg = cdiv(halo_px, 16);
     const char* name = "psld_conv3x3_limb_f32";
+    DConvPlan p;
+    if (int st = dconv3x3_plan(p, name, x1, c1, x2, c2, batch, h, w, wfrag, cout, y, ldy, epi, workspace, ws_bytes)) return st;
+    const int rg = cdiv(p.halo_px, 16);
     int st;
     // two images of RG <= 13 row groups (79,872 B) leave room for two workgroups per CU (163,840 B of LDS)
-    if (mt == 64) st = rg <= 7 ? launch_dconv_lp<7, true, 64>(a, ns, stream, name)
-                     : rg <= 9 ? launch_dconv_lp<9, true, 64>(a, ns, stream, name)
-                               : launch_dconv_lp<10, true, 64>(a, ns, stream, name);
-    else if (rg <= 12) st = launch_dconv_lp<12, true>(a, ns, stream, name);
-    else if (rg <= 13) st = launch_dconv_lp<13, true>(a, ns, stream, name);
-    else st = launch_dconv_lp<18, false>(a, ns, stream, name);
-    if (st != PSLD_OK) return st;
-    if (ns >= 2) return psld_detail_conv_reduce_epilogue(a.C, ns, a.M, cout, y, ldy, e, stream);
-    return PSLD_OK;
+    if (p.mt == 64) st = rg <= 7 ? launch_dconv_lp<7, true, 64>(p.a, p.ns, stream, name)
+                       : rg <= 9 ? launch_dconv_lp<9, true, 64>(p.a, p.ns, stream, name)
+                                 : launch_dconv_lp<10, true, 64>(p.a, p.ns, stream, name);
+    else if (rg <= 12) st = launch_dconv_lp<12, true>(p.a, p.ns, stream, name);
+    else if (rg <= 13) st = launch_dconv_lp<13, true>(p.a, p.ns, stream, name);
+    else st = launch_dconv_lp<18, false>(p.a, p.ns, stream, name);
+    return dconv_finish(st, p, stream);
 }
 
 extern "C" int psld_conv3x3_wgrad_split_supported(int cout, int cin, int batch, int h, int w) {
@@ -2020,25 +2071,11 @@ extern "C" int psld_conv3x3_wgrad_split_cout_tile(int cout) { return cout % 128 
 extern "C" int psld_conv3x3_wgrad_split_f32(const float* dy, int lddy, int cout, const float* x, int cin,
                                             const float* x2, int cin2, int batch, int h, int w, float* slabs,
                                             int cin_total, int col0, int nsplit, hipStream_t stream) {
-    PSLD_CHECK_ARG(dy && x && slabs && nsplit >= 1 && cin2 >= 0 && (cin2 == 0 || x2), "psld_conv3x3_wgrad_split_f32: bad args");
-    PSLD_CHECK_ARG(psld_conv3x3_wgrad_split_supported(cout, cin, batch, h, w) &&
-                       (cin2 == 0 || psld_conv3x3_wgrad_split_supported(cout, cin2, batch, h, w)),
-                   "psld_conv3x3_wgrad_split_f32: unsupported shape cout=%d cin=%d+%d %dx%d", cout, cin, cin2, h, w);
-    PSLD_CHECK_ARG(aligned16(dy) && aligned16(x) && (cin2 == 0 || aligned16(x2)) && lddy % 4 == 0,
-                   "psld_conv3x3_wgrad_split_f32: unaligned operand");
-    DWgradArgs a{};
-    a.dy = dy; a.lddy = lddy; a.x = x; a.cin = cin; a.x2 = x2; a.cin2 = cin2;
-    a.B = batch; a.H = h; a.W = w;
+    DWgradArgs a;
+    if (int st = dwgrad_plan(a, "psld_conv3x3_wgrad_split_f32", dy, lddy, cout, x, cin, x2, cin2, batch, h, w, slabs, cin_total,
+                             col0, nsplit))
+        return st;
     const int co_tile = psld_conv3x3_wgrad_split_cout_tile(cout);
-    a.cout_tiles = cout / co_tile; a.cin_tiles = (cin + cin2) / 64;
-    a.ktiles = batch * h * w / 32;
-    a.ktiles_per_split = cdiv(a.ktiles, nsplit);
-    PSLD_CHECK_ARG(cdiv(a.ktiles, a.ktiles_per_split) == nsplit, "psld_conv3x3_wgrad_split_f32: nsplit %d leaves empty slabs", nsplit);
-    a.slabs = slabs + col0;
-    a.ld_tap = cin_total;
-    a.slab_stride = (long long)cout * 9 * cin_total;
-    a.hw_w = (w < 32 ? w : 32) + 2;
-    a.hrows = w >= 32 ? 1 : 32 / w;
 #ifdef PSLD_ABLATIONS      // timing-only variants (wrong results): libpsld_hip_abl.so only (make -C tools/abl), never the product library
     static const int ws = [] { const char* v = getenv("PSLD_DWGRAD_WS"); return v ? atoi(v) : 1; }();
     if (!ws && co_tile == 128) return launch_dwgrad<4, false>(a, nsplit, stream);     // round 3's kernel, for A/B
@@ -2060,27 +2097,12 @@ extern "C" int psld_conv3x3_wgrad_split_f32(const float* dy, int lddy, int cout,
 extern "C" int psld_conv3x3_wgrad_xlimb_f32(const float* dy, int lddy, int cout, const void* x_limb, int cin,
                                             const void* x2_limb, int cin2, int batch, int h, int w, float* slabs,
                                             int cin_total, int col0, int nsplit, hipStream_t stream) {
-    PSLD_CHECK_ARG(dy && x_limb && slabs && nsplit >= 1 && cin2 >= 0 && (cin2 == 0 || x2_limb), "psld_conv3x3_wgrad_xlimb_f32: bad args");
-    PSLD_CHECK_ARG(psld_conv3x3_wgrad_split_supported(cout, cin, batch, h, w) &&
-                       (cin2 == 0 || psld_conv3x3_wgrad_split_supported(cout, cin2, batch, h, w)),
-                   "psld_conv3x3_wgrad_xlimb_f32: unsupported shape cout=%d cin=%d+%d %dx%d", cout, cin, cin2, h, w);
-    PSLD_CHECK_ARG(aligned16(dy) && aligned16(x_limb) && (cin2 == 0 || aligned16(x2_limb)) && lddy % 4 == 0,
-                   "psld_conv3x3_wgrad_xlimb_f32: unaligned operand");
-    DWgradArgs a{};
-    a.dy = dy; a.lddy = lddy; a.x = reinterpret_cast<const float*>(x_limb); a.cin = cin;
-    a.x2 = reinterpret_cast<const float*>(x2_limb); a.cin2 = cin2;
-    a.B = batch; a.H = h; a.W = w;
-    const int co_tile = psld_conv3x3_wgrad_split_cout_tile(cout);
-    a.cout_tiles = cout / co_tile; a.cin_tiles = (cin + cin2) / 64;
-    a.ktiles = batch * h * w / 32;
-    a.ktiles_per_split = cdiv(a.ktiles, nsplit);
-    PSLD_CHECK_ARG(cdiv(a.ktiles, a.ktiles_per_split) == nsplit, "psld_conv3x3_wgrad_xlimb_f32: nsplit %d leaves empty slabs", nsplit);
-    a.slabs = slabs + col0;
-    a.ld_tap = cin_total;
-    a.slab_stride = (long long)cout * 9 * cin_total;
-    a.hw_w = (w < 32 ? w : 32) + 2;
-    a.hrows = w >= 32 ? 1 : 32 / w;
-    return co_tile == 128 ? launch_dwgrad<4, true>(a, nsplit, stream) : launch_dwgrad<2, true>(a, nsplit, stream);
+    DWgradArgs a;
+    if (int st = dwgrad_plan(a, "psld_conv3x3_wgrad_xlimb_f32", dy, lddy, cout, x_limb, cin, x2_limb, cin2, batch, h, w, slabs,
+                             cin_total, col0, nsplit))
+        return st;
+    return psld_conv3x3_wgrad_split_cout_tile(cout) == 128 ? launch_dwgrad<4, true>(a, nsplit, stream)
+                                                           : launch_dwgrad<2, true>(a, nsplit, stream);
 }
 
 // ---- pointwise weight gradient ------------------------------------------------------------------------------
@@ -2091,35 +2113,7 @@ extern "C" int psld_gemm_tn_split_supported(int m, int n, int k) {
 extern "C" int psld_gemm_tn_split_f32(int m, int n, int k, const float* a, int lda, const float* b, int ldb,
                                       const float* b2, int ldb2, int n2, float* slabs, int ldc, int nsplit,
                                       hipStream_t stream) {
-    PSLD_CHECK_ARG(a && b && slabs && nsplit >= 1 && n2 >= 0 && (n2 == 0 || b2), "psld_gemm_tn_split_f32: bad args");
-    PSLD_CHECK_ARG(psld_gemm_tn_split_supported(m, n, k) && n2 % 128 == 0,
-                   "psld_gemm_tn_split_f32: unsupported shape m=%d n=%d+%d k=%d", m, n, n2, k);
-    PSLD_CHECK_ARG(aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0 && lda >= m && ldb >= n && ldc >= n + n2 &&
-                       (n2 == 0 || (aligned16(b2) && ldb2 % 4 == 0 && ldb2 >= n2)),
-                   "psld_gemm_tn_split_f32: unaligned operand or short row stride");
-    PWgradArgs p{};
-    p.a = a; p.lda = lda; p.b = b; p.ldb = ldb; p.b2 = b2; p.ldb2 = ldb2; p.n1 = n;
-    n += n2;
-    p.tiles_i = m / 128; p.tiles_j = n / 128;
-    p.ktiles = k / 32;
-    p.ktiles_per_split = cdiv(p.ktiles, nsplit);
-    PSLD_CHECK_ARG(cdiv(p.ktiles, p.ktiles_per_split) == nsplit, "psld_gemm_tn_split_f32: nsplit %d leaves empty slabs", nsplit);
-    p.slabs = slabs; p.ldc = ldc;
-    p.slab_stride = (long long)m * ldc;
-    constexpr size_t LDS = (size_t)2 * 3 * 32 * 288;
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwgrad_kernel<>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("psld_gemm_tn_split_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
-    hipLaunchKernelGGL(pwgrad_kernel<>, dim3((unsigned)(p.tiles_i * p.tiles_j * nsplit)), dim3(256), LDS, stream, p);
-    PSLD_CHECK_LAUNCH("psld_gemm_tn_split_f32");
-    return PSLD_OK;
+    return launch_pwgrad<false>("psld_gemm_tn_split_f32", m, n, k, a, lda, b, ldb, b2, ldb2, n2, slabs, ldc, nsplit, stream);
 }
 
 // m, n: multiples of 32 from 128 up, not both multiples of 128 (those are psld_gemm_tn_split_f32's)
@@ -2129,33 +2123,7 @@ extern "C" int psld_gemm_tn_split_tail_supported(int m, int n, int k) {
 
 extern "C" int psld_gemm_tn_split_tail_f32(int m, int n, int k, const float* a, int lda, const float* b, int ldb,
                                            float* slabs, int ldc, int nsplit, hipStream_t stream) {
-    PSLD_CHECK_ARG(a && b && slabs && nsplit >= 1, "psld_gemm_tn_split_tail_f32: bad args");
-    PSLD_CHECK_ARG(psld_gemm_tn_split_tail_supported(m, n, k), "psld_gemm_tn_split_tail_f32: unsupported shape m=%d n=%d k=%d", m, n, k);
-    PSLD_CHECK_ARG(aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0 && lda >= m && ldb >= n && ldc >= n,
-                   "psld_gemm_tn_split_tail_f32: unaligned operand or short row stride");
-    PWgradArgs p{};
-    p.a = a; p.lda = lda; p.b = b; p.ldb = ldb; p.n1 = n;
-    p.m = m; p.n = n;
-    p.tiles_i = cdiv(m, 128); p.tiles_j = cdiv(n, 128);
-    p.ktiles = k / 32;
-    p.ktiles_per_split = cdiv(p.ktiles, nsplit);
-    PSLD_CHECK_ARG(cdiv(p.ktiles, p.ktiles_per_split) == nsplit, "psld_gemm_tn_split_tail_f32: nsplit %d leaves empty slabs", nsplit);
-    p.slabs = slabs; p.ldc = ldc;
-    p.slab_stride = (long long)m * ldc;
-    constexpr size_t LDS = (size_t)2 * 3 * 32 * 288;
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pwgrad_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("psld_gemm_tn_split_tail_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
-    hipLaunchKernelGGL(pwgrad_kernel<true>, dim3((unsigned)(p.tiles_i * p.tiles_j * nsplit)), dim3(256), LDS, stream, p);
-    PSLD_CHECK_LAUNCH("psld_gemm_tn_split_tail_f32");
-    return PSLD_OK;
+    return launch_pwgrad<true>("psld_gemm_tn_split_tail_f32", m, n, k, a, lda, b, ldb, nullptr, 0, 0, slabs, ldc, nsplit, stream);
 }
 
 // ---- batched GEMM, both operands fp32 activations --------------------------------------------------------------
@@ -2199,44 +2167,29 @@ extern "C" int psld_pack_gemm_frag(const float* b, void* bfrag, int n, int k, lo
 extern "C" int psld_gemm_split_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
                                    float* y, int ldy, const psld_epilogue_t* epi, void* workspace, long long ws_bytes,
                                    hipStream_t stream) {
-    PSLD_CHECK_ARG(a1 && bfrag && y && (k2 == 0 || a2), "psld_gemm_split_f32: null pointer");
-    PSLD_CHECK_ARG(psld_gemm_split_supported(k1, k2, m, n), "psld_gemm_split_f32: unsupported shape k1=%d k2=%d m=%d n=%d", k1, k2, m, n);
-    PSLD_CHECK_ARG(aligned16(a1) && (!a2 || aligned16(a2)) && aligned16(bfrag), "psld_gemm_split_f32: unaligned pointer");
-    DConvArgs a{};
-    a.x1 = a1; a.x2 = a2; a.C1 = k1; a.C2 = k2;
-    a.B = 1; a.H = 1; a.W = 1;
-    a.wfrag = reinterpret_cast<const u32x4*>(bfrag);
-    a.N = n; a.M = m;
-    a.chunks = (k1 + k2) / 64;          // stages of two 32-channel chunks
-    a.nseg = 1; a.rps = 1; a.pitch = a.W + 2;
-    a.zero = psld_detail_zero_page("psld_gemm_split_f32");
-    if (!a.zero) return PSLD_ERR_LAUNCH;
-    const PsldEpilogue e = make_epilogue(epi);
-    PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw > 0 && e.gn_hw % 64 == 0 && m % e.gn_hw == 0 && !e.accumulate),
-                   "psld_gemm_split_f32: gn_part needs gn_hw (rows per image) a multiple of 64 dividing m, and no accumulation");
+    const char* name = "psld_gemm_split_f32";
     // eight-wave 128 x 256 tiles from 128 of them on (below: the four-wave 128 x 128 kernel).  Half a chip of persistent
     // workgroups still beats 256 four-wave tiles split in two K ranges plus their reduction launch: B=16 step 537 / 539 ->
     // 550 / 547 images/s, B=64 903 -> 908; from 64 tiles on it does not (543 / 542).
     const bool wide = n % 256 == 0 && (long long)cdiv(m, 128) * (n / 256) >= 128;
-    const int ns = plan_split(a, e, y, ldy, wide ? nullptr : workspace, ws_bytes);
-    PSLD_CHECK_ARG(a.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
+    DConvPlan p;
+    if (int st = pw_plan(p, name, false, psld_gemm_split_supported(k1, k2, m, n), a1, k1, a2, k2, m, bfrag, n, y, ldy, epi,
+                         wide ? nullptr : workspace, ws_bytes))
+        return st;
     if (wide) {
 #ifdef PSLD_ABLATIONS      // timing-only variants (wrong results): libpsld_hip_abl.so only
         static const int abl = [] { const char* v = getenv("PSLD_PW8_ABL"); return v ? atoi(v) : 0; }();
         switch (abl) {
-            case 1: return launch_pw8<1>(a, stream, "psld_gemm_split_f32");
-            case 2: return launch_pw8<2>(a, stream, "psld_gemm_split_f32");
-            case 3: return launch_pw8<3>(a, stream, "psld_gemm_split_f32");
-            case 4: return launch_pw8<4>(a, stream, "psld_gemm_split_f32");
-            case 7: return launch_pw8<7>(a, stream, "psld_gemm_split_f32");
+            case 1: return launch_pw8<1>(p.a, stream, name);
+            case 2: return launch_pw8<2>(p.a, stream, name);
+            case 3: return launch_pw8<3>(p.a, stream, name);
+            case 4: return launch_pw8<4>(p.a, stream, name);
+            case 7: return launch_pw8<7>(p.a, stream, name);
         }
 #endif
-        return launch_pw8<0>(a, stream, "psld_gemm_split_f32");
+        return launch_pw8<0>(p.a, stream, name);
     }
-    const int st = launch_dconv<8, 2, true>(a, ns, stream, "psld_gemm_split_f32");
-    if (st != PSLD_OK) return st;
-    if (ns >= 2) return psld_detail_conv_reduce_epilogue(a.C, ns, m, n, y, ldy, e, stream);
-    return PSLD_OK;
+    return dconv_finish(launch_dconv<8, 2, true>(p.a, p.ns, stream, name), p, stream);
 }
 
 // ---- two limbs (PSLD_MATH_BF16X3): the eight-wave pointwise kernel on hi / mid fragments ----------------------------
@@ -2255,34 +2208,17 @@ extern "C" int psld_pack_gemm_frag_x3(const float* b, void* bfrag, int n, int k,
 }
 
 extern "C" int psld_pack_frag_batch_x3(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
-    PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_frag_batch_x3: bad args");
-    const long long want = (total_items + 255) / 256;
-    hipLaunchKernelGGL(pack_frag_batch_kernel<2>, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream,
-                       table_dev, entries, total_items);
-    PSLD_CHECK_LAUNCH("psld_pack_frag_batch_x3");
-    return PSLD_OK;
+    return launch_pack_batch(pack_frag_batch_kernel<2>, table_dev, entries, total_items, stream, "psld_pack_frag_batch_x3");
 }
 
 extern "C" int psld_gemm_split_x3_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
                                       float* y, int ldy, const psld_epilogue_t* epi, hipStream_t stream) {
-    PSLD_CHECK_ARG(a1 && bfrag && y && (k2 == 0 || a2), "psld_gemm_split_x3_f32: null pointer");
-    PSLD_CHECK_ARG(psld_gemm_split_x3_supported(k1, k2, m, n), "psld_gemm_split_x3_f32: unsupported shape k1=%d k2=%d m=%d n=%d", k1, k2, m, n);
-    PSLD_CHECK_ARG(aligned16(a1) && (!a2 || aligned16(a2)) && aligned16(bfrag), "psld_gemm_split_x3_f32: unaligned pointer");
-    DConvArgs a{};
-    a.x1 = a1; a.x2 = a2; a.C1 = k1; a.C2 = k2;
-    a.B = 1; a.H = 1; a.W = 1;
-    a.wfrag = reinterpret_cast<const u32x4*>(bfrag);
-    a.N = n; a.M = m;
-    a.chunks = (k1 + k2) / 64;
-    a.nseg = 1; a.rps = 1; a.pitch = a.W + 2;
-    a.zero = psld_detail_zero_page("psld_gemm_split_x3_f32");
-    if (!a.zero) return PSLD_ERR_LAUNCH;
-    const PsldEpilogue e = make_epilogue(epi);
-    PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw > 0 && e.gn_hw % 64 == 0 && m % e.gn_hw == 0 && !e.accumulate),
-                   "psld_gemm_split_x3_f32: gn_part needs gn_hw (rows per image) a multiple of 64 dividing m, and no accumulation");
-    plan_split(a, e, y, ldy, nullptr, 0);
-    PSLD_CHECK_ARG(a.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
-    return launch_pw8<0, 2>(a, stream, "psld_gemm_split_x3_f32");
+    const char* name = "psld_gemm_split_x3_f32";
+    DConvPlan p;
+    if (int st = pw_plan(p, name, false, psld_gemm_split_x3_supported(k1, k2, m, n), a1, k1, a2, k2, m, bfrag, n, y, ldy, epi,
+                         nullptr, 0))
+        return st;
+    return launch_pw8<0, 2>(p.a, stream, name);
 }
 
 // ---- pointwise, channel widths in steps of 32 ("tail": the shapes psld_gemm_split_supported refuses for n % 128 or k % 64) ----
@@ -2302,9 +2238,8 @@ extern "C" int psld_pack_gemm_frag_tail(const float* b, void* bfrag, int n, int 
     PSLD_CHECK_ARG(n > 0 && k > 0 && n % 32 == 0 && k % 32 == 0 && n < (1 << 20) && k < (1 << 20),
                    "psld_pack_gemm_frag_tail: needs n %%32 and k %%32 (got %d, %d)", n, k);
     const long long items = (long long)tail_rows(n, 0, n) * tail_chunks(k, 0, k / 32) * 4;
-    const int blocks = (int)((items + 255) / 256 < 8192 ? (items + 255) / 256 : 8192);
-    hipLaunchKernelGGL(pack_tail_kernel, dim3(blocks), dim3(256), 0, stream, b, reinterpret_cast<u32x4*>(bfrag), n, k, stride_n,
-                       stride_k, items);
+    hipLaunchKernelGGL(pack_tail_kernel, dim3(psld_grid_blocks(items, 256, 8192)), dim3(256), 0, stream, b,
+                       reinterpret_cast<u32x4*>(bfrag), n, k, stride_n, stride_k, items);
     PSLD_CHECK_LAUNCH("psld_pack_gemm_frag_tail");
     return PSLD_OK;
 }
@@ -2316,35 +2251,15 @@ extern "C" long long psld_pack_frag_tail_items(int n, int n0, int n_total, int k
 }
 
 extern "C" int psld_pack_frag_batch_tail(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
-    PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_frag_batch_tail: bad args");
-    const long long want = (total_items + 255) / 256;
-    hipLaunchKernelGGL(pack_tail_batch_kernel, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream, table_dev,
-                       entries, total_items);
-    PSLD_CHECK_LAUNCH("psld_pack_frag_batch_tail");
-    return PSLD_OK;
+    return launch_pack_batch(pack_tail_batch_kernel, table_dev, entries, total_items, stream, "psld_pack_frag_batch_tail");
 }
 
 extern "C" int psld_gemm_split_tail_f32(const float* a, int k, int m, const void* bfrag, int n, float* y, int ldy,
                                         const psld_epilogue_t* epi, void* workspace, long long ws_bytes, hipStream_t stream) {
-    PSLD_CHECK_ARG(a && bfrag && y, "psld_gemm_split_tail_f32: null pointer");
-    PSLD_CHECK_ARG(psld_gemm_tail_supported(k, m, n), "psld_gemm_split_tail_f32: unsupported shape k=%d m=%d n=%d", k, m, n);
-    PSLD_CHECK_ARG(aligned16(a) && aligned16(bfrag), "psld_gemm_split_tail_f32: unaligned pointer");
-    PSLD_CHECK_ARG(ldy >= n, "psld_gemm_split_tail_f32: ldy %d < n %d", ldy, n);
-    const PsldEpilogue e = make_epilogue(epi);
-    PSLD_CHECK_ARG(!e.gn_part, "psld_gemm_split_tail_f32: no GroupNorm partial sums on cut tiles (take the statistics in a pass of their own)");
-    DConvArgs d{};
-    d.x1 = a; d.x2 = nullptr; d.C1 = k; d.C2 = 0;
-    d.B = 1; d.H = 1; d.W = 1;
-    d.wfrag = reinterpret_cast<const u32x4*>(bfrag);
-    d.N = n; d.M = m;
-    d.chunks = cdiv(k, 64);             // stages of two 32-channel chunks; the odd chunk behind k is zeros on both sides
-    d.nseg = 1; d.rps = 1; d.pitch = d.W + 2;
-    d.zero = psld_detail_zero_page("psld_gemm_split_tail_f32");
-    if (!d.zero) return PSLD_ERR_LAUNCH;
-    const int ns = plan_split(d, e, y, ldy, aligned16(workspace) ? workspace : nullptr, ws_bytes);
-    PSLD_CHECK_ARG(d.v4, "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
-    const int st = launch_dconv<8, 2, true, 128, true>(d, ns, stream, "psld_gemm_split_tail_f32");
-    if (st != PSLD_OK) return st;
-    if (ns >= 2) return psld_detail_conv_reduce_epilogue(d.C, ns, m, n, y, ldy, e, stream);
-    return PSLD_OK;
+    const char* name = "psld_gemm_split_tail_f32";
+    DConvPlan p;
+    if (int st = pw_plan(p, name, true, psld_gemm_tail_supported(k, m, n), a, k, nullptr, 0, m, bfrag, n, y, ldy, epi,
+                         aligned16(workspace) ? workspace : nullptr, ws_bytes))
+        return st;
+    return dconv_finish(launch_dconv<8, 2, true, 128, true>(p.a, p.ns, stream, name), p, stream);
 }

@@ -540,16 +540,7 @@ template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAI
 int launch_wino8s(const WinoArgs& a, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)VBYTES / 3 * NL + 2 * (size_t)4 * 64 * 128;
     static_assert(LDS <= 163840, "LDS budget");
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>>(LDS, name)) return st;
     dim3 grid((unsigned)(cdiv(a.M, 128) * cdiv(a.N, 128) * (a.ksplit > 1 ? a.ksplit : 1)));
     hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>), grid, dim3(WINO_THREADS), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
@@ -611,7 +602,7 @@ extern "C" int psld_pack_conv3x3_wino(const float* w_oihw, void* ufrag, int cout
     PSLD_CHECK_ARG(n_out >= 128 && k_in > 0 && n_out % 32 == 0 && k_in % 32 == 0,
                    "psld_pack_conv3x3_wino: needs out channels %%32 (>= 128) and in channels %%32 (got %d, %d)", n_out, k_in);
     const long long items = (long long)(n_out / 16) * (k_in / 32) * 64;
-    const int blocks = (int)((items + 63) / 64 < 16384 ? (items + 63) / 64 : 16384);
+    const unsigned blocks = psld_grid_blocks(items, 64, 16384);
     if (dgrad) hipLaunchKernelGGL(wino_pack_kernel<3>, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag),
                                   n_out, k_in, 9LL, (long long)cin * 9, 1);
     else hipLaunchKernelGGL(wino_pack_kernel<3>, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag),
@@ -625,7 +616,7 @@ extern "C" int psld_pack_conv3x3_wino_x3(const float* w_oihw, void* ufrag, int c
     PSLD_CHECK_ARG(cout >= 128 && cin > 0 && cout % 32 == 0 && cin % 32 == 0,
                    "psld_pack_conv3x3_wino_x3: needs out channels %%32 (>= 128) and in channels %%32 (got %d, %d)", cout, cin);
     const long long items = (long long)(cout / 16) * (cin / 32) * 64;
-    const int blocks = (int)((items + 63) / 64 < 16384 ? (items + 63) / 64 : 16384);
+    const unsigned blocks = psld_grid_blocks(items, 64, 16384);
     hipLaunchKernelGGL(wino_pack_kernel<2>, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag), cout, cin,
                        (long long)cin * 9, 9LL, 0);
     PSLD_CHECK_LAUNCH("psld_pack_conv3x3_wino_x3");
@@ -634,8 +625,7 @@ extern "C" int psld_pack_conv3x3_wino_x3(const float* w_oihw, void* ufrag, int c
 
 extern "C" int psld_pack_wino_batch_x3(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
     PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_wino_batch_x3: bad args");
-    const long long want = (total_items + 63) / 64;
-    hipLaunchKernelGGL(wino_pack_batch_kernel<2>, dim3((unsigned)(want < 32768 ? want : 32768)), dim3(64), 0, stream,
+    hipLaunchKernelGGL(wino_pack_batch_kernel<2>, dim3(psld_grid_blocks(total_items, 64, 32768)), dim3(64), 0, stream,
                        table_dev, entries, total_items);
     PSLD_CHECK_LAUNCH("psld_pack_wino_batch_x3");
     return PSLD_OK;
@@ -643,8 +633,7 @@ extern "C" int psld_pack_wino_batch_x3(const long long* table_dev, int entries, 
 
 extern "C" int psld_pack_wino_batch(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
     PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_wino_batch: bad args");
-    const long long want = (total_items + 63) / 64;
-    hipLaunchKernelGGL(wino_pack_batch_kernel<3>, dim3((unsigned)(want < 32768 ? want : 32768)), dim3(64), 0, stream,
+    hipLaunchKernelGGL(wino_pack_batch_kernel<3>, dim3(psld_grid_blocks(total_items, 64, 32768)), dim3(64), 0, stream,
                        table_dev, entries, total_items);
     PSLD_CHECK_LAUNCH("psld_pack_wino_batch");
     return PSLD_OK;

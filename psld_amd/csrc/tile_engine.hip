@@ -705,16 +705,7 @@ int launch_fast_impl(const TileArgs& a, FastGeom fg, int nz, hipStream_t stream,
     constexpr int A_SZ = A_KC ? TBM * KC_LD : BK * MC_LD;
     constexpr int B_SZ = B_KC ? TBN * KC_LD : BK * MC_LD;
     constexpr size_t LDS = (size_t)NBUF * (A_SZ + B_SZ) * sizeof(float);
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_kernel_fast<AMODE, BMODE, TBM, NBUF, TBN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) {
-            psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    if (int st = psld_lds_once<&tile_kernel_fast<AMODE, BMODE, TBM, NBUF, TBN>>(LDS, name)) return st;
     const long long tiles = (long long)cdiv(a.M, TBM) * cdiv(a.N, TBN);
     PSLD_CHECK_ARG(tiles < (1LL << 31) && nz * a.nsplit <= 65535, "%s: grid too large", name);
     dim3 grid((unsigned)tiles, (unsigned)(nz * a.nsplit));
