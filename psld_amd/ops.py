@@ -105,6 +105,15 @@ def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, out: Optional[Te
     return out
 
 
+def _small_grid_ws(rows: int, limit: int, nbytes, device):
+    """The (ws, wsb) pair of a launch that may split K to fill the chip: the stream's workspace of ``nbytes()`` bytes when the
+    grid is small (at most ``limit`` output rows - only those ever split: psld_conv2d_nhwc_ws_f32), else no workspace."""
+    if rows > limit:
+        return None, 0
+    wsb = nbytes()
+    return workspace(wsb, device).data_ptr(), wsb
+
+
 def gemm_tn_splitk(M: int, N: int, K: int, A: Tensor, lda: int, B: Tensor, ldb: int, slabs: Tensor, nsplit: int):
     check(lib().psld_gemm_tn_splitk_f32(M, N, K, A.data_ptr(), lda, B.data_ptr(), ldb, slabs.data_ptr(), nsplit,
                                         _stream()), "psld_gemm_tn_splitk_f32")
@@ -114,10 +123,7 @@ def conv2d_nhwc(x1: Tensor, x2: Optional[Tensor], w_ohwi: Tensor, cout: int, kh:
                 tstride: int, oh: int, ow: int, y: Tensor, epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
     b, ih, iw, c1 = x1.shape
     c2 = x2.shape[-1] if x2 is not None else 0
-    ws, wsb = None, 0
-    if b * oh * ow <= 16384:     # only small grids ever split K (see psld_conv2d_nhwc_ws_f32)
-        wsb = lib().psld_conv2d_workspace_bytes(b, oh, ow, cout)
-        ws = workspace(wsb, x1.device).data_ptr()
+    ws, wsb = _small_grid_ws(b * oh * ow, 16384, lambda: lib().psld_conv2d_workspace_bytes(b, oh, ow, cout), x1.device)
     check(lib().psld_conv2d_nhwc_ws_f32(x1.data_ptr(), c1, _p(x2), c2, b, ih, iw, w_ohwi.data_ptr(), cout, kh, kw,
                                         stride, pad, tstride, oh, ow, y.data_ptr(), ldy if ldy is not None else cout,
                                         C.byref(epi) if epi is not None else None, ws, wsb, _stream()),
@@ -170,10 +176,7 @@ def conv3x3_split(x1: Tensor, x2: Optional[Tensor], wfrag: Tensor, cout: int, y:
                   epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
     b, h, w, c1 = x1.shape
     c2 = x2.shape[-1] if x2 is not None else 0
-    ws, wsb = None, 0
-    if b * h * w <= 32768:
-        wsb = lib().psld_conv2d_workspace_bytes(b, h, w, cout)
-        ws = workspace(wsb, x1.device).data_ptr()
+    ws, wsb = _small_grid_ws(b * h * w, 32768, lambda: lib().psld_conv2d_workspace_bytes(b, h, w, cout), x1.device)
     if isinstance(x1, LimbPlanes):       # pre-split input(s): the LDS-DMA kernel
         assert x2 is None or isinstance(x2, LimbPlanes)
         check(lib().psld_conv3x3_limb_f32(x1.data_ptr(), c1, x2.data_ptr() if x2 is not None else None, c2, b, h, w,
@@ -233,31 +236,37 @@ def pack_wino_batch_x3(table: Tensor, entries: int, total_items: int):
     check(lib().psld_pack_wino_batch_x3(table.data_ptr(), entries, total_items, _stream()), "psld_pack_wino_batch_x3")
 
 
-def conv3x3_wino_x3(x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: Tensor,
-                    epi: Optional[Epilogue] = None, ldy: Optional[int] = None, allow_split: bool = False):
-    """conv3x3_wino on two-limb fragments (conv3x3_wino_frag_x3): V and U keep two limbs, three products each."""
+def _wino(name: str, ws_name: Optional[str], x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: Tensor, epi, ldy,
+          allow_split: bool, gn=None):
+    """One Winograd forward launch: entry point ``name`` - or, when ``allow_split`` finds the grid small enough for a split-chunk
+    workspace, ``ws_name`` (None: ``name`` itself takes the (ws, wsb) pair).  ``gn`` = (st1, st2, act): the fused GroupNorm's."""
     b, h, w, c1 = x1.shape
     c2 = x2.shape[-1] if x2 is not None else 0
     wsb = conv3x3_wino_ws_bytes(c1, c2, b, h, w, cout) if allow_split else 0
-    ws = workspace(wsb, x1.device).data_ptr() if wsb else None
-    check(lib().psld_conv3x3_wino_x3_f32(x1.data_ptr(), c1, _p(x2), c2, b, h, w, ufrag.data_ptr(), cout, y.data_ptr(),
-                                         ldy if ldy is not None else cout, C.byref(epi) if epi is not None else None,
-                                         ws, wsb, _stream()), "psld_conv3x3_wino_x3_f32")
+    args = [x1.data_ptr(), c1, _p(x2), c2]
+    if gn is not None:
+        st1, st2, act = gn
+        args = [x1.data_ptr(), c1, st1.scale.data_ptr(), st1.shift.data_ptr(), _p(x2), c2,
+                st2.scale.data_ptr() if st2 is not None else None, st2.shift.data_ptr() if st2 is not None else None,
+                1 if act else 0]
+    args += [b, h, w, ufrag.data_ptr(), cout, y.data_ptr(), ldy if ldy is not None else cout,
+             C.byref(epi) if epi is not None else None]
+    if wsb or ws_name is None:
+        name = ws_name or name
+        args += [workspace(wsb, x1.device).data_ptr() if wsb else None, wsb]
+    check(getattr(lib(), name)(*args, _stream()), name)
+
+
+def conv3x3_wino_x3(x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: Tensor,
+                    epi: Optional[Epilogue] = None, ldy: Optional[int] = None, allow_split: bool = False):
+    """conv3x3_wino on two-limb fragments (conv3x3_wino_frag_x3): V and U keep two limbs, three products each."""
+    _wino("psld_conv3x3_wino_x3_f32", None, x1, x2, ufrag, cout, y, epi, ldy, allow_split)
 
 
 def conv3x3_wino_gn_x3(x1: Tensor, st1: "GNStats", x2: Optional[Tensor], st2: Optional["GNStats"], act: bool, ufrag: Tensor,
                        cout: int, y: Tensor, epi: Optional[Epilogue] = None, allow_split: bool = False):
     """conv3x3_wino_gn on two-limb fragments (conv3x3_wino_frag_x3)."""
-    b, h, w, c1 = x1.shape
-    c2 = x2.shape[-1] if x2 is not None else 0
-    wsb = conv3x3_wino_ws_bytes(c1, c2, b, h, w, cout) if allow_split else 0
-    ws = workspace(wsb, x1.device).data_ptr() if wsb else None
-    check(lib().psld_conv3x3_wino_gn_x3_f32(x1.data_ptr(), c1, st1.scale.data_ptr(), st1.shift.data_ptr(), _p(x2), c2,
-                                            st2.scale.data_ptr() if st2 is not None else None,
-                                            st2.shift.data_ptr() if st2 is not None else None, 1 if act else 0, b, h, w,
-                                            ufrag.data_ptr(), cout, y.data_ptr(), y.shape[-1],
-                                            C.byref(epi) if epi is not None else None, ws, wsb, _stream()),
-          "psld_conv3x3_wino_gn_x3_f32")
+    _wino("psld_conv3x3_wino_gn_x3_f32", None, x1, x2, ufrag, cout, y, epi, y.shape[-1], allow_split, (st1, st2, act))
 
 
 _WINO_MODE = None     # 0: never, 1: where it pays (default), 2: wherever the kernel takes the shape (tests)
@@ -328,24 +337,8 @@ def conv3x3_wino_gn(x1: Tensor, st1: "GNStats", x2: Optional[Tensor], st2: Optio
     """conv3x3_wino applied to act(GroupNorm(x)) with the apply pass inside the kernel's input staging: x1 / x2 are the
     raw tensors, st1 / st2 their statistics (gn_stats / gn_stats_from_part).  Inference forward only (no dropout, the
     activated tensor is not kept)."""
-    b, h, w, c1 = x1.shape
-    c2 = x2.shape[-1] if x2 is not None else 0
-    wsb = conv3x3_wino_ws_bytes(c1, c2, b, h, w, cout) if allow_split else 0
-    if wsb:       # a small grid: channel chunks split like conv3x3_wino(allow_split=True)
-        ws = workspace(wsb, x1.device)
-        check(lib().psld_conv3x3_wino_gn_ws_f32(x1.data_ptr(), c1, st1.scale.data_ptr(), st1.shift.data_ptr(), _p(x2), c2,
-                                                st2.scale.data_ptr() if st2 is not None else None,
-                                                st2.shift.data_ptr() if st2 is not None else None, 1 if act else 0, b, h, w,
-                                                ufrag.data_ptr(), cout, y.data_ptr(), y.shape[-1],
-                                                C.byref(epi) if epi is not None else None, ws.data_ptr(), wsb, _stream()),
-              "psld_conv3x3_wino_gn_ws_f32")
-        return
-    check(lib().psld_conv3x3_wino_gn_f32(x1.data_ptr(), c1, st1.scale.data_ptr(), st1.shift.data_ptr(), _p(x2), c2,
-                                         st2.scale.data_ptr() if st2 is not None else None,
-                                         st2.shift.data_ptr() if st2 is not None else None, 1 if act else 0, b, h, w,
-                                         ufrag.data_ptr(), cout, y.data_ptr(), y.shape[-1],
-                                         C.byref(epi) if epi is not None else None, _stream()),
-          "psld_conv3x3_wino_gn_f32")
+    _wino("psld_conv3x3_wino_gn_f32", "psld_conv3x3_wino_gn_ws_f32", x1, x2, ufrag, cout, y, epi, y.shape[-1], allow_split,
+          (st1, st2, act))
 
 
 def conv3x3_wino(x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: Tensor,
@@ -353,21 +346,9 @@ def conv3x3_wino(x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: 
     """conv3x3_split in Winograd F(2x2, 3x3) form (fp32 NHWC input(s), fragments of conv3x3_wino_frag).  ``allow_split``: a launch
     whose grid leaves CUs idle may split its channel chunks over workgroups (another summation order than the unsplit launch;
     the executor always asks for it - conv3x3_wino_gn splits the same way, so the fused and unfused inference forwards stay
-    bitwise equal)."""
-    b, h, w, c1 = x1.shape
-    c2 = x2.shape[-1] if x2 is not None else 0
-    wsb = conv3x3_wino_ws_bytes(c1, c2, b, h, w, cout) if allow_split else 0
-    if wsb:
-        # a small grid (the 8x8 level at training batches): channel chunks split over workgroups, one reduction + epilogue pass
-        # (which also forms the GroupNorm partial sums an epilogue asks for)
-        ws = workspace(wsb, x1.device)
-        check(lib().psld_conv3x3_wino_ws_f32(x1.data_ptr(), c1, _p(x2), c2, b, h, w, ufrag.data_ptr(), cout, y.data_ptr(),
-                                             ldy if ldy is not None else cout, C.byref(epi) if epi is not None else None,
-                                             ws.data_ptr(), wsb, _stream()), "psld_conv3x3_wino_ws_f32")
-        return
-    check(lib().psld_conv3x3_wino_f32(x1.data_ptr(), c1, _p(x2), c2, b, h, w, ufrag.data_ptr(), cout, y.data_ptr(),
-                                      ldy if ldy is not None else cout, C.byref(epi) if epi is not None else None,
-                                      _stream()), "psld_conv3x3_wino_f32")
+    bitwise equal): a small grid (the 8x8 level at training batches) then runs one reduction + epilogue pass, which also
+    forms the GroupNorm partial sums an epilogue asks for."""
+    _wino("psld_conv3x3_wino_f32", "psld_conv3x3_wino_ws_f32", x1, x2, ufrag, cout, y, epi, ldy, allow_split)
 
 
 @functools.lru_cache(maxsize=None)
@@ -435,10 +416,7 @@ def gemm_split(a1: Tensor, a2: Optional[Tensor], m: int, bfrag: Tensor, n: int, 
     """y[m][n] = epilogue(concat(a1, a2) @ B^T) on the bf16 limb kernels; a1 / a2 are [m][k1] / [m][k2] contiguous."""
     k1 = a1.shape[-1]
     k2 = a2.shape[-1] if a2 is not None else 0
-    ws, wsb = None, 0
-    if m <= 32768:
-        wsb = 8 * m * n * 4
-        ws = workspace(wsb, a1.device).data_ptr()
+    ws, wsb = _small_grid_ws(m, 32768, lambda: 8 * m * n * 4, a1.device)
     check(lib().psld_gemm_split_f32(a1.data_ptr(), k1, _p(a2), k2, m, bfrag.data_ptr(), n, y.data_ptr(),
                                     ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
                                     ws, wsb, _stream()), "psld_gemm_split_f32")
@@ -539,10 +517,7 @@ def gemm_split_tail(a: Tensor, m: int, bfrag: Tensor, n: int, y: Tensor, epi: Op
     """y[m][n] = epilogue(a @ B^T) for the shapes gemm_tail_supported takes (fragments: gemm_frag_tail); gemm_split's
     workspace policy (``allow_split`` False: never a K split)."""
     k = a.shape[-1]
-    ws, wsb = None, 0
-    if allow_split and m <= 32768:
-        wsb = 8 * m * n * 4
-        ws = workspace(wsb, a.device).data_ptr()
+    ws, wsb = _small_grid_ws(m, 32768 if allow_split else 0, lambda: 8 * m * n * 4, a.device)
     check(lib().psld_gemm_split_tail_f32(a.data_ptr(), k, m, bfrag.data_ptr(), n, y.data_ptr(),
                                          ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
                                          ws, wsb, _stream()), "psld_gemm_split_tail_f32")

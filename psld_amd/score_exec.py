@@ -1,6 +1,6 @@
 """The NCSN++ forward as a program of libpsld_hip launches over NHWC tensors (and, when recording, the closures of its
 backward): time embedding, residual blocks, attention, input pyramid, concatenations, stem and head.  Kernel-level helpers
-and the tape machinery come from score_tape.py; which kernel runs each 3x3 convolution from score_routes.py."""
+and the tape machinery come from score_tape.py; which kernel runs each 3x3 convolution and pointwise GEMM from score_routes.py."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -11,9 +11,8 @@ import torch.nn as nn
 from . import ops
 from . import score_routes as R
 from .score_modules import NIN, AttnBlockpp, Downsample, ResnetBlockBigGANpp
-from .score_routes import _pick_nsplit
 from .score_tape import _CatNode, _ExecBase, _Node, _fir_kernel, _gbuf
-from .score_weights import _built_entry
+from .score_weights import PointwiseWeight
 
 Tensor = torch.Tensor
 _OVERLAP_MAX_PIXELS = 65536     # batch x H x W at the input resolution up to which weight gradients go to a side stream
@@ -117,6 +116,7 @@ class _Exec(_ExecBase):
         xb: Optional[_Node] = None
         if isinstance(x, _CatNode):
             x, xb = x.a, x.b
+        xb_v = xb.v if xb is not None else None
         first_x = self.use(x)
         first_xb = self.use(xb) if xb is not None else False
         b, h, w, c1 = x.v.shape
@@ -141,7 +141,7 @@ class _Exec(_ExecBase):
         # run inside the Winograd convolution's input staging where that pays - the activated tensor is needed nowhere else.
         ho, wo = (h // 2, w // 2) if down else ((h * 2, w * 2) if up else (h, w))
         plan = R.block_plan(self.split, self.limb_planes, self.record, self.drop_p > 0, c1, cin - c1, b, h, w, cout, up, down,
-                            self.wino_wanted)
+                            self.wino_wanted, mod.has_shortcut)
         fuse0, fuse1 = plan.conv0 == R.WINO_GN, plan.conv1 == R.WINO_GN
         apply0 = ops.gn_apply_limb if plan.lp0 else ops.gn_apply
         a0 = None
@@ -168,7 +168,7 @@ class _Exec(_ExecBase):
         h1p = ops.gn_part_buffer(b, ho * wo, cout, h1.device) if plan.part0 else None
         epi0 = ops.epilogue(bias=mod.Conv_0.bias, rowbias=tp, rows_per_img=ho * wo, ld_rowbias=tp_ld, gn_part=h1p, gn_hw=ho * wo)
         if fuse0:
-            self.conv3_gn(x.v, st0, xb.v if xb is not None else None, st0b, mod.Conv_0, h1, epi0)
+            self.conv3_gn(x.v, st0, xb_v, st0b, mod.Conv_0, h1, epi0)
         else:
             self.conv3(a0r, mod.Conv_0, h1, epi0, x2=a0b, route=plan.conv0)
         st1 = self.node_stats(_Node(h1, h1p), gn1.weight, gn1.bias)
@@ -182,15 +182,8 @@ class _Exec(_ExecBase):
             (ops.gn_apply_limb if plan.lp1 else ops.gn_apply)(h1, st1, True, drop_p=drop_p, seed=seed, seed_dev=seed_dev)
         out = torch.empty((b, ho, wo, cout), device=x.v.device, dtype=torch.float32)
         if mod.has_shortcut:
-            c2 = mod.Conv_2
-            sc_route = R.pointwise_route(self.split, c1, cin - c1, b * ho * wo, cout)
-            if sc_route != R.TILE:
-                self.gemm_fwd(xr, xb.v if xb is not None else None, b * ho * wo, cout, out, ops.epilogue(bias=c2.bias),
-                              lambda: net._pfrag(c2.weight, "fwd", cout, cin, cin, 1),
-                              lambda: net._pfrag(c2.weight, "fwd_x3", cout, cin, cin, 1), route=sc_route)
-            else:
-                ops.conv2d_nhwc(xr, xb.v if xb is not None else None, c2.weight, cout, 1, 1, 1, 0, 1, ho, wo, out,
-                                ops.epilogue(bias=c2.bias))
+            w2 = PointwiseWeight(net, mod.Conv_2.weight, cout, cin, "oi")
+            self.pw_fwd(plan.shortcut, xr, xb_v, b * ho * wo, w2, out, ops.epilogue(bias=mod.Conv_2.bias))
             res = out
         else:
             res = xr
@@ -206,7 +199,6 @@ class _Exec(_ExecBase):
         temb_act = self.temb_act
         dtp_all = self.dtp_all
         xr_saved = xr if mod.has_shortcut else None
-        xb_v = xb.v if xb is not None else None
 
         def bwd():
             dout = on.g
@@ -284,7 +276,7 @@ class _Exec(_ExecBase):
 
             self.on_side(side0, dh1, a0r, a0b)
             if xb is not None:
-                self._resblock_cat_bwd(mod, x, xb, dout, dh1, st0, st0b, g1, g2, first_x, first_xb, plan.dgrad0)
+                self._resblock_cat_bwd(mod, w2, x, xb, dout, dh1, st0, st0b, g1, g2, first_x, first_xb, plan.dgrad0)
                 return
             da0r = torch.empty((b, ho, wo, cin), device=dout.device, dtype=torch.float32)
             self.dgrad(dh1, mod.Conv_0, 3, 1, 1, ho, wo, da0r, route=plan.dgrad0[0])
@@ -292,23 +284,13 @@ class _Exec(_ExecBase):
             xg, acc = _gbuf(x)
             identity = False
             if mod.has_shortcut:
-                c2 = mod.Conv_2
-                m = b * ho * wo
-                def shortcut_dgrad(dst, epi):
-                    route = R.pointwise_route(self.split, cout, 0, m, cin)
-                    if route != R.TILE:
-                        fr = net._pfrag(c2.weight, "dgrad", cin, cout, 1, cin)
-                        self.gemm_limb(route, dout, m, fr, cin, dst, epi)
-                    else:
-                        ops.gemm_raw(0, 0, m, cin, cout, dout, cout, 0, c2.weight, cin, 0, dst, cin, 0, epi=epi)
-
                 if up or down:
                     dxr = torch.empty((b, ho, wo, cin), device=dout.device, dtype=torch.float32)
-                    shortcut_dgrad(dxr, ops.epilogue(alpha=s))
+                    self.pw_dgrad(plan.shortcut_dgrad, dout, b * ho * wo, w2, dxr, ops.epilogue(alpha=s))
                     self.resample_bwd(dxr, up, (h, w), xg, acc)
                     del dxr
                 else:
-                    shortcut_dgrad(xg, ops.epilogue(alpha=s, accumulate=acc))
+                    self.pw_dgrad(plan.shortcut_dgrad, dout, b * ho * wo, w2, xg, ops.epilogue(alpha=s, accumulate=acc))
             else:
                 identity = True          # out = (x + h)/sqrt(2): the x branch's gradient s*dout rides on GroupNorm_0's backward
             if up or down:
@@ -324,15 +306,16 @@ class _Exec(_ExecBase):
         self.push(bwd, mod)
         return on
 
-    def _resblock_cat_bwd(self, mod, xa: _Node, xb: _Node, dout: Tensor, dh1: Tensor, sta, stb, g1: int, g2: int,
-                          first_a: bool, first_b: bool, routes):
+    def _resblock_cat_bwd(self, mod, w2: PointwiseWeight, xa: _Node, xb: _Node, dout: Tensor, dh1: Tensor, sta, stb, g1: int,
+                          g2: int, first_a: bool, first_b: bool, routes):
         """Input side of the backward of a residual block fed by an unmaterialised concatenation: the data gradients
         of Conv_0 and of the 1x1 shortcut are computed per source (the fragments of a data gradient are ordered by
         output-channel tile, so each source's share is a contiguous slice) and GroupNorm_0's backward runs per source
-        over its groups; everything accumulates straight into the two sources' gradient buffers.  ``routes``: the plan's
-        per-source routes of Conv_0's data gradient (both Winograd or both direct: one fragment buffer is sliced)."""
+        over its groups; everything accumulates straight into the two sources' gradient buffers.  ``w2``: the shortcut's
+        weight (score_routes.cat_ok: its data gradient runs on the full-tile limb kernels); ``routes``: the plan's per-source
+        routes of Conv_0's data gradient (both Winograd or both direct: one fragment buffer is sliced)."""
         net, s = self.net, self.s
-        gn0, c2 = mod.GroupNorm_0, mod.Conv_2
+        gn0 = mod.GroupNorm_0
         b, h, w, cout = dout.shape
         m = b * h * w
         c1 = xa.v.shape[-1]
@@ -340,15 +323,14 @@ class _Exec(_ExecBase):
         wino = routes[0] == R.WINO
         # [cin/128 tiles][...]: data gradient of the 3x3 (Winograd fragments carry read-ahead padding at the end)
         f3 = net._wfrag(mod.Conv_0, True) if wino else net._frag(mod.Conv_0, True)
-        f1 = net._pfrag(c2.weight, "dgrad", cin, cout, 1, cin)  # same for the shortcut
-        cut3, cut1 = (f3.numel() - (R.WINO_FRAG_PAD_BYTES if wino else 0)) * c1 // cin, f1.numel() * c1 // cin
+        cut3 = (f3.numel() - (R.WINO_FRAG_PAD_BYTES if wino else 0)) * c1 // cin
         gam, bet = gn0.weight.detach(), gn0.bias.detach()
         dgam, dbet = self.g(gn0.weight), self.g(gn0.bias)
-        for node, lo, hi, fr3, fr1, st, g, first, route in ((xa, 0, c1, f3[:cut3], f1[:cut1], sta, g1, first_a, routes[0]),
-                                                           (xb, c1, cin, f3[cut3:], f1[cut1:], stb, g2, first_b, routes[1])):
+        for node, lo, hi, fr3, st, g, first, route in ((xa, 0, c1, f3[:cut3], sta, g1, first_a, routes[0]),
+                                                      (xb, c1, cin, f3[cut3:], stb, g2, first_b, routes[1])):
             c = hi - lo
             xg, acc = _gbuf(node)
-            ops.gemm_split(dout, None, m, fr1, c, xg, ops.epilogue(alpha=s, accumulate=acc))
+            self.pw_dgrad(R.LIMB, dout, m, w2, xg, ops.epilogue(alpha=s, accumulate=acc), cols=(lo, hi))
             da0 = torch.empty_like(node.v)
             if route == R.WINO:
                 ops.conv3x3_wino(dh1, None, fr3, c, da0, allow_split=True)
@@ -370,27 +352,21 @@ class _Exec(_ExecBase):
         hn = ops.gn_apply(x.v, st, False)
         n0, n1, n2, n3 = mod.NIN_0, mod.NIN_1, mod.NIN_2, mod.NIN_3
         scale = float(int(c) ** (-0.5))
-        # limb kernels: q|k|v come from ONE GEMM against the concatenated projections (N = 3c) into one buffer
-        # (c -> c, c -> 3c and 3c -> c take the same route: 3c is a multiple of 128 exactly when c is)
-        route = R.pointwise_route(self.split, c, 0, m, c)
-        fused = route != R.TILE
-        net = self.net
-        if fused:
-            assert R.pointwise_route(self.split, c, 0, m, 3 * c) == route == R.pointwise_route(self.split, 3 * c, 0, m, c)
-            f_qkv, f_qkv_d, b_qkv = net._qkv_frags(mod)
+        plan = R.attn_plan(self.split, c, m)
+        # (weight, output) of the projections of hn.  Limb kernels: q|k|v come from ONE GEMM against the concatenated
+        # projections (N = 3c) into one buffer; tile engine: one GEMM and one buffer each
+        if plan.fused:
+            wq = PointwiseWeight(self.net, mod, 3 * c, c, "qkv", self.net._qkv_frags(mod))
             qkv = torch.empty((b, hw, 3 * c), device=dev, dtype=torch.float32)
-            self.gemm_fwd(hn, None, m, 3 * c, qkv, ops.epilogue(bias=b_qkv), lambda: f_qkv, lambda: net._qkv_frags_x3(mod),
-                          route=route)
+            proj = [(wq, qkv, wq.qkv[2])]
             q, k, v = qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:]
-            ld = 3 * c
         else:
-            qkv = []
-            for nin in (n0, n1, n2):
-                y = torch.empty((b, hw, c), device=dev, dtype=torch.float32)
-                ops.gemm_raw(0, 0, m, c, c, hn, c, 0, nin.W, c, 0, y, c, 0, epi=ops.epilogue(bias=nin.b))
-                qkv.append(y)
-            q, k, v = qkv
-            ld = c
+            proj = [(PointwiseWeight(self.net, nin.W, c, c, "io"), torch.empty((b, hw, c), device=dev, dtype=torch.float32), nin.b)
+                    for nin in (n0, n1, n2)]
+            q, k, v = (y for _, y, _ in proj)
+        ld = q.stride(-2)       # 3c or c
+        for wp, y, bias in proj:
+            self.pw_fwd(plan.route, hn, None, m, wp, y, ops.epilogue(bias=bias))
         ho = torch.empty((b, hw, c), device=dev, dtype=torch.float32)
         if self.split and self.fused_attn and ops.attn_fwd_supported(hw, c):
             # QK^T -> softmax -> PV in ONE kernel: the [B, HW, HW] scores never reach HBM; the probabilities are written
@@ -403,29 +379,17 @@ class _Exec(_ExecBase):
             ops.softmax_rows(p, p, b * hw, hw)
             self.bmm(0, 0, hw, c, hw, p, hw, hw * hw, v, ld, hw * ld, ho, c, hw * c, b)
         out = torch.empty_like(x.v)
-        outp = self.part_for(b, hw, c, dev, route == R.LIMB)       # (the tail launch leaves no GroupNorm partial sums)
+        outp = self.part_for(b, hw, c, dev, plan.route == R.LIMB)       # (the tail launch leaves no GroupNorm partial sums)
         epi_out = ops.epilogue(bias=n3.b, residual=x.v, ld_residual=c, out_scale=s, gn_part=outp, gn_hw=hw)
-        if fused:
-            self.gemm_fwd(ho, None, m, c, out, epi_out, lambda: net._pfrag(n3.W, "fwd", c, c, 1, c),
-                          lambda: net._pfrag(n3.W, "fwd_x3", c, c, 1, c), route=route)
-        else:
-            ops.gemm_raw(0, 0, m, c, c, ho, c, 0, n3.W, c, 0, out, c, 0, epi=epi_out)
+        w3 = PointwiseWeight(self.net, n3.W, c, c, "io")
+        self.pw_fwd(plan.route, ho, None, m, w3, out, epi_out)
         on = _Node(out, outp, want_gsum=True)       # NIN_3.b = s * column sums of its gradient
         if not self.record:
             return on
 
         def nin_wgrad(a_in: Tensor, dy: Tensor, nin: NIN, alpha: float, ldd: int, bias: bool = True):
             # dW[in,out] = a_in^T dy  (K = B*HW -> split-K slabs); dy may be a column slice (row stride ldd)
-            wroute = R.pointwise_wgrad_route(self.split, c, c, 0, m)
-            if wroute != R.TILE:
-                nsplit = R._tn_split(c, c, m)
-                slabs = self.slabs_for(4 * c * c * nsplit, dev)
-                (ops.gemm_tn_split_tail if wroute == R.LIMB_TAIL else ops.gemm_tn_split)(c, c, m, a_in, c, dy, ldd, slabs, c, nsplit)
-            else:
-                nsplit = _pick_nsplit(((c + 127) // 128) ** 2, m)
-                slabs = self.slabs_for(4 * c * c * nsplit, dev)
-                ops.gemm_tn_splitk(c, c, m, a_in, c, dy, ldd, slabs, nsplit)
-            self.reduce_slabs(slabs, nsplit, c * c, self.g(nin.W), alpha=alpha)
+            self.pw_wgrad(plan.wgrad, c, c, m, a_in, c, dy, ldd, (self.g(nin.W),), alpha)
             if bias:
                 self.bias_grad(dy.view(b, hw, 1, c) if ldd == c else dy, self.g(nin.b), alpha=alpha, ld=ldd)
 
@@ -435,19 +399,13 @@ class _Exec(_ExecBase):
             have_b3 = self.bias_from(on, dout, n3.b, s)
             self.on_side(lambda: nin_wgrad(ho, dout, n3, s, c, bias=not have_b3), ho, dout)
             dho = torch.empty_like(ho)
-            if fused:
-                f_od = net._pfrag(n3.W, "dgrad", c, c, c, 1)
-                self.gemm_limb(route, dout, m, f_od, c, dho, ops.epilogue(alpha=s))
-            else:
-                ops.gemm_raw(0, 1, m, c, c, dout, c, 0, n3.W, c, 0, dho, c, 0, epi=ops.epilogue(alpha=s))
+            self.pw_dgrad(plan.route, dout, m, w3, dho, ops.epilogue(alpha=s))
             # dP = dho v^T ; dv = P^T dho
             dp = torch.empty_like(p)
             self.bmm(0, 1, hw, hw, c, dho, c, hw * c, v, ld, hw * ld, dp, hw, hw * hw, b)
-            if fused:
-                dqkv = torch.empty_like(qkv)
-                dq, dk, dv = dqkv[..., :c], dqkv[..., c:2 * c], dqkv[..., 2 * c:]
-            else:
-                dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+            dproj = [torch.empty_like(y) for _, y, _ in proj]
+            dqkv = dproj[0]             # (the [m][3c] buffer, where there is one)
+            dq, dk, dv = (dqkv[..., :c], dqkv[..., c:2 * c], dqkv[..., 2 * c:]) if plan.fused else dproj
             self.bmm(1, 0, hw, c, hw, p, hw, hw * hw, dho, c, hw * c, dv, ld, hw * ld, b)
             ds = dp
             ops.softmax_rows_bwd(p, dp, ds, b * hw, hw)
@@ -455,38 +413,22 @@ class _Exec(_ExecBase):
             self.bmm(1, 0, hw, c, hw, ds, hw, hw * hw, q, ld, hw * ld, dk, ld, hw * ld, b, scale)
             dhn = torch.empty_like(hn)
             # q / k / v bias gradients: ONE column-sum pass over the [m, 3c] gradient buffer, written to the three parameters
-            seg = fused and 3 * c <= 1024
+            seg = plan.fused and 3 * c <= 1024
             if seg:
                 self.on_side(lambda: ops.bias_grad_seg(dqkv, 3 * c, b, hw, (self.g(n0.b), self.g(n1.b), self.g(n2.b)), c), dqkv)
             # ... and their weight gradients from ONE GEMM hn^T [dq | dk | dv] (N = 3c: hn is staged and split once instead
             # of three times); the batched slab reduction cuts the [c][3c] result into the three parameters
-            qkv_wroute = R.pointwise_wgrad_route(self.split, c, 3 * c, 0, m)
-            one_gemm = fused and self.defer and qkv_wroute != R.TILE and ops.slab_units(c * c, 2, c, 3 * c) > 0
-
-            def qkv_wgrad():
-                nsplit = R._tn_split(c, 3 * c, m)
-                slabs = self.slabs_for(4 * 3 * c * c * nsplit, dev).view(torch.float32)
-                (ops.gemm_tn_split_tail if qkv_wroute == R.LIMB_TAIL else ops.gemm_tn_split)(
-                    c, 3 * c, m, hn, c, dqkv, 3 * c, slabs, 3 * c, nsplit)
-                for i, nin in enumerate((n0, n1, n2)):
-                    self.reduce_slabs(slabs[i * c:], nsplit, c * c, self.g(nin.W), layout=2, taps=c, cin=3 * c, more=i < 2)
-
-            if one_gemm:
-                self.on_side(qkv_wgrad, hn, dqkv)
+            if plan.qkv_one and self.defer:
+                self.on_side(lambda: self.pw_wgrad(plan.qkv_wgrad, c, 3 * c, m, hn, c, dqkv, 3 * c,
+                                                   (self.g(n0.W), self.g(n1.W), self.g(n2.W))), hn, dqkv)
                 if not seg:
                     for nin, d in ((n0, dq), (n1, dk), (n2, dv)):
                         self.on_side(lambda nin=nin, d=d: self.bias_grad(d, self.g(nin.b), ld=ld), d)
             else:
                 for nin, d in ((n0, dq), (n1, dk), (n2, dv)):
                     self.on_side(lambda nin=nin, d=d: nin_wgrad(hn, d, nin, 1.0, ld, bias=not seg), hn, d)
-            if fused:
-                self.gemm_limb(route, dqkv, m, f_qkv_d, c, dhn)
-            else:
-                first = True
-                for nin, d in ((n0, dq), (n1, dk), (n2, dv)):
-                    ops.gemm_raw(0, 1, m, c, c, d, c, 0, nin.W, c, 0, dhn, c, 0,
-                                 epi=None if first else ops.epilogue(accumulate=True))
-                    first = False
+            for i, ((wp, _, _), d) in enumerate(zip(proj, dproj)):     # (three accumulating launches on the tile engine)
+                self.pw_dgrad(plan.route, d, m, wp, dhn, ops.epilogue(accumulate=True) if i else None)
             xg, acc = _gbuf(x)
             self.gn_backward(dhn, x.v, st, gn.weight, gn.bias, self.g(gn.weight), self.g(gn.bias), False, xg,
                              accumulate_dx=acc, add=dout, add_scale=s, last_writer_of=x if first_x else None)
@@ -516,25 +458,16 @@ class _Exec(_ExecBase):
         oh, ow = (fh - 3) // 2 + 1, (fw - 3) // 2 + 1
         out = torch.empty((b, oh, ow, cout), device=xf.device, dtype=torch.float32)
         epi = ops.epilogue(bias=conv.bias, residual=h.v, ld_residual=cout, out_scale=s)
-        small = cin * 9 <= 64 and cout % 4 == 0
         cols = None
-        net = self.net
         m = b * oh * ow
         # many-channel levels on the limb kernels: explicit im2col (K order = the packed OHWI weights') + pointwise GEMM
-        r_fwd, r_bwd = R.pointwise_route(self.split, 9 * cin, 0, m, cout), R.pointwise_route(self.split, cout, 0, m, 9 * cin)
-        limb = not small and cin % 4 == 0 and r_fwd != R.TILE and r_bwd != R.TILE
-        pack = ops.gemm_frag_tail if r_fwd == R.LIMB_TAIL else ops.gemm_frag
-        pack_d = ops.gemm_frag_tail if r_bwd == R.LIMB_TAIL else ops.gemm_frag
+        small, limb, r_fwd, r_bwd = R.pyramid_plan(self.split, cin, cout, m)
+        wp = PointwiseWeight(self.net, conv, cout, 9 * cin, "ohwi")
         if small:
             cols = self.small_in_conv(xf, conv, 2, 0, oh, ow, out, epi)
         elif limb:
             patches = ops.im2col3x3(xf, 2, 0, oh, ow)
-            self.gemm_fwd(patches, None, m, cout, out, epi,
-                          lambda: net._wcache.get(conv.weight, "s2fwd", _built_entry,
-                                                  lambda prev: pack(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev)),
-                          lambda: net._wcache.get(conv.weight, "s2fwd_x3", _built_entry,
-                                                  lambda prev: ops.gemm_frag_x3(net._packed(conv), cout, 9 * cin, 9 * cin, 1, prev)),
-                          route=r_fwd)
+            self.pw_fwd(r_fwd, patches, None, m, wp, out, epi)
             del patches
         else:
             ops.conv2d_nhwc(xf, None, self.net._packed(conv), cout, 3, 3, 2, 0, 1, oh, ow, out, epi)
@@ -560,11 +493,8 @@ class _Exec(_ExecBase):
             if not first:
                 dxf = torch.empty_like(xf)
                 if limb:
-                    frd = net._wcache.get(
-                        conv.weight, "s2dgrad", _built_entry,
-                        lambda prev: pack_d(net._packed(conv), 9 * cin, cout, 1, 9 * cin, prev))
                     dpatches = torch.empty((m, 9 * cin), device=dout.device, dtype=torch.float32)
-                    self.gemm_limb(r_bwd, dout, m, frd, 9 * cin, dpatches, ops.epilogue(alpha=s))
+                    self.pw_dgrad(r_bwd, dout, m, wp, dpatches, ops.epilogue(alpha=s))
                     ops.col2im3x3(dpatches, xf.shape, 2, 0, oh, ow, out=dxf)
                     del dpatches
                 else:

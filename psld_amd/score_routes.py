@@ -1,5 +1,5 @@
-"""Which kernel runs each 3x3 convolution of the executor (score_exec.py / score_tape.py): pure functions of integers and
-flags.  No tensors, no executor state, importable without a GPU.
+"""Which kernel runs each 3x3 convolution and each pointwise GEMM of the executor (score_exec.py / score_tape.py): pure
+functions of integers and flags.  No tensors, no executor state, importable without a GPU.
 
 Everything that depends on the kernel a 3x3 stride-1 pad-1 convolution runs on - the layout its producer writes (fp32 or
 bf16 limb planes), the GroupNorm partial sums its epilogue can leave, the form of its data and weight gradients, whether a
@@ -124,6 +124,33 @@ def pointwise_wgrad_route(split: bool, m: int, n: int, n2: int, k: int) -> str:
     return TILE
 
 
+class AttnPlan(NamedTuple):
+    """Kernel choices of one attention block over [m = b * hw][c]."""
+    route: str                      # every projection and its data gradient (c -> c, and the fused c -> 3c / 3c -> c)
+    fused: bool                     # limb routes: q | k | v come from ONE GEMM into one [m][3c] buffer
+    wgrad: str                      # a NIN weight gradient dW[c][c], the one-GEMM q | k | v weight gradient dW[c][3c], and
+    qkv_wgrad: str                  # whether that one runs (a limb route takes it and the batched slab reduction cuts its
+    qkv_one: bool                   # result into the three parameters)
+
+
+def attn_plan(split: bool, c: int, m: int) -> AttnPlan:
+    route = pointwise_route(split, c, 0, m, c)
+    fused = route != TILE
+    # c -> c, c -> 3c and 3c -> c take the same route: 3c is a multiple of 128 exactly when c is
+    assert not fused or pointwise_route(split, c, 0, m, 3 * c) == route == pointwise_route(split, 3 * c, 0, m, c)
+    qkv_wgrad = pointwise_wgrad_route(split, c, 3 * c, 0, m)
+    return AttnPlan(route, fused, pointwise_wgrad_route(split, c, c, 0, m), qkv_wgrad,
+                    fused and qkv_wgrad != TILE and ops.slab_units(c * c, 2, c, 3 * c) > 0)
+
+
+def pyramid_plan(split: bool, cin: int, cout: int, m: int):
+    """(small, limb, fwd, bwd) of the input pyramid's 3x3 stride-2 convolution to [m][cout].  ``small``: few input channels (im2col
+    to K = 64 + a tile-engine GEMM); else ``limb``: im2col + pointwise GEMM on limb routes ``fwd`` / ``bwd``; neither: the tile engine."""
+    small = cin * 9 <= 64 and cout % 4 == 0
+    fwd, bwd = pointwise_route(split, 9 * cin, 0, m, cout), pointwise_route(split, cout, 0, m, 9 * cin)
+    return small, not small and cin % 4 == 0 and fwd != TILE and bwd != TILE, fwd, bwd
+
+
 def head_fewout(cin: int, cout: int) -> bool:
     """The head's 3x3 convolution to a few output channels runs on its own kernel (ops.conv3x3_fewout)."""
     return ops.conv3x3_fewout_supported(cin, cout)
@@ -141,10 +168,12 @@ class BlockPlan(NamedTuple):
     wgrad1: Optional[str] = None
     dgrad0: Tuple[str, ...] = ()    # ... and data-gradient routes; Conv_0's per source of a two-source block
     dgrad1: Optional[str] = None
+    shortcut: Optional[str] = None  # the 1x1 shortcut (blocks that have one): pointwise routes of its forward ...
+    shortcut_dgrad: Optional[str] = None    # ... and (recording passes) of its one-source data gradient
 
 
 def block_plan(split: bool, limb_planes: bool, record: bool, dropout: bool, c1: int, c2: int, b: int, h: int, w: int,
-               cout: int, up: bool, down: bool, wino=wino_wanted) -> BlockPlan:
+               cout: int, up: bool, down: bool, wino=wino_wanted, shortcut: bool = False) -> BlockPlan:
     """``c2``: channels of the second source of an unmaterialised concatenation (0: one source); ``[h, w]``: the block's
     input map - blocks that resample (``up`` / ``down``) do so between GroupNorm_0 and Conv_0, so both convolutions run
     on the output map."""
@@ -173,8 +202,9 @@ def block_plan(split: bool, limb_planes: bool, record: bool, dropout: bool, c1: 
     part1 = limb_takes(split, cout, 0, b, ho, wo, cout) and part
     assert not lp0 or conv0 == LIMB, "limb planes reach a Conv_0 kernel that cannot read them"
     assert not lp1 or conv1 == LIMB, "limb planes reach a Conv_1 kernel that cannot read them"
+    sc = pointwise_route(split, c1, c2, b * ho * wo, cout) if shortcut else None
     if not record:
-        return BlockPlan(conv0, conv1, lp0, lp1, part0, part1)
+        return BlockPlan(conv0, conv1, lp0, lp1, part0, part1, shortcut=sc)
     wgrad0 = wgrad_route(split, cout, c1, c2, b, ho, wo, lp0)
     wgrad1 = wgrad_route(split, cout, cout, 0, b, ho, wo, lp1)
     dgrad1 = conv3_route(split, cout, 0, b, ho, wo, cout, wino=wino)
@@ -190,7 +220,8 @@ def block_plan(split: bool, limb_planes: bool, record: bool, dropout: bool, c1: 
     assert not lp0 or wgrad0 == LIMB, "limb planes reach a Conv_0 weight gradient that cannot read them"
     assert not lp1 or wgrad1 == LIMB, "limb planes reach a Conv_1 weight gradient that cannot read them"
     assert wgrad0 != NONE, "unsupported two-source weight gradient"
-    return BlockPlan(conv0, conv1, lp0, lp1, part0, part1, wgrad0, wgrad1, dgrad0, dgrad1)
+    return BlockPlan(conv0, conv1, lp0, lp1, part0, part1, wgrad0, wgrad1, dgrad0, dgrad1, sc,
+                     pointwise_route(split, cout, 0, b * ho * wo, c1 + c2) if shortcut else None)
 
 
 def cat_ok(split: bool, record: bool, c1: int, c2: int, b: int, h: int, w: int, cout: int, up: bool, down: bool,

@@ -1,5 +1,5 @@
 """Executor base of the NCSN++ score network: graph nodes, the kernel-launch helpers shared by every block (3x3
-convolutions and their gradients dispatched on the routes of score_routes.py, GroupNorm backward, bias gradients,
+convolutions, pointwise GEMMs and their gradients dispatched on the routes of score_routes.py, GroupNorm backward, bias gradients,
 few-channel convolutions), the side stream, the deferred parameter-gradient reductions and the backward tape.  The
 network's program - which block runs when - is score_exec.py."""
 from __future__ import annotations
@@ -15,7 +15,7 @@ from . import ops
 from . import score_routes as R
 from .score_modules import _Affine
 from .score_routes import _pick_nsplit
-from .score_weights import _built_entry
+from .score_weights import PointwiseWeight, _built_entry
 
 Tensor = torch.Tensor
 
@@ -334,14 +334,8 @@ class _ExecBase:
             self.reduce_slabs(slabs, nsplit, n, self.g(conv.weight), layout=1, cout=cout, taps=taps, cin=cin, alpha=alpha)
             return
         pw = R.pointwise_wgrad_route(self.split, cout, c1, c2, b * oh * ow) if (k, stride, pad) == (1, 1, 0) else R.TILE
-        if pw != R.TILE:
-            nsplit = R._tn_split(cout, cin, b * oh * ow)
-            slabs = self.slabs_for(4 * n * nsplit, dy.device)
-            if pw == R.LIMB_TAIL:
-                ops.gemm_tn_split_tail(cout, c1, b * oh * ow, dy, cout, x, c1, slabs, cin, nsplit)
-            else:
-                ops.gemm_tn_split(cout, c1, b * oh * ow, dy, cout, x, c1, slabs, cin, nsplit, x2, c2, c2)
-            self.reduce_slabs(slabs, nsplit, n, self.g(conv.weight), alpha=alpha)
+        if pw != R.TILE:        # (a 1x1 convolution's tile-engine form is conv2d_wgrad_nhwc below, not pw_wgrad's GEMM)
+            self.pw_wgrad(pw, cout, c1, b * oh * ow, dy, cout, x, c1, (self.g(conv.weight),), alpha, x2, c2)
             return
         assert x2 is None, "unsupported two-source weight gradient"
         tiles = ((cout + 127) // 128) * ((cin + 127) // 128) * taps
@@ -425,23 +419,57 @@ class _ExecBase:
         else:
             ops.conv3x3_wino_gn(x, st, x2, st2, True, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)
 
-    def gemm_limb(self, route: str, a: Tensor, m: int, frag: Tensor, n: int, y: Tensor, epi=None):
-        """One-source pointwise GEMM on ``route`` (score_routes.pointwise_route: LIMB or LIMB_TAIL), three limbs."""
+    # -- pointwise GEMMs (1x1 shortcuts, NIN projections, the pyramid's im2col GEMM) on a score_routes.pointwise_* route ------
+    def pw_fwd(self, route: str, a1: Tensor, a2: Optional[Tensor], m: int, w: PointwiseWeight, y: Tensor, epi):
+        """y[m][w.n] = epi([a1 | a2] W^T).  LIMB runs the two-limb form where math mode 'bf16x3' wants it (LIMB_TAIL has none);
+        TILE is the tile engine's 1x1 convolution for an "oi" weight (it alone takes a second source), its GEMM for NIN."""
+        n = w.n
         if route == R.LIMB_TAIL:
-            ops.gemm_split_tail(a, m, frag, n, y, epi)
+            ops.gemm_split_tail(a1, m, w.frag(tail=True), n, y, epi)
+        elif route == R.LIMB and self.x3 and ops.gemm_split_x3_wanted(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n):
+            ops.gemm_split_x3(a1, a2, m, w.frag(x3=True), n, y, epi)
+        elif route == R.LIMB:
+            ops.gemm_split(a1, a2, m, w.frag(), n, y, epi)
+        elif w.kind == "oi":
+            ops.conv2d_nhwc(a1, a2, w.w, n, 1, 1, 1, 0, 1, a1.shape[1], a1.shape[2], y, epi)
         else:
-            ops.gemm_split(a, None, m, frag, n, y, epi)
+            wt, tb, ld = w.tile(False)
+            ops.gemm_raw(0, tb, m, n, w.k, a1, w.k, 0, wt, ld, 0, y, n, 0, epi=epi)
 
-    def gemm_fwd(self, a1: Tensor, a2: Optional[Tensor], m: int, n: int, y: Tensor, epi, frag, frag_x3, route: str = R.LIMB):
-        """Forward pointwise GEMM on the limb kernels; ``frag()`` / ``frag_x3()``: its three- / two-limb fragments.
-        ``route`` LIMB_TAIL: the three-limb tail launch in every math mode (there is no two-limb tail form)."""
-        k1, k2 = a1.shape[-1], a2.shape[-1] if a2 is not None else 0
+    def pw_dgrad(self, route: str, dy: Tensor, m: int, w: PointwiseWeight, dx: Tensor, epi=None, cols=None):
+        """dx[m][w.k] = epi(dy[m][w.n] W).  ``cols`` = (lo, hi), limb routes: input channels lo .. hi alone, into a dx that wide
+        (one source of an unmaterialised concatenation: a data gradient's fragments are ordered by output-channel tile, so a
+        source's share is a contiguous slice of them)."""
+        n = w.k
+        if route == R.TILE:
+            wt, tb, ld = w.tile(True)
+            return ops.gemm_raw(0, tb, m, n, w.n, dy, w.n, 0, wt, ld, 0, dx, n, 0, epi=epi)
+        frag = w.frag(True, tail=route == R.LIMB_TAIL)
+        if cols is not None:
+            frag, n = frag[frag.numel() * cols[0] // n:frag.numel() * cols[1] // n], cols[1] - cols[0]
         if route == R.LIMB_TAIL:
-            ops.gemm_split_tail(a1, m, frag(), n, y, epi)
-        elif self.x3 and ops.gemm_split_x3_wanted(k1, k2, m, n):
-            ops.gemm_split_x3(a1, a2, m, frag_x3(), n, y, epi)
+            ops.gemm_split_tail(dy, m, frag, n, dx, epi)
         else:
-            ops.gemm_split(a1, a2, m, frag(), n, y, epi)
+            ops.gemm_split(dy, None, m, frag, n, dx, epi)
+
+    def pw_wgrad(self, route: str, M: int, N: int, K: int, A: Tensor, lda: int, B: Tensor, ldb: int, outs, alpha: float = 1.0,
+                 B2: Optional[Tensor] = None, N2: int = 0):
+        """alpha * A[K][M]^T [B | B2][K][N + N2] (K = pixels) as split-K slabs, then their reduction into ``outs``: the one
+        gradient [M][N + N2], or several that share its columns equally (q | k | v: cut apart by the batched reduction)."""
+        nt = N + N2
+        nsplit = _pick_nsplit(-(-M // 128) * -(-nt // 128), K) if route == R.TILE else R._tn_split(M, nt, K)
+        slabs = self.slabs_for(4 * M * nt * nsplit, A.device)
+        if route == R.TILE:
+            ops.gemm_tn_splitk(M, nt, K, A, lda, B, ldb, slabs, nsplit)
+        elif route == R.LIMB_TAIL:
+            ops.gemm_tn_split_tail(M, N, K, A, lda, B, ldb, slabs, nt, nsplit)
+        else:
+            ops.gemm_tn_split(M, N, K, A, lda, B, ldb, slabs, nt, nsplit, B2, N2, N2)
+        if len(outs) == 1:
+            return self.reduce_slabs(slabs, nsplit, M * nt, outs[0], alpha=alpha)
+        slabs, n = slabs.view(torch.float32), nt // len(outs)
+        for i, out in enumerate(outs):
+            self.reduce_slabs(slabs[i * n:], nsplit, M * n, out, layout=2, taps=n, cin=nt, alpha=alpha, more=i + 1 < len(outs))
 
     # -- few-channel 3x3 convolutions (6-channel stem / first pyramid level in, 6-channel head out) as K = 64 GEMMs ----
     # K = 9*6 = 54 does not fit the tile engine's 32-channel chunking, so these convolutions used its scalar-gather

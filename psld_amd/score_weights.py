@@ -1,7 +1,7 @@
-"""Derived-weight entries of NCSNpp (weight_cache.py): ``make(owner, *args) -> Entry``, called on first use."""
+"""Derived-weight entries of NCSNpp (weight_cache.py): ``make(owner, *args) -> Entry``, called on first use; PointwiseWeight."""
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -122,3 +122,37 @@ def _temb_entry(w0: Tensor, modules) -> Entry:
                 r.append(([src.data_ptr(), dst.data_ptr(), n // 4], n // 4))
         return r
     return Entry(w0, out=out, family="temb", rows=rows, graph=True)
+
+
+class PointwiseWeight(NamedTuple):
+    """A pointwise weight as the B operand of y[m][n] = a[m][k] B^T (n = the layer's outputs; data gradient: n and k swapped) in
+    the form a route of score_routes.pointwise_route launches on: limb fragments (a front for NCSNpp._pfrag / _qkv_frags /
+    _wcache.get: tags and entries are theirs) or the stored matrix as ops.gemm_raw takes it.  ``kind``, and what ``w`` then is:
+    "oi" a 1x1 Conv weight, stored [n][k]; "io" NIN.W, stored [k][n]; "qkv" an attention block (its shared q | k | v set, n = 3c);
+    "ohwi" the pyramid's 3x3 stride-2 convolution as the [n][k = 9 cin] GEMM over im2col patches (packed from NCSNpp._packed,
+    by the tail packer on LIMB_TAIL).  The last two have fragments only."""
+    net: object
+    w: object
+    n: int
+    k: int
+    kind: str
+    qkv: tuple = ()     # "qkv": this pass's NCSNpp._qkv_frags(w) = (forward fragments, data-gradient fragments, gathered bias)
+
+    def tile(self, dgrad: bool):
+        """(stored matrix, tb, ld) for ops.gemm_raw ("oi" / "io")."""
+        oi = self.kind == "oi"
+        return self.w, int(oi != dgrad), self.k if oi else self.n
+
+    def frag(self, dgrad: bool = False, x3: bool = False, tail: bool = False) -> Tensor:
+        """Three-limb (``x3``: two-limb, forward only) fragments of B[n][k], or of B[k][n] for the data gradient."""
+        net, w, kind = self.net, self.w, self.kind
+        n, k = (self.k, self.n) if dgrad else (self.n, self.k)
+        if kind == "qkv":
+            return net._qkv_frags_x3(w) if x3 else self.qkv[int(dgrad)]
+        if kind == "ohwi":
+            pack = ops.gemm_frag_x3 if x3 else ops.gemm_frag_tail if tail else ops.gemm_frag
+            sn, sk = (1, n) if dgrad else (k, 1)
+            return net._wcache.get(w.weight, ("s2dgrad" if dgrad else "s2fwd") + ("_x3" if x3 else ""), _built_entry,
+                                   lambda prev: pack(net._packed(w), n, k, sn, sk, prev))
+        _, rows, ld = self.tile(dgrad)          # rows: B's rows are the stored matrix's rows
+        return net._pfrag(w, ("dgrad" if dgrad else "fwd") + ("_x3" if x3 else ""), n, k, *((ld, 1) if rows else (1, ld)))
