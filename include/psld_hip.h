@@ -253,7 +253,8 @@ int psld_gemm_split_x3_f32(const float* a1, int k1, const float* a2, int k2, int
  * one kernel, the hw x hw score matrix never written (unless p != NULL: the probabilities [batch][hw][hw] fp32, what the
  * backward pass reads).  q / k / v: [batch*hw][c] fp32 with a common row stride ld (the fused q|k|v buffer: ld = 3c); o:
  * [batch*hw][c], row stride ldo.  Limb-MFMA arithmetic (three exact bf16 limbs, six products, fp32 accumulation), fp32 softmax.
- * hw in {256, 64} (16x16 / 8x8 maps), c in {256, 128}.  Replaces einsum -> softmax -> einsum of AttnBlockpp.forward
+ * hw in {256, 64} (16x16 / 8x8 maps), c in {256, 128, 480} (480: the attention width of an nf = 160 network; 64 queries per
+ * workgroup at both map sizes, one workgroup per CU).  Reads exactly columns [0, c) of the hw rows of each image of q / k / v.  Replaces einsum -> softmax -> einsum of AttnBlockpp.forward
  * (song_sde/layerspp.py:82-86). */
 int psld_attn_fwd_split_supported(int hw, int c);
 int psld_attn_fwd_split_f32(const float* q, const float* k, const float* v, int ld, int batch, int hw, int c, float scale,
@@ -345,6 +346,15 @@ int psld_bgemm_split_supported(int ta, int tb, int m, int n, int k);
 int psld_bgemm_split_f32(int ta, int tb, int m, int n, int k, const float* a, int lda, long long stride_a,
                          const float* b, int ldb, long long stride_b, float* c, int ldc, long long stride_c,
                          int batch, float alpha, hipStream_t stream);
+/* The same product with the last column tile cut short (the N = 480 products of attention at 480 channels: P V and the
+ * gradients dV, dQ, dK on 16x16 maps).  psld_bgemm_split_tail_supported: not both transposed, m % 128 == 0, n % 32 == 0,
+ * n >= 128, k % 32 == 0 and NOT a shape of psld_bgemm_split_supported (so n % 128 != 0).  Same arguments as
+ * psld_bgemm_split_f32.  Columns (tb: rows) of b at or beyond n are not read and columns of c at or beyond n not written;
+ * every element written is bit for bit that of psld_bgemm_split_f32 on b zero-padded to roundup(n, 128) columns. */
+int psld_bgemm_split_tail_supported(int ta, int tb, int m, int n, int k);
+int psld_bgemm_split_tail_f32(int ta, int tb, int m, int n, int k, const float* a, int lda, long long stride_a,
+                              const float* b, int ldb, long long stride_b, float* c, int ldc, long long stride_c,
+                              int batch, float alpha, hipStream_t stream);
 
 /* Weight gradient of the convolution above for one input source:
  * slabs[s][co][tap][col0 + ci] = sum over the s-th range of output pixels of dy[pix][co] * x[pix+tap][ci]. */

@@ -138,6 +138,8 @@ SIGNATURES = {
     "psld_gemm_tn_split_tail_f32": (I, [I, I, I, P, I, P, I, P, I, I, P]),
     "psld_bgemm_split_supported": (I, [I, I, I, I, I]),
     "psld_bgemm_split_f32": (I, [I, I, I, I, I, P, I, LL, P, I, LL, P, I, LL, I, F, P]),
+    "psld_bgemm_split_tail_supported": (I, [I, I, I, I, I]),
+    "psld_bgemm_split_tail_f32": (I, [I, I, I, I, I, P, I, LL, P, I, LL, P, I, LL, I, F, P]),
     "psld_reduce_slabs_f32": (I, [P, I, LL, P, I, I, I, I, F, P]),
     "psld_pack_oihw_to_ohwi_f32": (I, [P, P, I, I, I, P]),
     "psld_pack_oihw_to_dgrad_f32": (I, [P, P, I, I, I, P]),

@@ -46,15 +46,19 @@ __device__ __forceinline__ u32x2 lds_tr16(const unsigned char* p) {
     return __builtin_bit_cast(u32x2, v);
 }
 
+// C = 480 (the nf = 160 networks; DESIGN 4c⁗): four waves at both map sizes, ONE workgroup per CU (the V image alone is
+// 95,232 B), so a wave has its SIMD to itself and up to 512 registers: 30 output accumulators (120 registers) beside the 16
+// score accumulators of a 16x16 map (64) and the V prefetch (60).  Eight waves are two per SIMD whatever the launch bounds
+// say - 256 registers, which that sum does not fit.
 template <int HW, int C, int QW>
-__global__ void __launch_bounds__(64 * QW, 2) attn_fwd_kernel(const AttnArgs a) {
+__global__ void __launch_bounds__(64 * QW, C == 480 ? 1 : 2) attn_fwd_kernel(const AttnArgs a) {
     constexpr int NT = 64 * QW;                 // threads: QW waves, wave w owns queries 16 w .. 16 w + 15 of the tile
     constexpr int QR = 16 * QW;                 // queries per workgroup
     constexpr int KB = HW / 16;                 // 16-key blocks
     constexpr int CB = C / 16;                  // 16-channel blocks of the output
     constexpr int KROWS = HW * ROWB;            // bytes of one limb of the K image
     constexpr int QROWS = QR * ROWB;
-    constexpr int VRS = C * 2 + 32;             // V image: bytes per key row and limb (544 for C = 256: rows 8 banks apart)
+    constexpr int VRS = C * 2 + 32;             // V image: bytes per key row and limb (544 for C = 256, 992 for 480: rows 8 banks apart)
     constexpr int VLIMB = 32 * VRS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // max(3 (KROWS + QROWS), 3 VLIMB)
     unsigned char* Ks = smem;
@@ -73,6 +77,7 @@ __global__ void __launch_bounds__(64 * QW, 2) attn_fwd_kernel(const AttnArgs a) 
     // of i and land while the MFMAs of i run (they are consumed behind the next barrier); V's first step is asked for during
     // the last chunk of the scores.
     constexpr int KI = HW * 8 / NT, QI = QR * 8 / NT, VI = 32 * (C / 4) / NT, QPR = C / 4, RSTEP = NT / 8;
+    static_assert(32 * (C / 4) % NT == 0, "a 32-key step of V is a whole number of items per thread");
     const int c4 = tid & 7, srow = tid >> 3;    // item i: row srow + RSTEP i, quad c4
     f32x4 kv[KI], qv[QI], vv[VI];
     auto load_kq = [&](int ch) {
@@ -235,7 +240,7 @@ int launch_attn(const AttnArgs& a, int batch, hipStream_t stream) {
 }  // namespace
 
 extern "C" int psld_attn_fwd_split_supported(int hw, int c) {
-    return (hw == 256 || hw == 64) && (c == 256 || c == 128);
+    return (hw == 256 || hw == 64) && (c == 256 || c == 128 || c == 480);
 }
 
 extern "C" int psld_attn_fwd_split_f32(const float* q, const float* k, const float* v, int ld, int batch, int hw, int c,
@@ -246,11 +251,12 @@ extern "C" int psld_attn_fwd_split_f32(const float* q, const float* k, const flo
                    "psld_attn_fwd_split_f32: 16-byte aligned rows needed");
     AttnArgs a{q, k, v, ld, scale, o, ldo, p};
     // 16x16 maps: 128 queries per workgroup, eight waves (K / V are split into limbs once per 128 queries); 8x8 maps: the
-    // whole image (64 queries), four waves
+    // whole image (64 queries), four waves.  c = 480: 64 queries and four waves at both map sizes
 #ifdef PSLD_ABLATIONS
     static const int qw4 = [] { const char* v = getenv("PSLD_ATTN_QW4"); return v ? atoi(v) : 0; }();
     if (qw4 && hw == 256 && c == 256) return launch_attn<256, 256, 4>(a, batch, stream);
 #endif
+    if (c == 480) return hw == 256 ? launch_attn<256, 480, 4>(a, batch, stream) : launch_attn<64, 480, 4>(a, batch, stream);
     if (hw == 256) return c == 256 ? launch_attn<256, 256, 8>(a, batch, stream) : launch_attn<256, 128, 8>(a, batch, stream);
     return c == 256 ? launch_attn<64, 256, 4>(a, batch, stream) : launch_attn<64, 128, 4>(a, batch, stream);
 }

@@ -1382,7 +1382,8 @@ __global__ void __launch_bounds__(256, 2) pwgrad_kernel(const PWgradArgs a) {
 struct BGemmArgs {
     const float* a;
     int lda;
-    long long sa;
+    int n;                  // TAIL: columns of C (a multiple of 32): the last column tile is cut short.  (n sits in what was
+    long long sa;           // padding: the argument block of the full-tile instances is byte for byte what it was)
     const float* b;
     int ldb;
     long long sb;
@@ -1393,7 +1394,12 @@ struct BGemmArgs {
     float alpha;
 };
 
-template <bool AT, bool BT>
+// TAIL (psld_bgemm_split_tail_f32: n a multiple of 32, no multiple of 128; attention at 480 channels, DESIGN 4c⁗): the
+// column quads (BT: the rows) of B in the last column tile that lie at or beyond n are loaded with the all-ones offset - a
+// raw buffer load out of range returns zeros, nothing is read - the 16-column blocks of a wave that lie wholly beyond n
+// (a wave-uniform count) issue no MFMAs, and their columns are not stored.  Every live output element sees the K tiles and
+// limb products of a full-tile launch on zero-padded operands.
+template <bool AT, bool BT, bool TAIL = false>
 __global__ void __launch_bounds__(256, 2) bgemm_kernel(const BGemmArgs a) {
     constexpr int MC_RS = 288, MC_LIMB = 32 * MC_RS, KC_LIMB = 128 * ROWB;
     constexpr int A_LIMB = AT ? MC_LIMB : KC_LIMB, B_LIMB = BT ? KC_LIMB : MC_LIMB;
@@ -1402,7 +1408,7 @@ __global__ void __launch_bounds__(256, 2) bgemm_kernel(const BGemmArgs a) {
     unsigned char* Bs = smem + 3 * A_LIMB;
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = TAIL ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int tiles = a.tiles_i * a.tiles_j;
     const int vid = xcd_remap(blockIdx.x, gridDim.x);
@@ -1410,6 +1416,8 @@ __global__ void __launch_bounds__(256, 2) bgemm_kernel(const BGemmArgs a) {
     const int i0 = (tile / a.tiles_j) * 128, j0 = (tile % a.tiles_j) * 128;
     const float* Ab = a.a + batch * a.sa + (AT ? (long long)i0 : (long long)i0 * a.lda);
     const float* Bb = a.b + batch * a.sb + (BT ? (long long)j0 * a.ldb : (long long)j0);
+    // live 16-column blocks of this wave's 64 columns (n is a multiple of 32: a block is live or dead as a whole)
+    const int nb_live = TAIL ? min(4, max(0, (a.n - j0 - wc * 64) >> 4)) : 4;
 
     const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p4 = i16 & 3;
     // fragment read addresses
@@ -1440,6 +1448,9 @@ __global__ void __launch_bounds__(256, 2) bgemm_kernel(const BGemmArgs a) {
         a_so[i] = AT ? r * MC_RS + cq * 8 : kc_so;
         b_go[i] = !BT ? (unsigned)((r * a.ldb + cq * 4) * 4) : (unsigned)((row * a.ldb + c4 * 4) * 4);
         b_so[i] = !BT ? r * MC_RS + cq * 8 : kc_so;
+        if constexpr (TAIL) {
+            if (j0 + (BT ? row : cq * 4) >= a.n) b_go[i] = 0xffffffffu;
+        }
     }
     f32x4 va[4], vb[4];
     auto load_tile = [&](int kt) {
@@ -1498,6 +1509,7 @@ __global__ void __launch_bounds__(256, 2) bgemm_kernel(const BGemmArgs a) {
             for (int l = 0; l < 3; ++l) fa[cb][l] = frag_a(l, cb);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
+            if (TAIL && nb >= nb_live) break;
             u32x4 fb[3];
 #pragma unroll
             for (int l = 0; l < 3; ++l) fb[l] = frag_b(l, nb);
@@ -1519,17 +1531,18 @@ __global__ void __launch_bounds__(256, 2) bgemm_kernel(const BGemmArgs a) {
         for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
+                if (TAIL && nb >= nb_live) continue;
                 const int i = i0 + wr * 64 + cb * 16 + 4 * g + v;
                 Cb[(long long)i * a.ldc + j0 + wc * 64 + nb * 16 + i16] = a.alpha * acc[cb][nb][v];
             }
 }
 
-template <bool AT, bool BT>
-int launch_bgemm(const BGemmArgs& a, int batch, hipStream_t stream) {
+template <bool AT, bool BT, bool TAIL>
+int launch_bgemm(const char* name, const BGemmArgs& a, int batch, hipStream_t stream) {
     constexpr size_t LDS = (size_t)3 * ((AT ? 32 * 288 : 128 * ROWB) + (BT ? 128 * ROWB : 32 * 288));
-    if (int st = psld_lds_once<&bgemm_kernel<AT, BT>>(LDS, "psld_bgemm_split_f32")) return st;
-    hipLaunchKernelGGL((bgemm_kernel<AT, BT>), dim3((unsigned)(a.tiles_i * a.tiles_j * batch)), dim3(256), LDS, stream, a);
-    PSLD_CHECK_LAUNCH("psld_bgemm_split_f32");
+    if (int st = psld_lds_once<&bgemm_kernel<AT, BT, TAIL>>(LDS, name)) return st;
+    hipLaunchKernelGGL((bgemm_kernel<AT, BT, TAIL>), dim3((unsigned)(a.tiles_i * a.tiles_j * batch)), dim3(256), LDS, stream, a);
+    PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
 }
 
@@ -2131,23 +2144,46 @@ extern "C" int psld_bgemm_split_supported(int ta, int tb, int m, int n, int k) {
     return !(ta && tb) && m > 0 && n > 0 && k > 0 && m % 128 == 0 && n % 128 == 0 && k % 32 == 0;
 }
 
-extern "C" int psld_bgemm_split_f32(int ta, int tb, int m, int n, int k, const float* a, int lda, long long stride_a,
-                                    const float* b, int ldb, long long stride_b, float* c, int ldc, long long stride_c,
-                                    int batch, float alpha, hipStream_t stream) {
-    PSLD_CHECK_ARG(a && b && c && batch >= 1, "psld_bgemm_split_f32: bad args");
-    PSLD_CHECK_ARG(psld_bgemm_split_supported(ta, tb, m, n, k), "psld_bgemm_split_f32: unsupported ta=%d tb=%d m=%d n=%d k=%d",
-                   ta, tb, m, n, k);
+// n: a multiple of 32 from 128 up that is no multiple of 128 (those are psld_bgemm_split_f32's); m in whole tiles as there
+extern "C" int psld_bgemm_split_tail_supported(int ta, int tb, int m, int n, int k) {
+    return !(ta && tb) && m > 0 && k > 0 && m % 128 == 0 && n >= 128 && n % 32 == 0 && k % 32 == 0 &&
+           !psld_bgemm_split_supported(ta, tb, m, n, k);
+}
+
+// psld_bgemm_split_f32 and, TAIL, its cut-tile form
+template <bool TAIL>
+static int bgemm_split(const char* name, int ta, int tb, int m, int n, int k, const float* a, int lda, long long stride_a,
+                       const float* b, int ldb, long long stride_b, float* c, int ldc, long long stride_c, int batch,
+                       float alpha, hipStream_t stream) {
+    PSLD_CHECK_ARG(a && b && c && batch >= 1, "%s: bad args", name);
+    PSLD_CHECK_ARG(TAIL ? psld_bgemm_split_tail_supported(ta, tb, m, n, k) : psld_bgemm_split_supported(ta, tb, m, n, k),
+                   "%s: unsupported ta=%d tb=%d m=%d n=%d k=%d", name, ta, tb, m, n, k);
     PSLD_CHECK_ARG(aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0 && stride_a % 4 == 0 && stride_b % 4 == 0,
-                   "psld_bgemm_split_f32: unaligned operand");
+                   "%s: unaligned operand", name);
     BGemmArgs p{};
     p.a = a; p.lda = lda; p.sa = stride_a;
     p.b = b; p.ldb = ldb; p.sb = stride_b;
     p.c = c; p.ldc = ldc; p.sc = stride_c;
-    p.tiles_i = m / 128; p.tiles_j = n / 128; p.ktiles = k / 32;
+    p.tiles_i = m / 128; p.tiles_j = cdiv(n, 128); p.ktiles = k / 32;
     p.alpha = alpha;
-    if (ta) return launch_bgemm<true, false>(p, batch, stream);
-    if (tb) return launch_bgemm<false, true>(p, batch, stream);
-    return launch_bgemm<false, false>(p, batch, stream);
+    if (TAIL) p.n = n;
+    if (ta) return launch_bgemm<true, false, TAIL>(name, p, batch, stream);
+    if (tb) return launch_bgemm<false, true, TAIL>(name, p, batch, stream);
+    return launch_bgemm<false, false, TAIL>(name, p, batch, stream);
+}
+
+extern "C" int psld_bgemm_split_f32(int ta, int tb, int m, int n, int k, const float* a, int lda, long long stride_a,
+                                    const float* b, int ldb, long long stride_b, float* c, int ldc, long long stride_c,
+                                    int batch, float alpha, hipStream_t stream) {
+    return bgemm_split<false>("psld_bgemm_split_f32", ta, tb, m, n, k, a, lda, stride_a, b, ldb, stride_b, c, ldc, stride_c, batch,
+                              alpha, stream);
+}
+
+extern "C" int psld_bgemm_split_tail_f32(int ta, int tb, int m, int n, int k, const float* a, int lda, long long stride_a,
+                                         const float* b, int ldb, long long stride_b, float* c, int ldc, long long stride_c,
+                                         int batch, float alpha, hipStream_t stream) {
+    return bgemm_split<true>("psld_bgemm_split_tail_f32", ta, tb, m, n, k, a, lda, stride_a, b, ldb, stride_b, c, ldc, stride_c,
+                             batch, alpha, stream);
 }
 
 // ---- pointwise (NT GEMM with pre-split B) -------------------------------------------------------------------

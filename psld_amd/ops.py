@@ -547,6 +547,18 @@ def bgemm_split(ta: int, tb: int, M: int, N: int, K: int, A: Tensor, lda: int, s
 
 
 @functools.lru_cache(maxsize=None)
+def bgemm_split_tail_supported(ta: int, tb: int, m: int, n: int, k: int) -> bool:
+    return bool(lib().psld_bgemm_split_tail_supported(ta, tb, m, n, k))
+
+
+def bgemm_split_tail(ta: int, tb: int, M: int, N: int, K: int, A: Tensor, lda: int, sa: int, B: Tensor, ldb: int, sb: int,
+                     Cc: Tensor, ldc: int, sc: int, batch: int = 1, alpha: float = 1.0):
+    """bgemm_split for N a multiple of 32 from 128 up that is no multiple of 128 (the last column tile is cut short)."""
+    check(lib().psld_bgemm_split_tail_f32(ta, tb, M, N, K, A.data_ptr(), lda, sa, B.data_ptr(), ldb, sb, Cc.data_ptr(), ldc, sc,
+                                          batch, alpha, _stream()), "psld_bgemm_split_tail_f32")
+
+
+@functools.lru_cache(maxsize=None)
 def attn_fwd_supported(hw: int, c: int) -> bool:
     return bool(lib().psld_attn_fwd_split_supported(hw, c))
 

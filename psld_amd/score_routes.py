@@ -1,5 +1,5 @@
-"""Which kernel runs each 3x3 convolution and each pointwise GEMM of the executor (score_exec.py / score_tape.py): pure
-functions of integers and flags.  No tensors, no executor state, importable without a GPU.
+"""Which kernel runs each 3x3 convolution, each pointwise GEMM and each batched product of the executor (score_exec.py /
+score_tape.py): pure functions of integers and flags.  No tensors, no executor state, importable without a GPU.
 
 Everything that depends on the kernel a 3x3 stride-1 pad-1 convolution runs on - the layout its producer writes (fp32 or
 bf16 limb planes), the GroupNorm partial sums its epilogue can leave, the form of its data and weight gradients, whether a
@@ -21,7 +21,7 @@ from . import ops
 WINO = "wino"           # Winograd F(2x2, 3x3): conv_wino.hip forward / data gradient, wgrad_wino.hip weight gradient
 LIMB = "limb"           # direct bf16 limb kernels (conv_split.hip); the only route that reads ops.LimbPlanes
 TILE = "tile"           # fp32 tile engine (ops.conv2d_nhwc / conv2d_wgrad_nhwc)
-LIMB_TAIL = "limb_tail"  # pointwise only: the limb kernels with the last channel tile cut short (widths in steps of 32)
+LIMB_TAIL = "limb_tail"  # pointwise and batched: the limb kernels with the last channel tile cut short (widths in steps of 32)
 WINO_GN = "wino_gn"     # forward only: SiLU(GroupNorm(.)) applied inside the Winograd kernel's input staging
 NONE = "none"           # weight gradient only: a two-source shape no kernel takes
 
@@ -120,6 +120,18 @@ def pointwise_wgrad_route(split: bool, m: int, n: int, n2: int, k: int) -> str:
     if split and ops.gemm_tn_split_supported(m, n, k) and n2 % 128 == 0:
         return LIMB
     if split and n2 == 0 and ops.gemm_tn_split_tail_supported(m, n, k):
+        return LIMB_TAIL
+    return TILE
+
+
+def batched_route(split: bool, ta: int, tb: int, m: int, n: int, k: int) -> str:
+    """Route of a batched activation x activation product c[b] = alpha op(a[b]) op(b[b]) - the attention block's QK^T, PV
+    and their gradients where the fused forward kernel does not run.  The ONE place that asks ops.bgemm_split_supported /
+    ops.bgemm_split_tail_supported for the executor (which sends operands that are not 16-byte aligned to the tile engine
+    whatever the route)."""
+    if split and ops.bgemm_split_supported(ta, tb, m, n, k):
+        return LIMB
+    if split and ops.bgemm_split_tail_supported(ta, tb, m, n, k):
         return LIMB_TAIL
     return TILE
 

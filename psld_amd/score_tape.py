@@ -362,9 +362,12 @@ class _ExecBase:
 
     def bmm(self, ta: int, tb: int, M: int, N: int, K: int, A: Tensor, lda: int, sa: int, B: Tensor, ldb: int, sb: int,
             Cc: Tensor, ldc: int, sc: int, batch: int, alpha: float = 1.0):
-        """Batched activation x activation product (attention): limb kernel when the shape allows, fp32 engine otherwise."""
-        if self.split and ops.bgemm_split_supported(ta, tb, M, N, K) and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0:
-            ops.bgemm_split(ta, tb, M, N, K, A, lda, sa, B, ldb, sb, Cc, ldc, sc, batch, alpha)
+        """Batched activation x activation product (attention): the limb kernel R.batched_route names (whole tiles, or the
+        last column tile cut short), fp32 engine otherwise and for operands that are not 16-byte aligned."""
+        route = R.batched_route(self.split, ta, tb, M, N, K)
+        if route != R.TILE and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0:
+            launch = ops.bgemm_split if route == R.LIMB else ops.bgemm_split_tail
+            launch(ta, tb, M, N, K, A, lda, sa, B, ldb, sb, Cc, ldc, sc, batch, alpha)
         else:
             ops.gemm_raw(ta, tb, M, N, K, A, lda, sa, B, ldb, sb, Cc, ldc, sc, batch,
                          ops.epilogue(alpha=alpha) if alpha != 1.0 else None)
