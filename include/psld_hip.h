@@ -153,7 +153,9 @@ int psld_conv3x3_split_f32(const float* x1, int c1, const float* x2, int c2, int
  * re-associated (what cuDNN may pick for the reference's nn.Conv2d 3x3, song_sde/layers.py:103-109), within ~2x of
  * the direct kernel's rounding error against fp64.  Weights come pre-transformed and pre-split in MFMA operand order
  * (psld_pack_conv3x3_wino, once per optimizer step; psld_conv3x3_wino_frag_bytes = 16/9 of the direct fragments).
- * Shapes: c1, c2 multiples of 32, cout a multiple of 128, h even, w in {8,16,32,64}, h*w dividing or divisible by 128. */
+ * Shapes: c1, c2 multiples of 32, cout a multiple of 128, h even, w in {8,16,32,64}, h*w dividing or divisible by 128.
+ * Row strides: ldy and epi->ldres below 2^20 elements (every psld_conv3x3_wino_* launch: the epilogue addresses the up to
+ * 416 pixels of a workgroup's region by 32-bit byte offsets from the first; larger strides are refused). */
 long long psld_conv3x3_wino_frag_bytes(int cout, int cin);
 int psld_conv3x3_wino_supported(int c1, int c2, int batch, int h, int w, int cout);
 int psld_pack_conv3x3_wino(const float* w_oihw, void* ufrag, int cout, int cin, int dgrad, hipStream_t stream);

@@ -53,19 +53,50 @@ struct WinoArgs {
     PsldEpilogue e;
     const float* zero;
     int nmajor;
-    int tiles_m;            // wino_conv8p_kernel: pixel tiles of the launch (cdiv(M, 128))
+    int tiles_m;            // pixel tiles of the launch, cdiv(M, 128): the grid is ksplit x tiles_m x channel tiles (launch_wino8s)
     int stagger;
     // wino_conv8s_kernel<., GNF = true>: GroupNorm apply (+ SiLU) of the input inside the raw staging - per-(image, channel)
     // scale / shift rows of source 1 and 2 ([B][C1], [B][C2]: psld_gn_stats_*), act = 1: SiLU
     const float *gsc1, *gsh1, *gsc2, *gsh2;
     int gn_act;
     unsigned long long* dbg;    // ablation library: s_memtime stamps of one chunk (ABL & 64), [workgroup][wave][8]
-    int lg_tiles_x, lg_tps; // wino_conv8p_kernel: log2 of the tiles per tile row (cw / 2) and per image segment
+    int lg_tiles_x, lg_tps; // log2 of the tiles per tile row (cw / 2) and per image segment
     // wino_conv8s_kernel, small grids (round 6): the channel chunks split over ksplit workgroups per tile, each writing its plain
     // partial output to C + split * slab_stride (no epilogue); psld_detail_conv_reduce_epilogue sums them.  ksplit = 0 / 1: off
     int ksplit;
     long long slab_stride;
+    // wino_conv8s_kernel: the launch geometry's divisions, done once on the host (wino_conv).  Powers of two as
+    // their log2; the halo decomposition px -> (seg, hr, hx), px < 256, as exact multiply-shifts (wino_div16)
+    int lg_ksplit, lg_xblocks;  // log2 of ksplit (0: off) and of W / cw
+    int lg_rpi;                 // log2 of the regions per image (H * W / 128), -1: not a power of two (non-square maps)
+    int mul_seg, mul_w2;        // wino_div16 multipliers of seg_px = (rps + 2) * (cw + 2) and of W2 = cw + 2
+    int rb_img;                 // the row bias is one row per image (rows_per_img == H * W): its row is the image index
 };
+
+// x / d for 0 <= x < 256 as (x * wino_mul16(d)) >> 16: exact for every divisor the halo decomposition meets
+constexpr int wino_mul16(int d) { return 65536 / d + 1; }
+__host__ __device__ constexpr int wino_div16(int x, int mul) { return (x * mul) >> 16; }
+// every (rps, cw) wino_geometry returns (64- and 128-wide maps run as the 32-wide case); nseg * seg_px <= 256
+constexpr int WINO_GEOS[6][2] = {{4, 8}, {8, 8}, {16, 8}, {4, 16}, {8, 16}, {4, 32}};
+constexpr bool wino_div16_exact() {
+    for (const auto& g : WINO_GEOS) {
+        const int W2 = g[1] + 2, seg_px = (g[0] + 2) * W2;
+        for (int x = 0; x < 256; ++x)
+            if (wino_div16(x, wino_mul16(seg_px)) != x / seg_px || wino_div16(x, wino_mul16(W2)) != x / W2) return false;
+    }
+    return true;
+}
+static_assert(wino_div16_exact(), "halo decomposition: multiply-shift must equal the division for every pixel below 256");
+constexpr bool wino_geo_listed(int rps, int cw) {
+    for (const auto& g : WINO_GEOS)
+        if (g[0] == rps && g[1] == cw) return true;
+    return false;
+}
+constexpr int wino_lg2(int v) {     // log2 of a power of two, -1 otherwise
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return (1 << l) == v ? l : -1;
+}
 
 // raw halo image: pixel hp, 16-byte slot q (4 channels) -> byte offset.  Pixels sit pairwise in 256-byte rows and the
 // half of the row a pixel takes alternates with the pair index: the transform phase reads pixels 2 apart (tiles are two
@@ -168,7 +199,11 @@ __global__ void wino_pack_batch_kernel(const long long* __restrict__ tab, int nt
 // (Two persistent forms of this kernel were built and measured slower: workgroups walking (pixel tile, channel tile) work
 // lists, 480 vs 454 us on 256->256 @32x32 B=128, and one workgroup per pixel tile looping over the channel tiles with the
 // half-phase pipeline running across the passes, 522 vs 451 us - hipcc's code for the accumulators degrades once the
-// epilogue sits inside a loop.  One workgroup per (pixel tile, channel tile) it is.)
+// epilogue sits inside a loop.  One workgroup per (pixel tile, channel tile) it is.  Both tried to HIDE a workgroup's ends - the
+// set-up and the epilogue, ~13 us that nothing covers on a CU the workgroup has to itself - behind a neighbouring item; the
+// epilogue's vector instructions are zero-sum beside a partner's MFMAs.  The ends are SHORTENED instead: no runtime division in
+// the index arithmetic (WinoArgs carries shifts and multiply-shift constants), the last chunk peeled out of the loop without the
+// staging and transform of a chunk that does not exist, A^T m A in place with 32-bit offsets from scalar bases.  profiles/r08/README.md has the per-launch times against the previous kernel.)
 // GNF: the input is the RAW tensor a GroupNorm (+ SiLU) is to be applied to, and the apply pass runs here, on the float4 a
 // thread has just loaded for the raw image: a = silu(x * scale[img][c] + shift[img][c]), zero outside the image (the
 // convolution pads the ACTIVATED tensor).  The inference forward (EM / SSCS sampling) needs the activated tensor nowhere
@@ -202,13 +237,13 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tiles_n = TAIL ? (a.N + 127) >> 7 : a.N >> 7;
     const int nsp = a.ksplit > 1 ? a.ksplit : 1;
-    const int per_range = (int)gridDim.x / nsp;                  // workgroups of one channel-chunk range
+    const int tiles_m = a.tiles_m;
+    const int per_range = tiles_m * tiles_n;                     // workgroups of one channel-chunk range (gridDim.x / nsp)
     const int vb = xcd_remap(blockIdx.x, gridDim.x);
-    const int split = vb / per_range;
+    const int split = nsp > 1 ? vb / per_range : 0;
     const int bid = vb - split * per_range;
-    const int kch = a.chunks / nsp, ch0 = split * kch;           // this workgroup's chunks [ch0, ch0 + kch)
+    const int kch = a.chunks >> a.lg_ksplit, ch0 = split * kch;  // this workgroup's chunks [ch0, ch0 + kch)
     float* const Cw = a.C + split * a.slab_stride;
-    const int tiles_m = per_range / tiles_n;
     const int tile_n = a.nmajor ? bid / tiles_m : bid % tiles_n;
     const int tile_m = a.nmajor ? bid - tile_n * tiles_m : bid / tiles_n;
     const int n0 = tile_n * 128;
@@ -219,13 +254,12 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     // the two raw images hold 256.
     const int HW = a.H * a.W;
     const int W2 = a.cw + 2;
-    const int tiles_x = a.cw >> 1;
-    const int tps = (a.rps >> 1) * tiles_x;
+    const int lg_tx = a.lg_tiles_x, lg_tps = a.lg_tps;          // tiles per tile row and per image segment: powers of two
     const int rpi = HW >= 128 ? HW >> 7 : 1;                    // regions per image
-    const int xblocks = a.W / a.cw;
-    const int reg = tile_m % rpi;
-    const int img0 = HW >= 128 ? tile_m / rpi : tile_m * a.nseg;
-    const int oy0 = (reg / xblocks) * a.rps, ox0 = (reg % xblocks) * a.cw;
+    const int tm_img = a.lg_rpi >= 0 ? tile_m >> a.lg_rpi : tile_m / rpi;      // wave-uniform: the scalar unit's
+    const int reg = tile_m - tm_img * rpi;
+    const int img0 = HW >= 128 ? tm_img : tile_m * a.nseg;
+    const int oy0 = (reg >> a.lg_xblocks) * a.rps, ox0 = (reg & ((1 << a.lg_xblocks) - 1)) * a.cw;
     const float* zp = a.zero;
 
     const int c4 = tid & 7;
@@ -235,9 +269,9 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int px = (tid + WINO_THREADS * i) >> 3;
-            const int seg = px / seg_px;
+            const int seg = wino_div16(px, a.mul_seg);
             const int rem = px - seg * seg_px;
-            const int hr = rem / W2, hx = rem - hr * W2;
+            const int hr = wino_div16(rem, a.mul_w2), hx = rem - hr * W2;
             const int img = img0 + seg, iy = oy0 + hr - 1, ix = ox0 + hx - 1;
             const bool ok = seg < a.nseg && img < a.B && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
             hoff[i] = ok ? (img * a.H + iy) * a.W + ix : -1;
@@ -283,11 +317,22 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     const int t_tile = (tid & 255) >> 3, t_q = tid & 7;
     int t_src;      // halo pixel of d[0][0]
     {
-        const int seg = t_tile / tps, rem = t_tile - seg * tps;
-        const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
+        const int seg = t_tile >> lg_tps, rem = t_tile & ((1 << lg_tps) - 1);
+        const int ty = rem >> lg_tx, tx = rem & ((1 << lg_tx) - 1);
         t_src = (seg * (a.rps + 2) + 2 * ty) * W2 + 2 * tx;
     }
     const int t_dst = t_tile * ROWB + (((t_q >> 1) ^ lds_swz(t_tile)) << 4) + (t_q & 1) * 8;
+    // raw-image offsets of d[vr + k][c]: a wave's two transforms read d rows vr .. vr + 2 only.  Formed once, in front of the
+    // loop AND of the peeled last chunk (left to hipcc they are hoisted per transform variant into the loop's guarded
+    // pre-header, and their ingredients spilled across the loop for the last chunk)
+    int t_ro[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            t_ro[k][c] = raw_off(t_src + (vr + k) * W2 + c, t_q);
+            asm volatile("" : "+v"(t_ro[k][c]));
+        }
     // V row 2 th + vr from two d rows: th = 0: (0: d0 - d2) (1: d1 + d2); th = 1: (2: d2 - d1) (3: d1 - d3)
     auto transform = [&](auto TH, auto VR, int rbuf) {
         constexpr int th = decltype(TH)::value, v_r = decltype(VR)::value;
@@ -299,8 +344,8 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
         f32x4 ea[4], eb[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            ea[c] = *reinterpret_cast<const f32x4*>(Rb + raw_off(t_src + ra_ * W2 + c, t_q));
-            eb[c] = *reinterpret_cast<const f32x4*>(Rb + raw_off(t_src + rb_ * W2 + c, t_q));
+            ea[c] = *reinterpret_cast<const f32x4*>(Rb + t_ro[ra_ - v_r][c]);
+            eb[c] = *reinterpret_cast<const f32x4*>(Rb + t_ro[rb_ - v_r][c]);
         }
         f32x4 r[4];
 #pragma unroll
@@ -356,8 +401,10 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
                 __builtin_bit_cast(bf16x8, bq[p & 3][lb]), __builtin_bit_cast(bf16x8, fa[la][tb]), acc[p][tb], 0, 0, 0);
     };
     // the eight positions of half h of chunk c (see wino_conv_kernel for the group order and the in-place A prefetch)
-    auto mfma_half = [&](auto HH, int c) {
+    // LAST (the final half-phase of the workgroup): no fragment is requested past the last position
+    auto mfma_half = [&](auto HH, auto LAST, int c) {
         constexpr int h = decltype(HH)::value;
+        constexpr bool last = decltype(LAST)::value;
         if constexpr ((ABL & 256) != 0) __builtin_amdgcn_s_setprio(2);       // experiment: the multiplying wave outranks its partner
         // NL = 2: three products, small terms first - V_lo U_hi, V_hi U_lo, V_hi U_hi
         if constexpr (NL == 3) read_a(8 * h, 2);
@@ -366,7 +413,7 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int p = 8 * h + i;
-            if (!(ABL & 2)) load_b(c * 16 + p + LA, bq[(p + LA) & 3]);
+            if (!(ABL & 2) && !(last && p + LA >= 16)) load_b(c * 16 + p + LA, bq[(p + LA) & 3]);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (NL == 3) {
                 mm(p, 2, 0);
@@ -416,27 +463,30 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
             }
         }
     };
-    for (int c = 0; c < kch; ++c) {
+    using No = std::false_type;
+    using Yes = std::true_type;
+
+    for (int c = 0; c < kch - 1; ++c) {         // every chunk but the last: it has a successor to stage and transform
         // HP0: MFMAs on V rows 0,1 of chunk c || V rows 2,3 of chunk c (raw image c & 1)
         stamp(c, 0);
-        if constexpr (!ERAW) load_raw(ch0 + min(c + 1, kch - 1));
+        if constexpr (!ERAW) load_raw(ch0 + c + 1);
         if (vr == 0 && !(ABL & 1)) transform(I1{}, I0{}, c & 1);             // waves 0-3: transform, then MFMAs
         __builtin_amdgcn_sched_barrier(0);
         if (vr == 0) stamp(c, 1);
-        if (live) mfma_half(I0{}, c);
+        if (live) mfma_half(I0{}, No{}, c);
         __builtin_amdgcn_sched_barrier(0);
         if (vr != 0) stamp(c, 1);
         if (vr != 0 && !(ABL & 1)) transform(I1{}, I1{}, c & 1);             // waves 4-7: MFMAs, then transform
         stamp(c, 2);
-        store_raw((c + 1) & 1, ch0 + min(c + 1, kch - 1));
+        store_raw((c + 1) & 1, ch0 + c + 1);
         stamp(c, 3);
         __syncthreads();
-        // HP1: MFMAs on V rows 2,3 of chunk c || V rows 0,1 of chunk c + 1 (raw image (c + 1) & 1; stale for the last chunk)
+        // HP1: MFMAs on V rows 2,3 of chunk c || V rows 0,1 of chunk c + 1 (raw image (c + 1) & 1)
         stamp(c, 4);
         if (vr == 0 && !(ABL & 1)) transform(I0{}, I0{}, (c + 1) & 1);
         __builtin_amdgcn_sched_barrier(0);
         if (vr == 0) stamp(c, 5);
-        if (live) mfma_half(I1{}, c);
+        if (live) mfma_half(I1{}, No{}, c);
         __builtin_amdgcn_sched_barrier(0);
         if (vr != 0) stamp(c, 5);
         if constexpr (ERAW) load_raw(ch0 + min(c + 2, kch - 1));
@@ -445,63 +495,124 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
         __syncthreads();
         stamp(c, 7);
     }
+    // The last chunk, straight-line (the first one when c_in = 32): nothing follows it, so no raw image is loaded or stored, no V
+    // rows 0,1 are formed, no fragment is requested past position 15 and no barrier closes it - the waves go into the output
+    // transform as their own MFMAs end.  (Outside the loop: hipcc's accumulator code degrades with a "last" test inside it.)
+    {
+        int c = kch - 1;
+        asm volatile("" : "+s"(c));     // opaque until here: the chunk's LDS addresses are formed now, not carried through the loop
+        stamp(c, 0);
+        if (vr == 0 && !(ABL & 1)) transform(I1{}, I0{}, c & 1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (vr == 0) stamp(c, 1);
+        if (live) mfma_half(I0{}, No{}, c);
+        __builtin_amdgcn_sched_barrier(0);
+        if (vr != 0) stamp(c, 1);
+        if (vr != 0 && !(ABL & 1)) transform(I1{}, I1{}, c & 1);
+        stamp(c, 2);
+        stamp(c, 3);
+        __syncthreads();
+        stamp(c, 4);
+        __builtin_amdgcn_sched_barrier(0);
+        stamp(c, 5);                    // no transform in this half-phase: slots 5 and 6 bracket the MFMAs alone
+        if (live) mfma_half(I1{}, Yes{}, c);
+        __builtin_amdgcn_sched_barrier(0);
+        stamp(c, 6);
+        stamp(c, 7);
+    }
 
     // ---- output transform + fused epilogue (as wino_conv_kernel) -----------------------------------------------------
+    // Few registers and few vector instructions beside the accumulators: A^T m A in place (the same order of additions), one
+    // scalar base per operand at the region's first pixel and 32-bit byte offsets from it (the host bounds the row strides),
+    // the time-embedding row once per tile block where it is one row per image.
     if (!live) return;      // no barrier follows
+    // Operands: all requested here, in front of the arithmetic.  (Requested in front of the last MFMA half-phase instead, they
+    // made the 32x32 launches 1-2 % slower: profiles/r08/README.md.)  Pixels count from the region's first one (org): a tile's
+    // first pixel is rel = seg * H * W + 2 ty * W + 2 tx, and a tile of an image beyond the batch reads pixel org (in range:
+    // img0 < B) and stores nothing.
     const PsldEpilogue& e = a.e;
     const int cn = n0 + wave * 16 + 4 * kq;
+    const int org = (img0 * a.H + oy0) * a.W + ox0;
     const f32x4v zero4 = {0.f, 0.f, 0.f, 0.f};
-    const f32x4v bias4 = e.bias ? *reinterpret_cast<const f32x4v*>(e.bias + cn) : zero4;
+    const bool rb_div = e.rowbias && !a.rb_img;
+    char* const c_b = reinterpret_cast<char*>(Cw + (long long)org * a.ldc);                           // wave-uniform bases
+    const char* const res_b = reinterpret_cast<const char*>(e.res ? e.res + (long long)org * e.ldres : zp);
+    f32x4v epi_bias, epi_tbv[2], epi_rv[2][4], epi_cv[2][4];
+    int epi_rel[2];
+    bool epi_ok[2];
+    auto epi_rows = [&](auto TB) {        // residual and previous-output rows of the four pixels of tile block tb
+        constexpr int tb = decltype(TB)::value;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int px = epi_rel[tb] + (j >> 1) * a.W + (j & 1);
+            epi_rv[tb][j] = e.res ? *reinterpret_cast<const f32x4v*>(res_b + (unsigned)((px * e.ldres + cn) * 4)) : zero4;
+            epi_cv[tb][j] = e.accumulate ? *reinterpret_cast<const f32x4v*>(c_b + (unsigned)((px * a.ldc + cn) * 4)) : zero4;
+        }
+    };
+    auto epi_request = [&]() {
+        epi_bias = e.bias ? *reinterpret_cast<const f32x4v*>(e.bias + cn) : zero4;
+#pragma unroll
+        for (int tb = 0; tb < 2; ++tb) {
+            const int tile = tb * 16 + r16;
+            const int seg = tile >> lg_tps, rem = tile & ((1 << lg_tps) - 1);
+            const int ty = rem >> lg_tx, tx = rem & ((1 << lg_tx) - 1);
+            epi_ok[tb] = img0 + seg < a.B;                  // whole images only: a tile is in range or not
+            epi_rel[tb] = epi_ok[tb] ? seg * HW + 2 * ty * a.W + 2 * tx : 0;
+            // the row bias as one row per image: the tile's image (the region's first for a tile beyond the batch)
+            epi_tbv[tb] = a.rb_img ? *reinterpret_cast<const f32x4v*>(
+                                         e.rowbias + (long long)(epi_ok[tb] ? img0 + seg : img0) * e.ld_rowbias + cn)
+                                   : zero4;
+        }
+        epi_rows(I0{});
+    };
+    epi_request();
+    epi_rows(I1{});
+    const f32x4v bias4 = epi_bias;
 #pragma unroll
     for (int tb = 0; tb < 2; ++tb) {
-        const int tile = tb * 16 + r16;
-        const int seg = tile / tps, rem = tile - seg * tps;
-        const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
-        const int gm00 = ((img0 + seg) * a.H + oy0 + 2 * ty) * a.W + ox0 + 2 * tx;
-        const bool ok = img0 + seg < a.B;                   // whole images only: a tile is in range or not
-        f32x4v s[4][2];
+        const bool ok = epi_ok[tb];
+        const int rel = epi_rel[tb];
+        // m -> m A per row of positions (columns (0 + 1 + 2), (1 - 2 - 3)), left in the accumulators of columns 0 and 1
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            s[i][0] = (acc[4 * i][tb] + acc[4 * i + 1][tb]) + acc[4 * i + 2][tb];
-            s[i][1] = (acc[4 * i + 1][tb] - acc[4 * i + 2][tb]) - acc[4 * i + 3][tb];
+            const f32x4v s0 = (acc[4 * i][tb] + acc[4 * i + 1][tb]) + acc[4 * i + 2][tb];
+            acc[4 * i + 1][tb] = (acc[4 * i + 1][tb] - acc[4 * i + 2][tb]) - acc[4 * i + 3][tb];
+            acc[4 * i][tb] = s0;
         }
-        f32x4v y[2][2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            y[0][b] = (s[0][b] + s[1][b]) + s[2][b];
-            y[1][b] = (s[1][b] - s[2][b]) - s[3][b];
-        }
-        float gs = 0.f, gss = 0.f;
-        const int gmc = ok ? gm00 : 0;
-        f32x4v rv[2][2], cv[2][2], tbv[2][2];
+        const f32x4v add4 = bias4 + epi_tbv[tb];
+        f32x4v o[2][2];
 #pragma unroll
         for (int ya = 0; ya < 2; ++ya)
 #pragma unroll
             for (int xb = 0; xb < 2; ++xb) {
-                const int gm = gmc + ya * a.W + xb;
-                rv[ya][xb] = e.res ? *reinterpret_cast<const f32x4v*>(e.res + (long long)gm * e.ldres + cn) : zero4;
-                cv[ya][xb] = e.accumulate ? *reinterpret_cast<const f32x4v*>(Cw + (long long)gm * a.ldc + cn) : zero4;
-                tbv[ya][xb] = e.rowbias ? *reinterpret_cast<const f32x4v*>(e.rowbias + (long long)(gm / e.rows_per_img) * e.ld_rowbias + cn)
-                                        : zero4;
+                const f32x4v y = ya == 0 ? (acc[xb][tb] + acc[4 + xb][tb]) + acc[8 + xb][tb]
+                                         : (acc[4 + xb][tb] - acc[8 + xb][tb]) - acc[12 + xb][tb];
+                f32x4v addv = add4;
+                if (rb_div)     // a row bias of another granularity (none of the networks' launches): the row of each pixel
+                    addv = bias4 + *reinterpret_cast<const f32x4v*>(
+                                       e.rowbias + (long long)((org + rel + ya * a.W + xb) / e.rows_per_img) * e.ld_rowbias + cn);
+                f32x4v x = y * e.alpha + addv;
+                if (e.res) x += epi_rv[tb][ya * 2 + xb];
+                x *= e.out_scale;
+                if (e.accumulate) x += epi_cv[tb][ya * 2 + xb];
+                o[ya][xb] = x;
             }
+        float gs = 0.f, gss = 0.f;
+        if (ok) {
 #pragma unroll
-        for (int ya = 0; ya < 2; ++ya)
+            for (int ya = 0; ya < 2; ++ya)
 #pragma unroll
-            for (int xb = 0; xb < 2; ++xb) {
-                const int gm = gmc + ya * a.W + xb;
-                f32x4v o = y[ya][xb] * e.alpha + (bias4 + tbv[ya][xb]);
-                if (e.res) o += rv[ya][xb];
-                o *= e.out_scale;
-                if (e.accumulate) o += cv[ya][xb];
-                if (ok && !((ABL & 8) && gm != 0)) {
-                    *reinterpret_cast<f32x4v*>(Cw + (long long)gm * a.ldc + cn) = o;
+                for (int xb = 0; xb < 2; ++xb) {
+                    const int px = rel + ya * a.W + xb;
+                    if ((ABL & 8) && org + px != 0) continue;
+                    *reinterpret_cast<f32x4v*>(c_b + (unsigned)((px * a.ldc + cn) * 4)) = o[ya][xb];
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
-                        gs += o[v];
-                        gss += o[v] * o[v];
+                        gs += o[ya][xb][v];
+                        gss += o[ya][xb][v] * o[ya][xb][v];
                     }
                 }
-            }
+        }
         if (e.gn_part) {
             float s1 = gs, s2 = gss;
 #pragma unroll
@@ -541,7 +652,10 @@ int launch_wino8s(const WinoArgs& a, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)VBYTES / 3 * NL + 2 * (size_t)4 * 64 * 128;
     static_assert(LDS <= 163840, "LDS budget");
     if (int st = psld_lds_once<&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>>(LDS, name)) return st;
-    dim3 grid((unsigned)(cdiv(a.M, 128) * cdiv(a.N, 128) * (a.ksplit > 1 ? a.ksplit : 1)));
+    // the kernel finds its (chunk range, channel tile, pixel tile) from tiles_m and lg_ksplit, not from gridDim
+    PSLD_CHECK_ARG(a.tiles_m == cdiv(a.M, 128) && (1 << a.lg_ksplit) == (a.ksplit > 1 ? a.ksplit : 1),
+                   "%s: launch geometry not filled in (tiles_m %d, ksplit %d)", name, a.tiles_m, a.ksplit);
+    dim3 grid((unsigned)(a.tiles_m * cdiv(a.N, 128) * (a.ksplit > 1 ? a.ksplit : 1)));
     hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>), grid, dim3(WINO_THREADS), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
@@ -763,6 +877,9 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
     PSLD_CHECK_ARG(ldy % 4 == 0 && aligned16(y) && (!e.res || (e.ldres % 4 == 0 && aligned16(e.res))) &&
                        (!e.bias || aligned16(e.bias)) && (!e.rowbias || (e.ld_rowbias % 4 == 0 && aligned16(e.rowbias))),
                    "limb kernels: y, residual, bias and rowbias need 16-byte aligned rows (pointer and row stride)");
+    // the epilogue addresses a region's operands by 32-bit byte offsets from its first pixel: below 512 pixels x row stride
+    PSLD_CHECK_ARG(ldy > 0 && ldy < (1 << 20) && (!e.res || (e.ldres > 0 && e.ldres < (1 << 20))),
+                   "psld_conv3x3_wino_*: row strides of y and the residual must be below 2^20 elements");
     a.zero = psld_detail_zero_page("psld_conv3x3_wino_f32");
     if (!a.zero) return PSLD_ERR_LAUNCH;
     a.nmajor = 1;       // channel-tile-major: an XCD streams ONE 128-channel slice of U at a time (pixel-tile-major measured 1-2 % slower)
@@ -772,6 +889,18 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
         a.cw = 32; a.rps = 4; a.nseg = 1;
         halo_px = 6 * 34;
     }
+    // the kernel's divisors (WinoArgs): every one a power of two or on the proven multiply-shift list
+    a.tiles_m = cdiv(a.M, 128);
+    a.lg_tiles_x = wino_lg2(a.cw >> 1);
+    a.lg_tps = wino_lg2((a.rps >> 1) * (a.cw >> 1));
+    a.lg_xblocks = wino_lg2(w / a.cw);
+    a.lg_rpi = h * w >= 128 ? wino_lg2((h * w) >> 7) : 0;
+    a.lg_ksplit = 0;
+    a.mul_seg = wino_mul16((a.rps + 2) * (a.cw + 2));
+    a.mul_w2 = wino_mul16(a.cw + 2);
+    a.rb_img = e.rowbias && e.rows_per_img == h * w;
+    PSLD_CHECK_ARG(wino_geo_listed(a.rps, a.cw) && a.lg_tiles_x >= 0 && a.lg_tps >= 0 && a.lg_xblocks >= 0,
+                   "psld_conv3x3_wino_*: no divisor table for the geometry of %dx%d", h, w);
     if (gn) {
         a.gsc1 = gn->sc1; a.gsh1 = gn->sh1; a.gsc2 = gn->sc2; a.gsh2 = gn->sh2; a.gn_act = gn->act;
     }
@@ -783,6 +912,8 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
     if (ks > 1 && (!e.gn_part || psld_detail_conv_reduce_gn_ok(a.M, cout, e)) && ws_bytes >= (long long)ks * a.M * cout * 4 && aligned16(workspace)) {
         WinoArgs s = a;
         s.ksplit = ks;
+        s.lg_ksplit = wino_lg2(ks);        // a power of two (psld_conv3x3_wino_ksplit)
+        s.rb_img = 0;
         s.slab_stride = (long long)a.M * cout;
         s.C = reinterpret_cast<float*>(workspace);
         s.ldc = cout;

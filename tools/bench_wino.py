@@ -1,7 +1,12 @@
 """Winograd F(2x2,3x3) limb convolution (psld_conv3x3_wino_f32) against the direct limb kernels, interleaved rounds in
 ONE process, random data: direct-conv-equivalent TFLOP/s (2*M*N*9*Cin / time) and rel-L2 against fp64 torch.
-    python tools/bench_wino.py [--rounds 5] [--iters 10] [--batch 128] [--check]"""
+    python tools/bench_wino.py [--rounds 5] [--iters 10] [--batch 128] [--check]
+--wino-only times the Winograd launch alone and prints one JSON line per shape (chunks per workgroup, workgroups, median and
+best microseconds): two builds of the library are compared by alternating such runs in separate processes under PSLD_HIP_LIB
+(profiles/r08: the split of a workgroup's time into a fixed part and a part per 32-channel chunk).  --allow-split hands the
+launch its split-chunk workspace where the grid is small (the 8x8 level)."""
 import argparse
+import json
 import os
 import sys
 
@@ -84,6 +89,8 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--epi", default="res", help="epilogue of the timed launches: plain | bias | res (bias + residual + scale)")
     ap.add_argument("--fused-gn", action="store_true", help="GroupNorm apply + SiLU: separate pass + convolution vs fused into the staging")
+    ap.add_argument("--wino-only", action="store_true", help="time conv3x3_wino alone, one JSON line per shape")
+    ap.add_argument("--allow-split", action="store_true", help="with --wino-only: split-chunk launches where the grid is small")
     ap.add_argument("--shapes", default="256,256,32;512,256,32;256,256,16;512,256,16;256,256,8")
     args = ap.parse_args()
     ops.lib()
@@ -125,6 +132,15 @@ def main():
             print(f"conv fwd {cin}->{cout} @{s} B={B} GN+SiLU: apply pass + conv {ma * 1e6:7.1f} us (conv alone {mc * 1e6:7.1f})  "
                   f"fused {mb * 1e6:7.1f} us  x{ma / mb:.3f} vs two passes, conv {mb / mc - 1:+.1%} per launch  bitwise equal: {torch.equal(ya, yb)}",
                   flush=True)
+            continue
+        if args.wino_only:
+            split = args.allow_split
+            ks = int(ops.lib().psld_conv3x3_wino_ksplit(cin, 0, B, s, s, cout)) if split else 1
+            ts = [timeit(lambda: ops.conv3x3_wino(x, None, uf, cout, y2, epi, allow_split=split), args.iters)
+                  for _ in range(args.rounds)]
+            print(json.dumps({"shape": f"{cin}->{cout}@{s}", "batch": B, "chunks_per_wg": cin // 32 // ks,
+                              "workgroups": B * s * s // 128 * (cout // 128) * ks, "ksplit": ks,
+                              "median_us": round(sorted(ts)[len(ts) // 2] * 1e6, 2), "best_us": round(min(ts) * 1e6, 2)}), flush=True)
             continue
         xl = ops.f32_to_limb(x)
         fl = 2.0 * B * s * s * cout * 9 * cin
