@@ -44,12 +44,21 @@ const char* psld_last_error(void);
  *                    hi*hi + (hi*lo + lo*hi); the dropped terms are each < 2^-16 of the product (rel-L2 ~1e-5 on a whole
  *                    network forward).  The library only stores this value: which launches use the two-limb entry
  *                    points is the caller's choice (psld_amd: forwards that record no backward pass).
- * Process-wide; the initial value comes from the environment variable PSLD_MATH ("f32" | "bf16x6" | "bf16x3"). */
+ * Process-wide; the initial value comes from the environment variable PSLD_MATH ("f32" | "bf16x6" | "bf16x3" |
+ * "bf16x3_train": mode PSLD_MATH_BF16X3 with record math PSLD_MATH_BF16X3, below). */
 #define PSLD_MATH_F32 0
 #define PSLD_MATH_BF16X6 1
 #define PSLD_MATH_BF16X3 2
 int psld_set_math_mode(int mode);
 int psld_get_math_mode(void);
+/* Arithmetic of the passes that record a backward pass (training steps, the classifier's guidance pass): PSLD_MATH_BF16X6
+ * (default: every launch of such a pass is the three-limb one, whatever the math mode) or PSLD_MATH_BF16X3 (opt-in: under a limb
+ * math mode the pass takes the two-limb entry points where one exists - Winograd 3x3 forward and data gradient, pointwise forward
+ * and data gradient, Winograd-domain weight gradient psld_conv3x3_wgrad_wino_x3_f32; gradients ~1e-5 rel-L2 from fp32).  Like the
+ * math mode the library only stores the value; any other value is refused.  Initial value: PSLD_MATH_BF16X3 when PSLD_MATH is
+ * "bf16x3_train", else PSLD_MATH_BF16X6. */
+int psld_set_record_math(int mode);
+int psld_get_record_math(void);
 
 /* ---- fused epilogue of every MFMA tile kernel ------------------------------------------
  * value = ((alpha * acc + bias[n] + rowbias[m / rows_per_img][n] + residual[m][n]) * out_scale)
@@ -198,12 +207,14 @@ int psld_conv3x3_wino_gn_ws_f32(const float* x1, int c1, const float* scale1, co
                                 void* workspace, long long ws_bytes, hipStream_t stream);
 
 /* Two-limb (PSLD_MATH_BF16X3) forms of the Winograd forward: fragments of two limb planes [...][16 pos][2 limbs][64 lanes]
- * (cout*cin*16*4 bytes + the same prefetch pad; the planes are the hi and mid planes of psld_pack_conv3x3_wino, forward
- * orientation only; psld_pack_wino_batch_x3 takes psld_pack_wino_batch's table), V split in two limbs, three products per
- * accumulator.  Shapes: psld_conv3x3_wino_supported / psld_conv3x3_wino_gn_supported; workspace: NULL, or
+ * (cout*cin*16*4 bytes + the same prefetch pad; the planes are the hi and mid planes of psld_pack_conv3x3_wino: dgrad = 0
+ * from psld_pack_conv3x3_wino_x3, dgrad = 1 - the data gradient is the same kernel on those fragments - from
+ * psld_pack_conv3x3_wino_dgrad_x3; psld_pack_wino_batch_x3 takes psld_pack_wino_batch's table, rows of either orientation), V
+ * split in two limbs, three products per accumulator.  Shapes: psld_conv3x3_wino_supported / psld_conv3x3_wino_gn_supported; workspace: NULL, or
  * psld_conv3x3_wino_ws_bytes bytes (the launches psld_conv3x3_wino_ksplit splits, split the same way).  Epilogue as above. */
 long long psld_conv3x3_wino_frag_bytes_x3(int cout, int cin);
 int psld_pack_conv3x3_wino_x3(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream);
+int psld_pack_conv3x3_wino_dgrad_x3(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream);
 int psld_pack_wino_batch_x3(const long long* table_dev, int entries, long long total_items, hipStream_t stream);
 int psld_conv3x3_wino_x3_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
                              const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
@@ -238,7 +249,7 @@ int psld_pack_gemm_frag(const float* b, void* bfrag, int n, int k, long long str
 int psld_gemm_split_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
                         float* y, int ldy, const psld_epilogue_t* epi, void* workspace, long long ws_bytes,
                         hipStream_t stream);
-/* Two-limb (PSLD_MATH_BF16X3) form of the forward GEMM: fragments of the hi and mid planes only (n*k*4 bytes;
+/* Two-limb (PSLD_MATH_BF16X3) form of the forward GEMM (and, on fragments packed with n and k swapped, of its data gradient): fragments of the hi and mid planes only (n*k*4 bytes;
  * psld_pack_frag_batch_x3 takes psld_pack_frag_batch's table, taps = 1), rows split in two limbs, three products per
  * accumulator, every epilogue of psld_gemm_split_f32.  Always the eight-wave kernel of 128 x 256 tiles: shapes of
  * psld_gemm_split_supported with n a multiple of 256 (psld_gemm_split_f32 takes that kernel from 128 tiles on - below, its
@@ -296,6 +307,12 @@ long long psld_conv3x3_wgrad_wino_ws_bytes(int cout, int cin_total, int nsplit);
 int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, const float* x, int cin, const float* x2, int cin2,
                                 int batch, int h, int w, float* slabs, int nsplit, float* dw_oihw, int accumulate,
                                 float alpha, hipStream_t stream);
+/* The same launch on two limbs per operand (record math PSLD_MATH_BF16X3): the transformed values keep limbs 0 and 1 of the
+ * three-limb split, bit for bit, and a product is hi*mid + mid*hi + hi*hi (smallest first) - half the MFMAs.  Shapes, splits,
+ * workspace (*_supported, *_nsplit, *_ws_bytes above) and the reduction are those of psld_conv3x3_wgrad_wino_f32. */
+int psld_conv3x3_wgrad_wino_x3_f32(const float* dy, int lddy, int cout, const float* x, int cin, const float* x2, int cin2,
+                                   int batch, int h, int w, float* slabs, int nsplit, float* dw_oihw, int accumulate,
+                                   float alpha, hipStream_t stream);
 /* Pointwise weight gradient on the limb kernels: slabs[s][i][j] (row stride ldc) = sum over the s-th range of
  * ceil(k/32 / nsplit) 32-row tiles of a[p][i] * b[p][j]  (a: [k][m] rows of lda floats, b: [k][n] rows of ldb floats;
  * b2 / ldb2 / n2 (null / 0 / 0 for none): further columns [n, n + n2) of B from a second tensor (concatenation);

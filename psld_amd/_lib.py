@@ -73,6 +73,8 @@ SIGNATURES = {
     "psld_last_error": (C.c_char_p, []),
     "psld_set_math_mode": (I, [I]),
     "psld_get_math_mode": (I, []),
+    "psld_set_record_math": (I, [I]),
+    "psld_get_record_math": (I, []),
     "psld_set_gn_bwd_kernel": (I, [I]),
     "psld_get_gn_bwd_kernel": (I, []),
     "psld_gemm_f32": (I, [I, I, I, I, I, P, I, LL, P, I, LL, P, I, LL, I, EP, P]),
@@ -101,6 +103,7 @@ SIGNATURES = {
     "psld_conv3x3_wino_gn_ws_f32": (I, [P, I, P, P, P, I, P, P, I, I, I, I, P, I, P, I, EP, P, LL, P]),
     "psld_conv3x3_wino_frag_bytes_x3": (LL, [I, I]),
     "psld_pack_conv3x3_wino_x3": (I, [P, P, I, I, P]),
+    "psld_pack_conv3x3_wino_dgrad_x3": (I, [P, P, I, I, P]),
     "psld_pack_wino_batch_x3": (I, [P, I, LL, P]),
     "psld_conv3x3_wino_x3_f32": (I, [P, I, P, I, I, I, I, P, I, P, I, EP, P, LL, P]),
     "psld_conv3x3_wino_gn_x3_f32": (I, [P, I, P, P, P, I, P, P, I, I, I, I, P, I, P, I, EP, P, LL, P]),
@@ -126,6 +129,7 @@ SIGNATURES = {
     "psld_conv3x3_wgrad_wino_nsplit": (I, [I, I, I, I, I]),
     "psld_conv3x3_wgrad_wino_ws_bytes": (LL, [I, I, I]),
     "psld_conv3x3_wgrad_wino_f32": (I, [P, I, I, P, I, P, I, I, I, I, P, I, P, I, F, P]),
+    "psld_conv3x3_wgrad_wino_x3_f32": (I, [P, I, I, P, I, P, I, I, I, I, P, I, P, I, F, P]),
     "psld_gemm_tn_split_supported": (I, [I, I, I]),
     "psld_gemm_tn_split_f32": (I, [I, I, I, P, I, P, I, P, I, I, P, I, I, P]),
     "psld_gemm_tail_supported": (I, [I, I, I]),

@@ -503,6 +503,11 @@ def build_parser() -> argparse.ArgumentParser:
             p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32"],
                            help="arithmetic of the network evaluations (ops.set_math_mode; default: the process's mode, "
                                 "PSLD_MATH); bf16x3 = two-limb reduced-precision inference")
+        if name in ("train", "train_clf"):
+            p.add_argument("--train-math", default=None, choices=["bf16x6", "bf16x3"],
+                           help="arithmetic of the passes that record a backward pass (ops.set_record_math; default: the "
+                                "process's setting); bf16x3 = two-limb forward, data-gradient and Winograd weight-gradient "
+                                "launches, gradients ~1e-5 rel-L2 from fp32")
     return ap
 
 
@@ -513,6 +518,9 @@ def main(argv=None):
     if getattr(args, "math", None):         # before the network is built
         from psld_amd import ops
         ops.set_math_mode(args.math)
+    if getattr(args, "train_math", None):
+        from psld_amd import ops
+        ops.set_record_math(args.train_math)
     {"train": train, "sample": sample, "inpaint": inpaint, "train_clf": train_clf,
      "cc_sample": cc_sample}[args.cmd](args, overrides)
 

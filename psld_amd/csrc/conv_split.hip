@@ -42,11 +42,18 @@ namespace {
 constexpr int TAP_U4 = 4 * 3 * 64;   // uint4 per (wave column, tap, 32-channel chunk): [n-block 4][limb 3][lane 64]
 
 int g_math_mode = -1;
+int g_record_math = -1;     // arithmetic of passes that record a backward pass (psld_set_record_math)
+// PSLD_MATH is read once, by whichever getter runs first: "bf16x3_train" = math mode bf16x3 + record math bf16x3.  A value
+// set through the C ABI before that stays.
+inline void math_from_env() {
+    const char* e = getenv("PSLD_MATH");
+    const bool train = e && !strcmp(e, "bf16x3_train");
+    if (g_math_mode < 0)
+        g_math_mode = (e && !strcmp(e, "f32")) ? PSLD_MATH_F32 : ((e && !strcmp(e, "bf16x3")) || train) ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
+    if (g_record_math < 0) g_record_math = train ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
+}
 inline int math_mode() {
-    if (g_math_mode < 0) {
-        const char* e = getenv("PSLD_MATH");
-        g_math_mode = (e && !strcmp(e, "f32")) ? PSLD_MATH_F32 : (e && !strcmp(e, "bf16x3")) ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
-    }
+    if (g_math_mode < 0) math_from_env();
     return g_math_mode;
 }
 
@@ -1999,6 +2006,17 @@ extern "C" int psld_set_math_mode(int mode) {
 }
 
 extern "C" int psld_get_math_mode(void) { return math_mode(); }
+
+extern "C" int psld_set_record_math(int mode) {
+    PSLD_CHECK_ARG(mode == PSLD_MATH_BF16X6 || mode == PSLD_MATH_BF16X3, "psld_set_record_math: unknown mode %d", mode);
+    g_record_math = mode;
+    return PSLD_OK;
+}
+
+extern "C" int psld_get_record_math(void) {
+    if (g_record_math < 0) math_from_env();
+    return g_record_math;
+}
 
 extern "C" long long psld_conv3x3_frag_bytes(int cout, int cin) { return (long long)cout * cin * 9 * 6; }
 

@@ -222,7 +222,7 @@ __global__ void wino_pack_batch_kernel(const long long* __restrict__ tab, int nt
 // TAIL (cout % 128 != 0 only): the last channel tile holds 32, 64 or 96 channels; the waves beyond cout take their share of the
 // staging and the transform (and the barriers) but load no fragments, issue no MFMAs and leave before the epilogue.  Every
 // live wave does exactly what it does in a full tile, so a channel's result does not depend on how many share its launch.
-// NL = 2 (PSLD_MATH_BF16X3, forward only): V and U keep their first two limbs (split2) and a product is the three limb
+// NL = 2 (PSLD_MATH_BF16X3; the data gradient is this kernel on dgrad = 1 fragments): V and U keep their first two limbs (split2) and a product is the three limb
 // products hi*hi + (hi*lo + lo*hi): V image [pos][2][tile][32 ch] (64 KB), fragments [...][16 pos][2 limbs][64 lanes], per
 // chunk and wave 16 positions x (4 ds_read_b128 + 2 fragment loads + 6 MFMAs).  Everything else is the NL = 3 kernel.
 template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3>
@@ -734,6 +734,18 @@ extern "C" int psld_pack_conv3x3_wino_x3(const float* w_oihw, void* ufrag, int c
     hipLaunchKernelGGL(wino_pack_kernel<2>, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag), cout, cin,
                        (long long)cin * 9, 9LL, 0);
     PSLD_CHECK_LAUNCH("psld_pack_conv3x3_wino_x3");
+    return PSLD_OK;
+}
+
+// the data-gradient orientation on two limbs (record math PSLD_MATH_BF16X3): psld_pack_conv3x3_wino(..., dgrad = 1)'s planes 0 and 1
+extern "C" int psld_pack_conv3x3_wino_dgrad_x3(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream) {
+    PSLD_CHECK_ARG(w_oihw && ufrag && aligned16(ufrag), "psld_pack_conv3x3_wino_dgrad_x3: null / unaligned pointer");
+    PSLD_CHECK_ARG(cin >= 128 && cout > 0 && cin % 32 == 0 && cout % 32 == 0,
+                   "psld_pack_conv3x3_wino_dgrad_x3: needs in channels %%32 (>= 128) and out channels %%32 (got %d, %d)", cin, cout);
+    const long long items = (long long)(cin / 16) * (cout / 32) * 64;
+    hipLaunchKernelGGL(wino_pack_kernel<2>, dim3(psld_grid_blocks(items, 64, 16384)), dim3(64), 0, stream, w_oihw,
+                       reinterpret_cast<u32x4*>(ufrag), cin, cout, 9LL, (long long)cin * 9, 1);
+    PSLD_CHECK_LAUNCH("psld_pack_conv3x3_wino_dgrad_x3");
     return PSLD_OK;
 }
 

@@ -19,13 +19,16 @@
 // global memory / L2 (the 16 x c_in-tile workgroups of one K range sit on ONE XCD and walk it in step: one HBM fetch).
 //
 // Shape of the kernel (the skeleton of dwgrad_ws_kernel, conv_split.hip):
-//   512 threads, one workgroup per CU, 156 KB of LDS = two images of { dY-side [3 limbs][32 tiles][256 ch], x-side [3][32][128] };
+//   512 threads, one workgroup per CU, 156 KB of LDS = two images of { dY-side [NL limbs][32 tiles][256 ch], x-side [NL][32][128] }
+//     at NL = 3 limbs (the default arithmetic); the two-limb form NL = 2 (record math 'bf16x3',
+//     psld_conv3x3_wgrad_wino_x3_f32) keeps two images of two limbs, 104 KB, and leaves the rest of the LDS unused;
 //   waves 4-7 (producers): per K tile of 32 Winograd tiles, thread = (tile, channel quad) items - 4 x-items of 4 loads, 8
-//     dY-items of 1 / 2 / 4 loads - combine, split3, ds_write_b64 per limb into the NEXT image; every item has a register slot
-//     that is refilled with the same item of the tile after as soon as it is consumed (a whole K tile for a load to land);
+//     dY-items of 1 / 2 / 4 loads - combine, split3 (NL = 2: split2, its first two limbs), ds_write_b64 per limb into the NEXT
+//     image; every item has a register slot that is refilled with the same item of the tile after as soon as it is consumed
+//     (a whole K tile for a load to land);
 //   waves 0-3 (consumers): 128 (c_out) x 64 (c_in) each = 8 x 4 blocks of v_mfma_f32_16x16x32_bf16 x 6 limb products = 192 MFMAs
-//     per K tile on transposed fragment reads (ds_read_b64_tr_b16, k slot = tile 4g + 16j + q as in dwgrad_kernel), 128
-//     accumulator registers;
+//     per K tile (NL = 2: the three products hi.mid, mid.hi, hi.hi, smallest first = 96 MFMAs) on transposed fragment reads
+//     (ds_read_b64_tr_b16, k slot = tile 4g + 16j + q as in dwgrad_kernel), 128 accumulator registers;
 //   one barrier per K tile; slabs[split][position][c_out][c_in] -> wwgrad_reduce_kernel: sum over the splits in fixed order,
 //     G^T . G with the folded signs, written (or added) to the OIHW gradient.
 // Signs: A's last row is [0, -1]: the dY-side values of positions with i = 3 or j = 3 are formed WITHOUT that sign (one load,
@@ -46,12 +49,12 @@ __device__ __forceinline__ u32x2 lds_tr16(const unsigned char* p) {
 constexpr int WW_CI = 128;                       // c_in per workgroup; c_out per workgroup CO = 256 (128 for layers of 128 output channels)
 constexpr int WW_RSB = WW_CI * 2 + 32;           // 288: x-side row stride (bytes per tile row and limb); 32 mod 256 like pwgrad_kernel's:
 constexpr int WW_BLIMB = 32 * WW_RSB;            // eight consecutive rows cover all 64 banks
-template <int CO>
+template <int CO, int NL = 3>
 struct WWGeom {
     static constexpr int RSA = CO * 2 + 32;      // 544 / 288: dY-side row stride
     static constexpr int ALIMB = 32 * RSA;
-    static constexpr int IMG = 3 * (ALIMB + WW_BLIMB);           // 79 872 / 55 296 bytes
-    static constexpr size_t LDS = 2 * (size_t)IMG;               // 159 744 / 110 592
+    static constexpr int IMG = NL * (ALIMB + WW_BLIMB);          // 79 872 / 55 296 bytes (two limbs: 53 248 / 36 864)
+    static constexpr size_t LDS = 2 * (size_t)IMG;               // 159 744 / 110 592 (two limbs: 106 496 / 73 728)
     static constexpr int NY = CO / 32;           // dY items per producer thread and K tile (8 / 4)
     static constexpr int CB = CO / 32;           // 16-channel c_out blocks per consumer wave (wave tile CO/2 x 64)
 };
@@ -103,19 +106,34 @@ __device__ __forceinline__ void ww_split3(float x0, float x1, unsigned& hi, unsi
     lo = ww_cvt_pk(s0, s1);
 }
 
-template <int ABL = 0>
+// limbs 0 and 1 of ww_split3, bit for bit (limb.h's split2)
+__device__ __forceinline__ void ww_split2(float x0, float x1, unsigned& hi, unsigned& mid) {
+    hi = ww_cvt_pk(x0, x1);
+    const float r0 = x0 - __uint_as_float(hi << 16), r1 = x1 - __uint_as_float(hi & 0xffff0000u);
+    mid = ww_cvt_pk(r0, r1);
+}
+
+template <int ABL = 0, int NL = 3>
 __device__ __forceinline__ void ww_store(unsigned char* d, int limb_stride, const f32x4& v) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    if constexpr ((ABL & 1) != 0) {
-        h0 = m0 = l0 = __float_as_uint(v[0]) ^ __float_as_uint(v[1]);
-        h1 = m1 = l1 = __float_as_uint(v[2]) ^ __float_as_uint(v[3]);
+    if constexpr (NL == 2) {
+        unsigned h0, m0, h1, m1;
+        ww_split2(v[0], v[1], h0, m0);
+        ww_split2(v[2], v[3], h1, m1);
+        *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
+        *reinterpret_cast<u32x2*>(d + limb_stride) = u32x2{m0, m1};
     } else {
-        ww_split3(v[0], v[1], h0, m0, l0);
-        ww_split3(v[2], v[3], h1, m1, l1);
+        unsigned h0, m0, l0, h1, m1, l1;
+        if constexpr ((ABL & 1) != 0) {
+            h0 = m0 = l0 = __float_as_uint(v[0]) ^ __float_as_uint(v[1]);
+            h1 = m1 = l1 = __float_as_uint(v[2]) ^ __float_as_uint(v[3]);
+        } else {
+            ww_split3(v[0], v[1], h0, m0, l0);
+            ww_split3(v[2], v[3], h1, m1, l1);
+        }
+        *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
+        *reinterpret_cast<u32x2*>(d + limb_stride) = u32x2{m0, m1};
+        *reinterpret_cast<u32x2*>(d + 2 * limb_stride) = u32x2{l0, l1};
     }
-    *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
-    *reinterpret_cast<u32x2*>(d + limb_stride) = u32x2{m0, m1};
-    *reinterpret_cast<u32x2*>(d + 2 * limb_stride) = u32x2{l0, l1};
 }
 
 __device__ __forceinline__ f32x4 bload(const __amdgpu_buffer_rsrc_t& r, unsigned off) {
@@ -139,9 +157,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t brsrc(const float* p) {
 // TAIL (cout or c_in not a multiple of 128, multiples of 32 from 128 up): the last c_out / c_in tile is cut short.  The producers
 // load nothing for the channels beyond the tensor (masked buffer loads return zeros) and the consumers skip their slab rows and
 // columns; every channel that exists goes through the same loads, splits and MFMAs as in a full tile.
-template <int ABL = 0, int CO = 256, bool TAIL = false>
+// NL = 2 (psld_conv3x3_wgrad_wino_x3_f32, record math PSLD_MATH_BF16X3): the producers store split2 of the same transformed
+// values - limbs 0 and 1 of the three-limb split, bit for bit - into images of two limb planes and the consumers issue the three
+// products hi*mid, mid*hi, hi*hi (smallest first): 96 MFMAs and 2/3 of the fragment reads per K tile and wave, 2/3 of the
+// producers' conversions and LDS stores; loads, transforms, slabs and the reduction are those of NL = 3.
+template <int ABL = 0, int CO = 256, bool TAIL = false, int NL = 3>
 __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
-    using G = WWGeom<CO>;
+    static_assert(NL == 3 || (NL == 2 && ABL == 0), "two or three limbs; the timing ablations exist for three");
+    using G = WWGeom<CO, NL>;
     constexpr int WW_CO = CO, WW_RSA = G::RSA, WW_ALIMB = G::ALIMB, WW_IMG = G::IMG, NY = G::NY, CB = G::CB;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -213,9 +236,9 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
         // load has a whole K tile of work (~3,000 cycles) to land, whatever the L2 does under load.  (The first form kept three
         // groups of four items and gave a group one group's work to land: 486 us on 256->256 @32 B=128 where this runs 404.)
         auto stage = [&](auto nr_tag, auto nc_tag) {
-            constexpr int NR = decltype(nr_tag)::value, NC = decltype(nc_tag)::value, NL = NR * NC;
+            constexpr int NR = decltype(nr_tag)::value, NC = decltype(nc_tag)::value, NLD = NR * NC;
             f32x4 sx[4][4];         // [item][r1c1, r1c2, r2c1, r2c2]
-            f32x4 sy[NY][NL];
+            f32x4 sy[NY][NLD];
             auto load_tile = [&](int kt) {
                 const int kc = kt & a.kpr_mask;                      // column block of the K tile in its tile row (0 unless W = 128)
                 const int R0 = (kt >> a.lg_kpr) * a.rows_per_kt;     // global tile row (image * tile rows + ty) of the K tile
@@ -253,7 +276,7 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     v[e] = (sx[i][0][e] + xsc * sx[i][1][e]) + xsr * (sx[i][2][e] + xsc * sx[i][3][e]);
-                ww_store<ABL>(img + 3 * WW_ALIMB + lds_x + i * 8 * WW_RSB, WW_BLIMB, v);
+                ww_store<ABL, NL>(img + NL * WW_ALIMB + lds_x + i * 8 * WW_RSB, WW_BLIMB, v);
             };
             auto put_y = [&](unsigned char* img, int i) {
                 f32x4 v;
@@ -268,7 +291,7 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
                     }
                     v[e] = t;
                 }
-                ww_store<ABL>(img + lds_y + i * KSTEP * WW_RSA, WW_ALIMB, v);
+                ww_store<ABL, NL>(img + lds_y + i * KSTEP * WW_RSA, WW_ALIMB, v);
             };
             {
                 auto ld = load_tile(kt_beg);
@@ -329,7 +352,7 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
     for (int j = 0; j < 2; ++j) {
         const int k = 4 * g + 16 * j + q;              // tile (K slot) of this lane's row in read j
         a_base[j] = k * WW_RSA + (wr * (CO / 2) + 4 * p4) * 2;
-        b_base[j] = 3 * WW_ALIMB + k * WW_RSB + (wc * 64 + 4 * p4) * 2;
+        b_base[j] = NL * WW_ALIMB + k * WW_RSB + (wc * 64 + 4 * p4) * 2;
     }
     auto frag = [&](const unsigned char* img, const int (&base)[2], int off) -> u32x4 {
         const u32x2 lo = lds_tr16(img + base[0] + off), hi = lds_tr16(img + base[1] + off);
@@ -361,21 +384,24 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
                 continue;
             }
         }
-        u32x4 fb[4][3];
+        u32x4 fb[4][NL];
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
-            for (int l = 0; l < 3; ++l) fb[nb][l] = frag(img, b_base, l * WW_BLIMB + nb * 32);
-        u32x4 fa[2][3];
+            for (int l = 0; l < NL; ++l) fb[nb][l] = frag(img, b_base, l * WW_BLIMB + nb * 32);
+        u32x4 fa[2][NL];
 #pragma unroll
-        for (int l = 0; l < 3; ++l) fa[0][l] = frag(img, a_base, l * WW_ALIMB);
+        for (int l = 0; l < NL; ++l) fa[0][l] = frag(img, a_base, l * WW_ALIMB);
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) {
             if (cb + 1 < CB) {
 #pragma unroll
-                for (int l = 0; l < 3; ++l) fa[(cb + 1) & 1][l] = frag(img, a_base, l * WW_ALIMB + (cb + 1) * 32);
+                for (int l = 0; l < NL; ++l) fa[(cb + 1) & 1][l] = frag(img, a_base, l * WW_ALIMB + (cb + 1) * 32);
             }
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+            // limb products, smallest first; two limbs: hi*mid, mid*hi, hi*hi
+            constexpr int NP = NL == 3 ? 6 : 3;
+            constexpr int PA[6] = {NL == 3 ? 2 : 0, NL == 3 ? 0 : 1, NL == 3 ? 1 : 0, 1, 0, 0};     // {2 0 1 1 0 0} / {0 1 0}
+            constexpr int PB[6] = {NL == 3 ? 0 : 1, NL == 3 ? 2 : 0, NL == 3 ? 1 : 0, 0, 1, 0};     // {0 2 1 0 1 0} / {1 0 0}
             if constexpr ((ABL & 4) != 0) {
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb)
@@ -385,7 +411,7 @@ __global__ void __launch_bounds__(512) wwgrad_ws_kernel(const WWgradArgs a) {
                         for (int e = 0; e < 4; ++e) acc[cb][nb][e] += __uint_as_float(fa[cb & 1][l][e] ^ fb[nb][l][e]);
             } else {
 #pragma unroll
-                for (int u = 0; u < 6; ++u)
+                for (int u = 0; u < NP; ++u)
 #pragma unroll
                     for (int nb = 0; nb < 4; ++nb)
                         acc[cb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -494,17 +520,47 @@ extern "C" long long psld_conv3x3_wgrad_wino_ws_bytes(int cout, int cin_total, i
     return (long long)nsplit * 16 * cout * cin_total * 4;
 }
 
-extern "C" int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, const float* x, int cin, const float* x2, int cin2,
-                                           int batch, int h, int w, float* slabs, int nsplit, float* dw_oihw, int accumulate,
-                                           float alpha, hipStream_t stream) {
-    PSLD_CHECK_ARG(dy && x && slabs && dw_oihw && nsplit >= 1 && (cin2 == 0 || x2), "psld_conv3x3_wgrad_wino_f32: bad args");
+// the four product instances of one limb count: LDS opt-in once per device, then the one the shape takes
+template <int NL>
+static int ww_launch(const WWgradArgs& a, int co_tile, bool tail, dim3 grid, hipStream_t stream, const char* name) {
+    constexpr size_t LDS256 = WWGeom<256, NL>::LDS, LDS128 = WWGeom<128, NL>::LDS;
+    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
+    if (!configured) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 256, false, NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS256);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 128, false, NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS128);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 128, true, NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS128);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 256, true, NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS256);
+        if (e != hipSuccess) {
+            psld_set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e));
+            return PSLD_ERR_LAUNCH;
+        }
+        configured = true;
+    }
+    if (tail && co_tile == 256)         // c_in tail only (cout % 256 == 0)
+        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 256, true, NL>), grid, dim3(512), LDS256, stream, a);
+    else if (tail)
+        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 128, true, NL>), grid, dim3(512), LDS128, stream, a);
+    else if (co_tile == 256)
+        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 256, false, NL>), grid, dim3(512), LDS256, stream, a);
+    else
+        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 128, false, NL>), grid, dim3(512), LDS128, stream, a);
+    PSLD_CHECK_LAUNCH(name);
+    return PSLD_OK;
+}
+
+static int ww_run(int nl, const char* name, const float* dy, int lddy, int cout, const float* x, int cin, const float* x2, int cin2,
+                  int batch, int h, int w, float* slabs, int nsplit, float* dw_oihw, int accumulate, float alpha, hipStream_t stream) {
+    PSLD_CHECK_ARG(dy && x && slabs && dw_oihw && nsplit >= 1 && (cin2 == 0 || x2), "%s: bad args", name);
     PSLD_CHECK_ARG(psld_conv3x3_wgrad_wino_supported(cout, cin, cin2, batch, h, w),
-                   "psld_conv3x3_wgrad_wino_f32: unsupported shape cout=%d cin=%d+%d B=%d %dx%d", cout, cin, cin2, batch, h, w);
+                   "%s: unsupported shape cout=%d cin=%d+%d B=%d %dx%d", name, cout, cin, cin2, batch, h, w);
     PSLD_CHECK_ARG(aligned16(dy) && aligned16(x) && (cin2 == 0 || aligned16(x2)) && lddy % 4 == 0 && lddy >= cout,
-                   "psld_conv3x3_wgrad_wino_f32: unaligned operand");
+                   "%s: unaligned operand", name);
     const long long ktiles = (long long)batch * h * w / 4 / 32;
     const long long per_split = (ktiles + nsplit - 1) / nsplit;
-    PSLD_CHECK_ARG((ktiles + per_split - 1) / per_split == nsplit, "psld_conv3x3_wgrad_wino_f32: %d splits of %lld K tiles leave empty slabs", nsplit, ktiles);
+    PSLD_CHECK_ARG((ktiles + per_split - 1) / per_split == nsplit, "%s: %d splits of %lld K tiles leave empty slabs", name, nsplit, ktiles);
     WWgradArgs a{};
     a.dy = dy; a.lddy = lddy; a.x = x; a.cin = cin; a.x2 = x2; a.cin2 = cin2;
     a.H = h; a.W = w;
@@ -532,7 +588,7 @@ extern "C" int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, 
         launched = true;                                                                                                            \
         break;
     bool launched = false;
-    switch (co_tile == 256 && !tail ? abl : 0) {
+    switch (co_tile == 256 && !tail && nl == 3 ? abl : 0) {
         WW_ABL_CASE(1) WW_ABL_CASE(2) WW_ABL_CASE(3) WW_ABL_CASE(4) WW_ABL_CASE(8) WW_ABL_CASE(12) WW_ABL_CASE(16) WW_ABL_CASE(32) WW_ABL_CASE(64)
         default: break;
     }
@@ -540,33 +596,26 @@ extern "C" int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, 
     if (!launched)
 #endif
     {
-    static PsldPerDeviceFlag configured_; bool& configured = configured_.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WWGeom<256>::LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WWGeom<128>::LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WWGeom<128>::LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wwgrad_ws_kernel<0, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WWGeom<256>::LDS);
-        if (e != hipSuccess) {
-            psld_set_error("psld_conv3x3_wgrad_wino_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return PSLD_ERR_LAUNCH;
-        }
-        configured = true;
-    }
-    if (tail && co_tile == 256)         // c_in tail only (cout % 256 == 0)
-        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 256, true>), grid, dim3(512), WWGeom<256>::LDS, stream, a);
-    else if (tail)
-        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 128, true>), grid, dim3(512), WWGeom<128>::LDS, stream, a);
-    else if (co_tile == 256)
-        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 256>), grid, dim3(512), WWGeom<256>::LDS, stream, a);
-    else
-        hipLaunchKernelGGL((wwgrad_ws_kernel<0, 128>), grid, dim3(512), WWGeom<128>::LDS, stream, a);
-    PSLD_CHECK_LAUNCH("wwgrad_ws_kernel");
+        const int rc = nl == 2 ? ww_launch<2>(a, co_tile, tail, grid, stream, name) : ww_launch<3>(a, co_tile, tail, grid, stream, name);
+        if (rc != PSLD_OK) return rc;
     }
     const long long n = (long long)cout * a.cin_total;
     hipLaunchKernelGGL(wwgrad_reduce_kernel, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, stream, slabs, nsplit, n, dw_oihw, accumulate, alpha);
     PSLD_CHECK_LAUNCH("wwgrad_reduce_kernel");
     return PSLD_OK;
+}
+
+extern "C" int psld_conv3x3_wgrad_wino_f32(const float* dy, int lddy, int cout, const float* x, int cin, const float* x2, int cin2,
+                                           int batch, int h, int w, float* slabs, int nsplit, float* dw_oihw, int accumulate,
+                                           float alpha, hipStream_t stream) {
+    return ww_run(3, "psld_conv3x3_wgrad_wino_f32", dy, lddy, cout, x, cin, x2, cin2, batch, h, w, slabs, nsplit, dw_oihw, accumulate,
+                  alpha, stream);
+}
+
+// two limbs per operand, three products (record math PSLD_MATH_BF16X3): same shapes, splits, workspace and reduction
+extern "C" int psld_conv3x3_wgrad_wino_x3_f32(const float* dy, int lddy, int cout, const float* x, int cin, const float* x2, int cin2,
+                                              int batch, int h, int w, float* slabs, int nsplit, float* dw_oihw, int accumulate,
+                                              float alpha, hipStream_t stream) {
+    return ww_run(2, "psld_conv3x3_wgrad_wino_x3_f32", dy, lddy, cout, x, cin, x2, cin2, batch, h, w, slabs, nsplit, dw_oihw, accumulate,
+                  alpha, stream);
 }

@@ -144,6 +144,19 @@ def math_mode() -> str:
     return MATH_MODES[lib().psld_get_math_mode()]
 
 
+def set_record_math(mode: str):
+    """Arithmetic of the passes that record a backward pass: 'bf16x6' (default: such a pass is the three-limb one, launch for
+    launch, whatever the math mode) or 'bf16x3' (under a limb math mode it runs the two-limb ``*_x3`` launches where one
+    exists: Winograd 3x3 forward / data gradient / weight gradient, pointwise forward / data gradient); process-wide."""
+    if mode not in ("bf16x6", "bf16x3"):
+        raise ValueError(f"record math must be 'bf16x6' or 'bf16x3', got {mode!r}")
+    check(lib().psld_set_record_math(MATH_MODES.index(mode)), "psld_set_record_math")
+
+
+def record_math() -> str:
+    return MATH_MODES[lib().psld_get_record_math()]
+
+
 @functools.lru_cache(maxsize=None)
 def conv3x3_split_supported(c1: int, c2: int, b: int, h: int, w: int, cout: int) -> bool:
     return bool(lib().psld_conv3x3_split_supported(c1, c2, b, h, w, cout))
@@ -217,7 +230,7 @@ def pack_wino_batch(table: Tensor, entries: int, total_items: int):
     check(lib().psld_pack_wino_batch(table.data_ptr(), entries, total_items, _stream()), "psld_pack_wino_batch")
 
 
-# ---- two limbs (math mode 'bf16x3'): forward orientation only, same shapes and tables as the three-limb forms ----------
+# ---- two limbs (math mode 'bf16x3'): same shapes and tables as the three-limb forms --------------------------------------
 def conv3x3_wino_frag_bytes_x3(cout: int, cin: int) -> int:
     return int(lib().psld_conv3x3_wino_frag_bytes_x3(cout, cin))
 
@@ -231,8 +244,18 @@ def conv3x3_wino_frag_x3(w_oihw: Tensor, out: Optional[Tensor] = None) -> Tensor
     return out
 
 
+def conv3x3_wino_dgrad_frag_x3(w_oihw: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """conv3x3_wino_frag(w, True) - the data gradient's fragments - with the hi and mid limb planes only."""
+    co, ci = w_oihw.shape[0], w_oihw.shape[1]
+    if out is None:
+        out = torch.empty(conv3x3_wino_frag_bytes_x3(ci, co), dtype=torch.uint8, device=w_oihw.device)
+    check(lib().psld_pack_conv3x3_wino_dgrad_x3(w_oihw.data_ptr(), out.data_ptr(), co, ci, _stream()),
+          "psld_pack_conv3x3_wino_dgrad_x3")
+    return out
+
+
 def pack_wino_batch_x3(table: Tensor, entries: int, total_items: int):
-    """pack_wino_batch into two-limb fragment buffers (rows: conv3x3_wino_frag_entry(w, False, out) + [first work item])."""
+    """pack_wino_batch into two-limb fragment buffers (rows: conv3x3_wino_frag_entry(w, dgrad, out) + [first work item])."""
     check(lib().psld_pack_wino_batch_x3(table.data_ptr(), entries, total_items, _stream()), "psld_pack_wino_batch_x3")
 
 
@@ -633,10 +656,8 @@ def conv3x3_wgrad_wino_plan(cout: int, cin_total: int, b: int, h: int, w: int):
     return ns, int(lib().psld_conv3x3_wgrad_wino_ws_bytes(cout, cin_total, ns))
 
 
-def conv3x3_wgrad_wino(dy: Tensor, cout: int, x: Tensor, dw: Tensor, x2: Optional[Tensor] = None, accumulate: bool = False,
-                       slabs: Optional[Tensor] = None, nsplit: Optional[int] = None, alpha: float = 1.0):
-    """dw[cout][cin (+ cin2)][3][3] (OIHW, contiguous) = (or +=) the weight gradient of the 3x3 stride-1 convolution, formed in
-    the Winograd F(2x2, 3x3) domain (psld_conv3x3_wgrad_wino_f32: 16 limb products per 2x2 tile instead of 36)."""
+def _wgrad_wino(name: str, dy: Tensor, cout: int, x: Tensor, dw: Tensor, x2: Optional[Tensor], accumulate: bool,
+                slabs: Optional[Tensor], nsplit: Optional[int], alpha: float):
     b, h, w, cin = x.shape
     cin2 = x2.shape[-1] if x2 is not None else 0
     ns, wsb = conv3x3_wgrad_wino_plan(cout, cin + cin2, b, h, w)
@@ -645,9 +666,22 @@ def conv3x3_wgrad_wino(dy: Tensor, cout: int, x: Tensor, dw: Tensor, x2: Optiona
     if slabs is None:
         slabs = workspace(wsb, x.device)
     assert slabs.numel() * slabs.element_size() >= wsb and dw.is_contiguous() and dw.numel() == cout * (cin + cin2) * 9
-    check(lib().psld_conv3x3_wgrad_wino_f32(dy.data_ptr(), cout, cout, x.data_ptr(), cin, _p(x2), cin2, b, h, w,
-                                            slabs.data_ptr(), ns, dw.data_ptr(), 1 if accumulate else 0, float(alpha), _stream()),
-          "psld_conv3x3_wgrad_wino_f32")
+    check(getattr(lib(), name)(dy.data_ptr(), cout, cout, x.data_ptr(), cin, _p(x2), cin2, b, h, w, slabs.data_ptr(), ns,
+                               dw.data_ptr(), 1 if accumulate else 0, float(alpha), _stream()), name)
+
+
+def conv3x3_wgrad_wino(dy: Tensor, cout: int, x: Tensor, dw: Tensor, x2: Optional[Tensor] = None, accumulate: bool = False,
+                       slabs: Optional[Tensor] = None, nsplit: Optional[int] = None, alpha: float = 1.0):
+    """dw[cout][cin (+ cin2)][3][3] (OIHW, contiguous) = (or +=) the weight gradient of the 3x3 stride-1 convolution, formed in
+    the Winograd F(2x2, 3x3) domain (psld_conv3x3_wgrad_wino_f32: 16 limb products per 2x2 tile instead of 36)."""
+    _wgrad_wino("psld_conv3x3_wgrad_wino_f32", dy, cout, x, dw, x2, accumulate, slabs, nsplit, alpha)
+
+
+def conv3x3_wgrad_wino_x3(dy: Tensor, cout: int, x: Tensor, dw: Tensor, x2: Optional[Tensor] = None, accumulate: bool = False,
+                          slabs: Optional[Tensor] = None, nsplit: Optional[int] = None, alpha: float = 1.0):
+    """conv3x3_wgrad_wino on two limbs per operand and three products (psld_conv3x3_wgrad_wino_x3_f32; record math 'bf16x3'):
+    same shapes, splits and workspace."""
+    _wgrad_wino("psld_conv3x3_wgrad_wino_x3_f32", dy, cout, x, dw, x2, accumulate, slabs, nsplit, alpha)
 
 
 def conv2d_wgrad_nhwc(dy: Tensor, cout: int, x: Tensor, kh: int, kw: int, stride: int, pad: int, oh: int, ow: int,

@@ -382,9 +382,9 @@ class NCSNpp(nn.Module):
         """Winograd-transformed bf16 limb fragments of a 3x3 weight (ops.conv3x3_wino_frag)."""
         return self._wcache.get(conv.weight, "dwfrag" if dgrad else "wfrag", _frag_entry, dgrad, True)
 
-    def _wfrag_x3(self, conv: _Affine) -> Tensor:
-        """Two-limb Winograd fragments of a 3x3 weight, forward orientation (ops.conv3x3_wino_frag_x3)."""
-        return self._wcache.get(conv.weight, "wfrag_x3", _wfrag_x3_entry)
+    def _wfrag_x3(self, conv: _Affine, dgrad: bool = False) -> Tensor:
+        """Two-limb Winograd fragments of a 3x3 weight (ops.conv3x3_wino_frag_x3 / conv3x3_wino_dgrad_frag_x3)."""
+        return self._wcache.get(conv.weight, "wfrag_d_x3" if dgrad else "wfrag_x3", _wfrag_x3_entry, dgrad)
 
     def _pfrag(self, owner: nn.Parameter, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor] = None,
                chunk0: int = 0, chunks_total: int = 0, n0: int = 0, n_total: int = 0) -> Tensor:
@@ -420,15 +420,20 @@ class NCSNpp(nn.Module):
             self._pfrag(nin.W, "qkv_d", c, c, c, 1, into=pd, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
         return self._wcache.fresh(e)
 
-    def _qkv_frags_x3(self, mod):
-        """The forward q | k | v fragment set of _qkv_frags in two-limb form (math mode 'bf16x3')."""
+    def _qkv_frags_x3(self, mod, dgrad: bool = False):
+        """The forward (``dgrad``: data-gradient) q | k | v fragment set of _qkv_frags in two-limb form (math mode / record
+        math 'bf16x3'; whole-tile sets only: c % 128 == 0)."""
         n0 = mod.NIN_0
         c = n0.W.shape[0]
         fb = ops.gemm_frag_bytes_x3(c, c)
-        pf = self._wcache.entry(n0.W, "qkv_x3", lambda w: Entry(
+        # the holder of the shared buffer (no family: the "qkv_d_x3" / "qkv_f_x3" entries of the three projections fill it)
+        pf = self._wcache.entry(n0.W, "qkv_set_d_x3" if dgrad else "qkv_set_x3", lambda w: Entry(
             w, out=torch.empty(3 * fb, dtype=torch.uint8, device=w.device), build=lambda prev: prev)).out
         for i, nin in enumerate((n0, mod.NIN_1, mod.NIN_2)):
-            self._pfrag(nin.W, "qkv_f_x3", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
+            if dgrad:       # concatenated along K, as in _qkv_frags
+                self._pfrag(nin.W, "qkv_d_x3", c, c, c, 1, into=pf, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
+            else:
+                self._pfrag(nin.W, "qkv_f_x3", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
         return pf
 
     def _temb_plan(self):

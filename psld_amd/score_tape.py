@@ -103,8 +103,11 @@ class _ExecBase:
         mode = ops.math_mode()
         self.split = mode in ("bf16x6", "bf16x3")   # 3x3 convs on the bf16 limb kernels (csrc/conv_split.hip)
         # 'bf16x3' (reduced-precision inference): a forward that records no backward pass runs the two-limb form of every
-        # Winograd-forward / pointwise-forward launch that has one; a recording pass is the 'bf16x6' one, launch for launch
-        self.x3 = mode == "bf16x3" and not record
+        # Winograd-forward / pointwise-forward launch that has one; a recording pass is the 'bf16x6' one, launch for launch -
+        # unless record math 'bf16x3' (ops.set_record_math, opt-in) asks for two limbs there as well: then, under either limb
+        # math mode, its forward launches, its Winograd / pointwise data gradients and its Winograd-domain weight gradients are
+        # the two-limb ones (direct limb 3x3 kernels, pointwise / NIN weight gradients and attention products have no such form)
+        self.x3 = (mode == "bf16x3" and not record) or (record and self.split and ops.record_math() == "bf16x3")
         self.limb_planes = os.environ.get("PSLD_LIMB_PLANES", "1") != "0"    # A/B switch for tools/bench_sample.py
         # forward attention in one kernel (attention.hip) wherever it takes the shape (B=128: 8x8 maps 17 vs 54 us of the
         # three-kernel path, 16x16 maps 62-65 vs 72 us, tools/bench_attn.py); PSLD_FUSED_ATTN=0: the three kernels
@@ -325,7 +328,7 @@ class _ExecBase:
             # Winograd domain (wgrad_wino.hip): 16 limb products per 2x2 tile instead of 36; its own slabs and reduction
             # (G^T . G over 16 positions), written straight into the flat gradient
             # (the stream's workspace: the reduction follows at once, nothing is parked in the slab arena)
-            ops.conv3x3_wgrad_wino(dy, cout, x, self.g(conv.weight), x2=x2, alpha=alpha)
+            (ops.conv3x3_wgrad_wino_x3 if self.x3 else ops.conv3x3_wgrad_wino)(dy, cout, x, self.g(conv.weight), x2=x2, alpha=alpha)
             return
         if route == R.LIMB:
             nsplit = R.wgrad_limb_nsplit(cout, cin, b, oh, ow, isinstance(x, ops.LimbPlanes))
@@ -442,16 +445,20 @@ class _ExecBase:
     def pw_dgrad(self, route: str, dy: Tensor, m: int, w: PointwiseWeight, dx: Tensor, epi=None, cols=None):
         """dx[m][w.k] = epi(dy[m][w.n] W).  ``cols`` = (lo, hi), limb routes: input channels lo .. hi alone, into a dx that wide
         (one source of an unmaterialised concatenation: a data gradient's fragments are ordered by output-channel tile, so a
-        source's share is a contiguous slice of them)."""
+        source's share is a contiguous slice of them).  LIMB runs the two-limb form where a recording pass under record math
+        'bf16x3' wants it (the policy of pw_fwd, on the launch's own width)."""
         n = w.k
         if route == R.TILE:
             wt, tb, ld = w.tile(True)
             return ops.gemm_raw(0, tb, m, n, w.n, dy, w.n, 0, wt, ld, 0, dx, n, 0, epi=epi)
-        frag = w.frag(True, tail=route == R.LIMB_TAIL)
+        x3 = route == R.LIMB and self.x3 and ops.gemm_split_x3_wanted(w.n, 0, m, n if cols is None else cols[1] - cols[0])
+        frag = w.frag(True, x3=x3, tail=route == R.LIMB_TAIL)
         if cols is not None:
             frag, n = frag[frag.numel() * cols[0] // n:frag.numel() * cols[1] // n], cols[1] - cols[0]
         if route == R.LIMB_TAIL:
             ops.gemm_split_tail(dy, m, frag, n, dx, epi)
+        elif x3:
+            ops.gemm_split_x3(dy, None, m, frag, n, dx, epi)
         else:
             ops.gemm_split(dy, None, m, frag, n, dx, epi)
 
@@ -539,7 +546,10 @@ class _ExecBase:
         if route is None and (k, stride, pad) == (3, 1, 1):
             route = R.conv3_route(self.split, dy.shape[-1], 0, dy.shape[0], ih, iw, cin, wino=self.wino_wanted)
         if route == R.WINO:
-            ops.conv3x3_wino(dy, None, self.net._wfrag(conv, True), cin, out, epi, allow_split=True)     # Winograd F(2x2, 3x3)
+            if self.x3:
+                ops.conv3x3_wino_x3(dy, None, self.net._wfrag_x3(conv, True), cin, out, epi, allow_split=True)
+            else:
+                ops.conv3x3_wino(dy, None, self.net._wfrag(conv, True), cin, out, epi, allow_split=True)     # Winograd F(2x2, 3x3)
             return
         if route == R.LIMB:
             ops.conv3x3_split(dy, None, self.net._frag(conv, True), cin, out, epi)

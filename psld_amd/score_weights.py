@@ -30,10 +30,12 @@ def _frag_entry(w: Tensor, dgrad: bool, wino: bool) -> Entry:
                  rows=lambda out: [(row(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
 
 
-def _wfrag_x3_entry(w: Tensor) -> Entry:
-    """Two-limb Winograd fragments (forward orientation): the 'wino' entries' sibling for math mode 'bf16x3'."""
-    return Entry(w, build=lambda prev: ops.conv3x3_wino_frag_x3(w.detach(), prev), family="wino_x3",
-                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, False, out), w.shape[0] * w.shape[1] // 8)], graph=True)
+def _wfrag_x3_entry(w: Tensor, dgrad: bool = False) -> Entry:
+    """Two-limb Winograd fragments: the 'wino' entries' siblings for math mode 'bf16x3' (forward orientation) and record math
+    'bf16x3' (both orientations)."""
+    pack = ops.conv3x3_wino_dgrad_frag_x3 if dgrad else ops.conv3x3_wino_frag_x3
+    return Entry(w, build=lambda prev: pack(w.detach(), prev), family="wino_x3",
+                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
 
 
 def pfrag_tail(n: int, k: int, n_total: int = 0, chunks_total: int = 0) -> bool:
@@ -144,11 +146,11 @@ class PointwiseWeight(NamedTuple):
         return self.w, int(oi != dgrad), self.k if oi else self.n
 
     def frag(self, dgrad: bool = False, x3: bool = False, tail: bool = False) -> Tensor:
-        """Three-limb (``x3``: two-limb, forward only) fragments of B[n][k], or of B[k][n] for the data gradient."""
+        """Three-limb (``x3``: two-limb, whole-tile sets only) fragments of B[n][k], or of B[k][n] for the data gradient."""
         net, w, kind = self.net, self.w, self.kind
         n, k = (self.k, self.n) if dgrad else (self.n, self.k)
         if kind == "qkv":
-            return net._qkv_frags_x3(w) if x3 else self.qkv[int(dgrad)]
+            return net._qkv_frags_x3(w, dgrad) if x3 else self.qkv[int(dgrad)]
         if kind == "ohwi":
             pack = ops.gemm_frag_x3 if x3 else ops.gemm_frag_tail if tail else ops.gemm_frag
             sn, sk = (1, n) if dgrad else (k, 1)

@@ -138,7 +138,9 @@ class SDEWrapper(_Base):
         net, optim, sde = self.score_fn, self.optimizers(), self.sde
         if not hasattr(self, "_graph_steps"):
             self._graph_steps = {}
-        key = (tuple(batch.shape), batch.device.index, bool(net.training))
+        # a capture replays its own launches: which ones a recording pass issues depends on the math mode (limb kernels or the
+        # fp32 tile engine) and on the record math (three or two limbs)
+        key = (tuple(batch.shape), batch.device.index, bool(net.training), ops.math_mode(), ops.record_math())
         ent = self._graph_steps.get(key)
         if ent is None:
             ent = self._graph_steps[key] = {"seen": 0}
