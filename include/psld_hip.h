@@ -45,7 +45,8 @@ const char* psld_last_error(void);
  *                    network forward).  The library only stores this value: which launches use the two-limb entry
  *                    points is the caller's choice (psld_amd: forwards that record no backward pass).
  * Process-wide; the initial value comes from the environment variable PSLD_MATH ("f32" | "bf16x6" | "bf16x3" |
- * "bf16x3_train": mode PSLD_MATH_BF16X3 with record math PSLD_MATH_BF16X3, below). */
+ * "bf16x3_train": mode PSLD_MATH_BF16X3 with record math PSLD_MATH_BF16X3, below | "f16": mode PSLD_MATH_BF16X3 with eval math
+ * PSLD_EVAL_MATH_F16, below). */
 #define PSLD_MATH_F32 0
 #define PSLD_MATH_BF16X6 1
 #define PSLD_MATH_BF16X3 2
@@ -59,6 +60,18 @@ int psld_get_math_mode(void);
  * "bf16x3_train", else PSLD_MATH_BF16X6. */
 int psld_set_record_math(int mode);
 int psld_get_record_math(void);
+/* Eval math: arithmetic of the forwards that record NO backward pass (sampling).  PSLD_EVAL_MATH_LIMB (default): they follow the
+ * math mode.  PSLD_EVAL_MATH_F16 (opt-in, meaningful under a limb math mode): they take the one-product fp16 entry points
+ * (*_f16 below: Winograd 3x3 forward, eight-wave pointwise forward) where one exists and run as under PSLD_MATH_BF16X3 elsewhere.
+ * Operands are rounded ONCE to fp16 (round to nearest even, clamped to +-65504: a finite operand never becomes an infinity),
+ * products are exact in fp32, accumulation is fp32: 11 significant bits, the significand of TF32 - rel-L2 ~1e-3 on a whole
+ * network forward, i.e. what the reference's default GPU arithmetic gives, NOT fp32-equivalent.  Values below 2^-24 in magnitude
+ * round to zero (no per-tensor scaling).  The library only stores the value; any other value is refused.  Initial value:
+ * PSLD_EVAL_MATH_F16 when PSLD_MATH is "f16" (which also selects math mode PSLD_MATH_BF16X3), else PSLD_EVAL_MATH_LIMB. */
+#define PSLD_EVAL_MATH_LIMB 0
+#define PSLD_EVAL_MATH_F16 1
+int psld_set_eval_math(int kind);
+int psld_get_eval_math(void);
 
 /* ---- fused epilogue of every MFMA tile kernel ------------------------------------------
  * value = ((alpha * acc + bias[n] + rowbias[m / rows_per_img][n] + residual[m][n]) * out_scale)
@@ -223,6 +236,21 @@ int psld_conv3x3_wino_gn_x3_f32(const float* x1, int c1, const float* scale1, co
                                 int c2, const float* scale2, const float* shift2, int act, int batch, int h, int w,
                                 const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
                                 void* workspace, long long ws_bytes, hipStream_t stream);
+/* One-product fp16 (PSLD_EVAL_MATH_F16) forms of the Winograd forward: V = B^T d B and U = G g G^T are formed in fp32 as above and
+ * stored as ONE plane of fp16 values (fragments [...][16 pos][1][64 lanes]: cout*cin*16*2 bytes + the same prefetch pad, from
+ * psld_pack_conv3x3_wino_f16 - forward orientation only; psld_pack_wino_batch_f16 takes psld_pack_wino_batch's table), one
+ * v_mfma_f32_16x16x32_f16 per accumulator, fp32 accumulation / output transform / epilogue as above.  Shapes, workspace and
+ * K splits: those of the *_x3 entries. */
+long long psld_conv3x3_wino_frag_bytes_f16(int cout, int cin);
+int psld_pack_conv3x3_wino_f16(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream);
+int psld_pack_wino_batch_f16(const long long* table_dev, int entries, long long total_items, hipStream_t stream);
+int psld_conv3x3_wino_f16_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
+                              const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
+                              void* workspace, long long ws_bytes, hipStream_t stream);
+int psld_conv3x3_wino_gn_f16_f32(const float* x1, int c1, const float* scale1, const float* shift1, const float* x2,
+                                 int c2, const float* scale2, const float* shift2, int act, int batch, int h, int w,
+                                 const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
+                                 void* workspace, long long ws_bytes, hipStream_t stream);
 
 /* "Limb planes": an NHWC activation [rows][c] (c a multiple of 32) stored already decomposed, as bf16
  * [rows][c/32 chunks][3 limbs hi|mid|lo][32 channels] (6 bytes per element; hi + mid + lo == x bit for bit).  The
@@ -261,6 +289,16 @@ int psld_pack_gemm_frag_x3(const float* b, void* bfrag, int n, int k, long long 
 int psld_pack_frag_batch_x3(const long long* table_dev, int entries, long long total_items, hipStream_t stream);
 int psld_gemm_split_x3_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
                            float* y, int ldy, const psld_epilogue_t* epi, hipStream_t stream);
+/* One-product fp16 (PSLD_EVAL_MATH_F16) form of the forward GEMM: fragments of one fp16 plane (n*k*2 bytes; psld_pack_frag_batch_f16
+ * takes psld_pack_frag_batch's table, taps = 1), rows rounded once to fp16 (clamped to +-65504), one product per accumulator.
+ * The eight-wave kernel and the shapes of the *_x3 entries. */
+long long psld_gemm_frag_bytes_f16(int n, int k);
+int psld_gemm_split_f16_supported(int k1, int k2, int m, int n);
+int psld_pack_gemm_frag_f16(const float* b, void* bfrag, int n, int k, long long stride_n, long long stride_k,
+                            hipStream_t stream);
+int psld_pack_frag_batch_f16(const long long* table_dev, int entries, long long total_items, hipStream_t stream);
+int psld_gemm_split_f16_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
+                            float* y, int ldy, const psld_epilogue_t* epi, hipStream_t stream);
 
 /* Fused single-head spatial self-attention, forward: o[b][i][:] = sum_j softmax_j(scale * q[b][i] . k[b][j]) v[b][j][:] in
  * one kernel, the hw x hw score matrix never written (unless p != NULL: the probabilities [batch][hw][hw] fp32, what the

@@ -500,9 +500,11 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--clf-config", default="clf_c10", choices=["clf_c10", "clf_afhqv2_128", "clf_default", "tiny_clf"])
         p.add_argument("--labels", default="synthetic", help="train_clf: int [N] .npy or 'synthetic'")
         if name in ("sample", "cc_sample", "inpaint"):
-            p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32"],
+            p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32", "f16"],
                            help="arithmetic of the network evaluations (ops.set_math_mode; default: the process's mode, "
-                                "PSLD_MATH); bf16x3 = two-limb reduced-precision inference")
+                                "PSLD_MATH); bf16x3 = two-limb reduced-precision inference; f16 = bf16x3 with the Winograd and "
+                                "wide pointwise forwards on ONE fp16 product (ops.set_eval_math): ~1e-3 rel-L2 from fp32, the "
+                                "precision of the reference's default TF32 convolutions, outside the 1e-4 parity contract")
         if name in ("train", "train_clf"):
             p.add_argument("--train-math", default=None, choices=["bf16x6", "bf16x3"],
                            help="arithmetic of the passes that record a backward pass (ops.set_record_math; default: the "
@@ -517,7 +519,8 @@ def main(argv=None):
         raise SystemExit("psld_amd needs an MI355X: there is no CPU fallback")
     if getattr(args, "math", None):         # before the network is built
         from psld_amd import ops
-        ops.set_math_mode(args.math)
+        ops.set_math_mode("bf16x3" if args.math == "f16" else args.math)
+        ops.set_eval_math("f16" if args.math == "f16" else "limb")
     if getattr(args, "train_math", None):
         from psld_amd import ops
         ops.set_record_math(args.train_math)

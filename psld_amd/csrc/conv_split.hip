@@ -43,14 +43,17 @@ constexpr int TAP_U4 = 4 * 3 * 64;   // uint4 per (wave column, tap, 32-channel 
 
 int g_math_mode = -1;
 int g_record_math = -1;     // arithmetic of passes that record a backward pass (psld_set_record_math)
-// PSLD_MATH is read once, by whichever getter runs first: "bf16x3_train" = math mode bf16x3 + record math bf16x3.  A value
-// set through the C ABI before that stays.
+int g_eval_math = -1;       // arithmetic of forwards that record none (psld_set_eval_math): 0 follows the math mode, 1 = f16
+// PSLD_MATH is read once, by whichever getter runs first: "bf16x3_train" = math mode bf16x3 + record math bf16x3, "f16" = math
+// mode bf16x3 + eval math f16.  A value set through the C ABI before that stays.
 inline void math_from_env() {
     const char* e = getenv("PSLD_MATH");
     const bool train = e && !strcmp(e, "bf16x3_train");
+    const bool f16 = e && !strcmp(e, "f16");
     if (g_math_mode < 0)
-        g_math_mode = (e && !strcmp(e, "f32")) ? PSLD_MATH_F32 : ((e && !strcmp(e, "bf16x3")) || train) ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
+        g_math_mode = (e && !strcmp(e, "f32")) ? PSLD_MATH_F32 : ((e && !strcmp(e, "bf16x3")) || train || f16) ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
     if (g_record_math < 0) g_record_math = train ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
+    if (g_eval_math < 0) g_eval_math = f16 ? PSLD_EVAL_MATH_F16 : PSLD_EVAL_MATH_LIMB;
 }
 inline int math_mode() {
     if (g_math_mode < 0) math_from_env();
@@ -75,6 +78,7 @@ __device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, cons
 // chunk0 / chunks_total: the tensor fills the 32-wide K chunks chunk0 .. chunk0 + k_in/32 of a fragment set whose K
 // dimension has chunks_total chunks (several parameters concatenated along K: the attention q | k | v data gradient).
 // NL = 2 (PSLD_MATH_BF16X3): the hi and mid limbs only ([...][nb][2 limbs][lane]), bit for bit planes 0 and 1 of NL = 3.
+// NL = 1 (eval math f16): one plane of fp16 values (limb.h: cvt_pk_f16), [...][nb][1][lane].
 template <int NL = 3>
 __device__ __forceinline__ void pack_frag_item(const float* __restrict__ w, u32x4* __restrict__ out, long long item,
                                                int k_in, int taps, long long sn, long long sk, long long st, int flip,
@@ -98,11 +102,12 @@ __device__ __forceinline__ void pack_frag_item(const float* __restrict__ w, u32x
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if constexpr (NL == 3) split3(p[(2 * j) * sk], p[(2 * j + 1) * sk], hi[j], mid[j], lo[j]);
-            else split2(p[(2 * j) * sk], p[(2 * j + 1) * sk], hi[j], mid[j]);
+            else if constexpr (NL == 2) split2(p[(2 * j) * sk], p[(2 * j + 1) * sk], hi[j], mid[j]);
+            else hi[j] = cvt_pk_f16(p[(2 * j) * sk], p[(2 * j + 1) * sk]);
         }
         u32x4* o = out + (((base + tap) * 4 + nb) * NL) * 64 + lane;
         o[0] = u32x4{hi[0], hi[1], hi[2], hi[3]};
-        o[64] = u32x4{mid[0], mid[1], mid[2], mid[3]};
+        if constexpr (NL >= 2) o[64] = u32x4{mid[0], mid[1], mid[2], mid[3]};
         if constexpr (NL == 3) o[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
     }
 }
@@ -1567,6 +1572,8 @@ constexpr int PW8_ROWS = 256;                       // LDS pixel rows per image:
 constexpr int PW8_LIMB = PW8_ROWS * ROWB;           // bytes per limb of one image
 // NL = 2 (PSLD_MATH_BF16X3): rows and weights keep their first two limbs (split2), three products per accumulator instead of
 // six (hi*hi + (hi*lo + lo*hi), smallest first), images of two limb planes, fragments of psld_pack_gemm_frag_x3.
+// NL = 1 (eval math f16): rows and weights rounded once to fp16 (cvt_pk_f16), one product per accumulator, images of one
+// plane, fragments of psld_pack_gemm_frag_f16.
 template <int ABL = 0, int NL = 3>      // timing-only ablations (PSLD_PW8_ABL): 1 no staging after the prologue, 2 weights loaded once, 4 no epilogue
 __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1619,14 +1626,17 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
             if constexpr (NL == 3) {
                 split3(hv[i][0], hv[i][1], h0, m0_, l0);
                 split3(hv[i][2], hv[i][3], h1, m1, l1);
-            } else {
+            } else if constexpr (NL == 2) {
                 split2(hv[i][0], hv[i][1], h0, m0_);
                 split2(hv[i][2], hv[i][3], h1, m1);
+            } else {
+                h0 = cvt_pk_f16(hv[i][0], hv[i][1]);
+                h1 = cvt_pk_f16(hv[i][2], hv[i][3]);
             }
             const int prow = (tid >> 3) + 64 * i;
             unsigned char* q = smem + img * IMG + prow * ROWB + (((c4 >> 1) ^ lds_swz(prow)) << 4) + (c4 & 1) * 8;
             *reinterpret_cast<u32x2*>(q) = u32x2{h0, h1};
-            *reinterpret_cast<u32x2*>(q + PW8_LIMB) = u32x2{m0_, m1};
+            if constexpr (NL >= 2) *reinterpret_cast<u32x2*>(q + PW8_LIMB) = u32x2{m0_, m1};
             if constexpr (NL == 3) *reinterpret_cast<u32x2*>(q + 2 * PW8_LIMB) = u32x2{l0, l1};
         }
     };
@@ -1659,6 +1669,15 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
     auto mfma_q = [&](auto J) {
         constexpr int j = decltype(J)::value;
         constexpr int pp = j >> 2, b0 = (j & 3) * 2;
+        if constexpr (NL == 1) {                    // one fp16 product per accumulator (v_mfma_f32_16x16x32_f16)
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < 2; ++nb)
+                    acc[b0 + mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                        __builtin_bit_cast(f16x8, bq[pp][nb][0]), __builtin_bit_cast(f16x8, fa[j & 1][mb][0]), acc[b0 + mb][nb], 0, 0, 0);
+            return;
+        }
         constexpr int NP = NL == 3 ? 6 : 3;         // two limbs: A_lo B_hi, A_hi B_lo, A_hi B_hi
         constexpr int PA[6] = {NL == 3 ? 2 : 1, 0, NL == 3 ? 1 : 0, 1, 0, 0}, PB[6] = {0, NL == 3 ? 2 : 1, NL == 3 ? 1 : 0, 0, 1, 0};
 #pragma unroll
@@ -2018,6 +2037,17 @@ extern "C" int psld_get_record_math(void) {
     return g_record_math;
 }
 
+extern "C" int psld_set_eval_math(int kind) {
+    PSLD_CHECK_ARG(kind == PSLD_EVAL_MATH_LIMB || kind == PSLD_EVAL_MATH_F16, "psld_set_eval_math: unknown kind %d", kind);
+    g_eval_math = kind;
+    return PSLD_OK;
+}
+
+extern "C" int psld_get_eval_math(void) {
+    if (g_eval_math < 0) math_from_env();
+    return g_eval_math;
+}
+
 extern "C" long long psld_conv3x3_frag_bytes(int cout, int cin) { return (long long)cout * cin * 9 * 6; }
 
 extern "C" int psld_conv3x3_split_supported(int c1, int c2, int batch, int h, int w, int cout) {
@@ -2273,6 +2303,32 @@ extern "C" int psld_gemm_split_x3_f32(const float* a1, int k1, const float* a2, 
                          nullptr, 0))
         return st;
     return launch_pw8<0, 2>(p.a, stream, name);
+}
+
+// ---- one fp16 plane (eval math f16): the eight-wave pointwise kernel on fragments of psld_pack_gemm_frag_f16 ----------------
+extern "C" long long psld_gemm_frag_bytes_f16(int n, int k) { return (long long)n * k * 2; }
+
+extern "C" int psld_gemm_split_f16_supported(int k1, int k2, int m, int n) { return psld_gemm_split_x3_supported(k1, k2, m, n); }
+
+extern "C" int psld_pack_gemm_frag_f16(const float* b, void* bfrag, int n, int k, long long stride_n, long long stride_k,
+                                       hipStream_t stream) {
+    PSLD_CHECK_ARG(b && bfrag, "psld_pack_gemm_frag_f16: null pointer");
+    PSLD_CHECK_ARG(n > 0 && k > 0 && n % 128 == 0 && k % 64 == 0, "psld_pack_gemm_frag_f16: needs n %%128 and k %%64 (got %d, %d)", n, k);
+    return launch_pack<1>(b, bfrag, n, k, 1, stride_n, stride_k, 0, 0, stream, "psld_pack_gemm_frag_f16");
+}
+
+extern "C" int psld_pack_frag_batch_f16(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
+    return launch_pack_batch(pack_frag_batch_kernel<1>, table_dev, entries, total_items, stream, "psld_pack_frag_batch_f16");
+}
+
+extern "C" int psld_gemm_split_f16_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
+                                       float* y, int ldy, const psld_epilogue_t* epi, hipStream_t stream) {
+    const char* name = "psld_gemm_split_f16_f32";
+    DConvPlan p;
+    if (int st = pw_plan(p, name, false, psld_gemm_split_f16_supported(k1, k2, m, n), a1, k1, a2, k2, m, bfrag, n, y, ldy, epi,
+                         nullptr, 0))
+        return st;
+    return launch_pw8<0, 1>(p.a, stream, name);
 }
 
 // ---- pointwise, channel widths in steps of 32 ("tail": the shapes psld_gemm_split_supported refuses for n % 128 or k % 64) ----

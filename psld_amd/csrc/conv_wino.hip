@@ -35,7 +35,7 @@ namespace {
 
 constexpr int WT = 32;                    // tiles per workgroup
 constexpr int VPLANE = WT * ROWB;         // bytes of one (position, limb) plane of the V image: 32 tiles x 64 B
-constexpr int VBYTES = 16 * 3 * VPLANE;   // 98,304 (three limbs; two: 65,536)
+constexpr int VBYTES = 16 * 3 * VPLANE;   // 98,304 (three limbs; two: 65,536; one fp16 plane: 32,768)
 constexpr int WINO_THREADS = 512;
 
 struct WinoArgs {
@@ -43,7 +43,7 @@ struct WinoArgs {
     const float* x2;
     int C1, C2;
     int B, H, W;
-    const u32x4* ufrag;     // [N/16 = 128-channel tile x 8 waves][chunk][16 pos][3 limbs][64 lanes] (a tail tile: fewer waves)
+    const u32x4* ufrag;     // [N/16 = 128-channel tile x 8 waves][chunk][16 pos][3 limbs][64 lanes] (a tail tile: fewer waves; NL = 2 / 1: two limbs / one fp16 plane)
     int N, M;               // cout (multiple of 128; TAIL: of 32, >= 128 - the last channel tile is cut short), B*H*W
     int chunks;             // (C1 + C2) / 32
     float* C;
@@ -109,6 +109,7 @@ __device__ __forceinline__ int raw_off(int hp, int q) {
 // One work item = lane slot (nt, wave, chunk, lane): n = nt*128 + wave*16 + (lane & 15), k = chunk*32 + (lane >> 4)*8 + j.
 // dgrad = 0: g = w[co = n][ci = k][:, :]; dgrad = 1: g = w[co = k][ci = n] rotated by 180 degrees (conv_split.hip).
 // NL = 2 (PSLD_MATH_BF16X3): the hi and mid limbs only, [...][16 pos][2 limbs][64 lanes] - bit for bit planes 0 and 1 of NL = 3.
+// NL = 1 (eval math f16): U rounded once to fp16 (limb.h: cvt_pk_f16), [...][16 pos][1][64 lanes].
 template <int NL = 3>
 __device__ __forceinline__ void wino_pack_item(const float* __restrict__ w, u32x4* __restrict__ out, long long it, int k_in,
                                                long long sn, long long sk, int flip) {
@@ -151,10 +152,11 @@ __device__ __forceinline__ void wino_pack_item(const float* __restrict__ w, u32x
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if constexpr (NL == 3) split3(U[2 * j][p], U[2 * j + 1][p], hi[j], mid[j], lo[j]);
-            else split2(U[2 * j][p], U[2 * j + 1][p], hi[j], mid[j]);
+            else if constexpr (NL == 2) split2(U[2 * j][p], U[2 * j + 1][p], hi[j], mid[j]);
+            else hi[j] = cvt_pk_f16(U[2 * j][p], U[2 * j + 1][p]);
         }
         o[(p * NL + 0) * 64] = u32x4{hi[0], hi[1], hi[2], hi[3]};
-        o[(p * NL + 1) * 64] = u32x4{mid[0], mid[1], mid[2], mid[3]};
+        if constexpr (NL >= 2) o[(p * NL + 1) * 64] = u32x4{mid[0], mid[1], mid[2], mid[3]};
         if constexpr (NL == 3) o[(p * 3 + 2) * 64] = u32x4{lo[0], lo[1], lo[2], lo[3]};
     }
 }
@@ -225,6 +227,10 @@ __global__ void wino_pack_batch_kernel(const long long* __restrict__ tab, int nt
 // NL = 2 (PSLD_MATH_BF16X3; the data gradient is this kernel on dgrad = 1 fragments): V and U keep their first two limbs (split2) and a product is the three limb
 // products hi*hi + (hi*lo + lo*hi): V image [pos][2][tile][32 ch] (64 KB), fragments [...][16 pos][2 limbs][64 lanes], per
 // chunk and wave 16 positions x (4 ds_read_b128 + 2 fragment loads + 6 MFMAs).  Everything else is the NL = 3 kernel.
+// NL = 1 (eval math f16, forward only): V and U are rounded ONCE to fp16 (cvt_pk_f16: round to nearest even, clamped to +-65504)
+// and a product is one v_mfma_f32_16x16x32_f16 - exact in fp32 (11 + 11 significant bits), so the operand rounding is the mode's
+// only error.  V image [pos][1][tile][32 ch] (32 KB), fragments [...][16 pos][1][64 lanes], per chunk and wave 16 positions x
+// (2 ds_read_b128 + 1 fragment load + 2 MFMAs).  fp32 transforms, accumulation, output transform and epilogue are the NL = 3 kernel's.
 template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3>
 __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -357,13 +363,16 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
             if constexpr (NL == 3) {
                 split3(v[0], v[1], h0, m0_, l0);
                 split3(v[2], v[3], h1, m1, l1);
-            } else {
+            } else if constexpr (NL == 2) {
                 split2(v[0], v[1], h0, m0_);
                 split2(v[2], v[3], h1, m1);
+            } else {
+                h0 = cvt_pk_f16(v[0], v[1]);
+                h1 = cvt_pk_f16(v[2], v[3]);
             }
             unsigned char* q = Vs + (vrow * 4 + j) * NL * VPLANE + t_dst;
             *reinterpret_cast<u32x2*>(q) = u32x2{h0, h1};
-            *reinterpret_cast<u32x2*>(q + VPLANE) = u32x2{m0_, m1};
+            if constexpr (NL >= 2) *reinterpret_cast<u32x2*>(q + VPLANE) = u32x2{m0_, m1};
             if constexpr (NL == 3) *reinterpret_cast<u32x2*>(q + 2 * VPLANE) = u32x2{l0, l1};
         }
     };
@@ -389,16 +398,21 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     for (int p = 0; p < 16; ++p)
 #pragma unroll
         for (int tb = 0; tb < 2; ++tb) acc[p][tb] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    u32x4 fa[NL][2];         // [limb hi | mid | lo][tile block]
+    u32x4 fa[NL == 1 ? 2 : NL][2];         // [limb hi | mid | lo][tile block]; NL = 1: [position parity][tile block]
     auto read_a = [&](int p, int l) {
 #pragma unroll
         for (int tb = 0; tb < 2; ++tb) fa[l][tb] = *reinterpret_cast<const u32x4*>(Vs + (p * NL + l) * VPLANE + aoff[tb]);
     };
     auto mm = [&](int p, int la, int lb) {
 #pragma unroll
-        for (int tb = 0; tb < 2; ++tb)
-            acc[p][tb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(      // weights first: D^T[channel][tile]
-                __builtin_bit_cast(bf16x8, bq[p & 3][lb]), __builtin_bit_cast(bf16x8, fa[la][tb]), acc[p][tb], 0, 0, 0);
+        for (int tb = 0; tb < 2; ++tb) {
+            if constexpr (NL == 1)
+                acc[p][tb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(   // one fp16 product: the bf16 operand order, element type changed
+                    __builtin_bit_cast(f16x8, bq[p & 3][lb]), __builtin_bit_cast(f16x8, fa[la][tb]), acc[p][tb], 0, 0, 0);
+            else
+                acc[p][tb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(      // weights first: D^T[channel][tile]
+                    __builtin_bit_cast(bf16x8, bq[p & 3][lb]), __builtin_bit_cast(bf16x8, fa[la][tb]), acc[p][tb], 0, 0, 0);
+        }
     };
     // the eight positions of half h of chunk c (see wino_conv_kernel for the group order and the in-place A prefetch)
     // LAST (the final half-phase of the workgroup): no fragment is requested past the last position
@@ -406,9 +420,26 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
         constexpr int h = decltype(HH)::value;
         constexpr bool last = decltype(LAST)::value;
         if constexpr ((ABL & 256) != 0) __builtin_amdgcn_s_setprio(2);       // experiment: the multiplying wave outranks its partner
+        if constexpr (NL == 1) {        // one plane: position p + 1's A operand is read (other parity) in front of p's two MFMAs
+            auto read_a1 = [&](int p) {
+#pragma unroll
+                for (int tb = 0; tb < 2; ++tb) fa[p & 1][tb] = *reinterpret_cast<const u32x4*>(Vs + p * VPLANE + aoff[tb]);
+            };
+            read_a1(8 * h);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int p = 8 * h + i;
+                if (!(last && p + LA >= 16)) load_b(c * 16 + p + LA, bq[(p + LA) & 3]);
+                if (i < 7) read_a1(p + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                mm(p, p & 1, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            return;
+        }
         // NL = 2: three products, small terms first - V_lo U_hi, V_hi U_lo, V_hi U_hi
         if constexpr (NL == 3) read_a(8 * h, 2);
-        read_a(8 * h, 1);
+        if constexpr (NL >= 2) read_a(8 * h, 1);
         read_a(8 * h, 0);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -422,12 +453,14 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
                 __builtin_amdgcn_sched_barrier(0);
                 mm(p, 1, 1);
             }
-            mm(p, 1, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (i < 7) read_a(p + 1, 1);
-            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (NL >= 2) {
+                mm(p, 1, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (i < 7) read_a(p + 1, 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             if constexpr (NL == 3) mm(p, 0, 2);
-            mm(p, 0, 1);
+            if constexpr (NL >= 2) mm(p, 0, 1);
             mm(p, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (i < 7) read_a(p + 1, 0);
@@ -703,6 +736,9 @@ extern "C" long long psld_conv3x3_wino_frag_bytes(int cout, int cin) { return (l
 // two limbs (PSLD_MATH_BF16X3): 2/3 of the payload, the same pad
 extern "C" long long psld_conv3x3_wino_frag_bytes_x3(int cout, int cin) { return (long long)cout * cin * 16 * 4 + 16384; }
 
+// one fp16 plane (eval math f16): 1/3 of the payload, the same pad
+extern "C" long long psld_conv3x3_wino_frag_bytes_f16(int cout, int cin) { return (long long)cout * cin * 16 * 2 + 16384; }
+
 // cout: a multiple of 128, or of 32 from 128 up (the last channel tile cut short: wino_conv8s_kernel<..., TAIL = true>)
 extern "C" int psld_conv3x3_wino_supported(int c1, int c2, int batch, int h, int w, int cout) {
     int nseg, rps, halo;
@@ -737,6 +773,18 @@ extern "C" int psld_pack_conv3x3_wino_x3(const float* w_oihw, void* ufrag, int c
     return PSLD_OK;
 }
 
+extern "C" int psld_pack_conv3x3_wino_f16(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream) {
+    PSLD_CHECK_ARG(w_oihw && ufrag && aligned16(ufrag), "psld_pack_conv3x3_wino_f16: null / unaligned pointer");
+    PSLD_CHECK_ARG(cout >= 128 && cin > 0 && cout % 32 == 0 && cin % 32 == 0,
+                   "psld_pack_conv3x3_wino_f16: needs out channels %%32 (>= 128) and in channels %%32 (got %d, %d)", cout, cin);
+    const long long items = (long long)(cout / 16) * (cin / 32) * 64;
+    const unsigned blocks = psld_grid_blocks(items, 64, 16384);
+    hipLaunchKernelGGL(wino_pack_kernel<1>, dim3(blocks), dim3(64), 0, stream, w_oihw, reinterpret_cast<u32x4*>(ufrag), cout, cin,
+                       (long long)cin * 9, 9LL, 0);
+    PSLD_CHECK_LAUNCH("psld_pack_conv3x3_wino_f16");
+    return PSLD_OK;
+}
+
 // the data-gradient orientation on two limbs (record math PSLD_MATH_BF16X3): psld_pack_conv3x3_wino(..., dgrad = 1)'s planes 0 and 1
 extern "C" int psld_pack_conv3x3_wino_dgrad_x3(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream) {
     PSLD_CHECK_ARG(w_oihw && ufrag && aligned16(ufrag), "psld_pack_conv3x3_wino_dgrad_x3: null / unaligned pointer");
@@ -754,6 +802,14 @@ extern "C" int psld_pack_wino_batch_x3(const long long* table_dev, int entries, 
     hipLaunchKernelGGL(wino_pack_batch_kernel<2>, dim3(psld_grid_blocks(total_items, 64, 32768)), dim3(64), 0, stream,
                        table_dev, entries, total_items);
     PSLD_CHECK_LAUNCH("psld_pack_wino_batch_x3");
+    return PSLD_OK;
+}
+
+extern "C" int psld_pack_wino_batch_f16(const long long* table_dev, int entries, long long total_items, hipStream_t stream) {
+    PSLD_CHECK_ARG(table_dev && entries > 0 && total_items > 0, "psld_pack_wino_batch_f16: bad args");
+    hipLaunchKernelGGL(wino_pack_batch_kernel<1>, dim3(psld_grid_blocks(total_items, 64, 32768)), dim3(64), 0, stream,
+                       table_dev, entries, total_items);
+    PSLD_CHECK_LAUNCH("psld_pack_wino_batch_f16");
     return PSLD_OK;
 }
 
@@ -859,7 +915,34 @@ extern "C" int psld_conv3x3_wino_gn_x3_f32(const float* x1, int c1, const float*
     return wino_conv(x1, c1, x2, c2, batch, h, w, ufrag, cout, y, ldy, epi, &gn, workspace, ws_bytes, stream, 2);
 }
 
+// ---- one fp16 plane (eval math f16): the same launches on fragments of psld_pack_conv3x3_wino_f16 ----------------------------
+extern "C" int psld_conv3x3_wino_f16_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
+                                         const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
+                                         void* workspace, long long ws_bytes, hipStream_t stream) {
+    return wino_conv(x1, c1, x2, c2, batch, h, w, ufrag, cout, y, ldy, epi, nullptr, workspace, ws_bytes, stream, 1);
+}
+
+extern "C" int psld_conv3x3_wino_gn_f16_f32(const float* x1, int c1, const float* scale1, const float* shift1, const float* x2,
+                                            int c2, const float* scale2, const float* shift2, int act, int batch, int h, int w,
+                                            const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
+                                            void* workspace, long long ws_bytes, hipStream_t stream) {
+    PSLD_CHECK_ARG(scale1 && shift1 && (c2 == 0 || (scale2 && shift2)), "psld_conv3x3_wino_gn_f16_f32: null scale / shift");
+    PSLD_CHECK_ARG(psld_conv3x3_wino_gn_supported(c1, c2, batch, h, w, cout),
+                   "psld_conv3x3_wino_gn_f16_f32: unsupported shape c1=%d c2=%d %dx%d cout=%d (needs h*w >= 128)", c1, c2, h, w, cout);
+    PSLD_CHECK_ARG(aligned16(scale1) && aligned16(shift1) && (c2 == 0 || (aligned16(scale2) && aligned16(shift2))),
+                   "psld_conv3x3_wino_gn_f16_f32: unaligned scale / shift");
+    const WinoGn gn{scale1, shift1, scale2, shift2, act};
+    return wino_conv(x1, c1, x2, c2, batch, h, w, ufrag, cout, y, ldy, epi, &gn, workspace, ws_bytes, stream, 1);
+}
+
 namespace {
+// LA = 3: a position is two MFMAs here (six on two limbs), so the fragments are requested one position further ahead
+int wino_launch_f16(const WinoArgs& a, bool gn, hipStream_t stream) {
+    if (gn) return launch_wino8s<0, true, false, 3, false, 1>(a, stream, "psld_conv3x3_wino_gn_f16_f32");
+    if (a.N % 128) return launch_wino8s<0, false, false, 3, true, 1>(a, stream, "psld_conv3x3_wino_f16_f32");
+    return launch_wino8s<0, false, false, 3, false, 1>(a, stream, "psld_conv3x3_wino_f16_f32");
+}
+
 int wino_launch_x3(const WinoArgs& a, bool gn, hipStream_t stream) {
     if (gn) return launch_wino8s<0, true, false, 2, false, 2>(a, stream, "psld_conv3x3_wino_gn_x3_f32");
     if (a.N % 128) return launch_wino8s<0, false, false, 2, true, 2>(a, stream, "psld_conv3x3_wino_x3_f32");
@@ -930,12 +1013,14 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
         s.C = reinterpret_cast<float*>(workspace);
         s.ldc = cout;
         s.e = make_epilogue(nullptr);
-        const int rc = nl == 2 ? wino_launch_x3(s, gn != nullptr, stream)
+        const int rc = nl == 1 ? wino_launch_f16(s, gn != nullptr, stream)
+                       : nl == 2 ? wino_launch_x3(s, gn != nullptr, stream)
                        : gn    ? launch_wino8s<0, true>(s, stream, "psld_conv3x3_wino_gn_f32")
                                : (cout % 128 ? launch_wino8s<0, false, false, 2, true>(s, stream, name) : launch_wino8s<0>(s, stream, name));
         if (rc != PSLD_OK) return rc;
         return psld_detail_conv_reduce_epilogue(s.C, ks, a.M, cout, y, ldy, e, stream);
     }
+    if (nl == 1) return wino_launch_f16(a, gn != nullptr, stream);
     if (nl == 2) return wino_launch_x3(a, gn != nullptr, stream);
     if (gn) return launch_wino8s<0, true>(a, stream, "psld_conv3x3_wino_gn_f32");
     if (cout % 128) return launch_wino8s<0, false, false, 2, true>(a, stream, name);      // last channel tile cut short

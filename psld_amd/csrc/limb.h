@@ -40,6 +40,19 @@ __device__ __forceinline__ void split2(float x0, float x1, unsigned& hi, unsigne
     lo = cvt_pk_bf16(x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u));
 }
 
+// One fp16 "limb" (eval math f16: NL = 1 in the kernels): two fp32 values -> packed fp16 pair (x0 in the low half), round to
+// nearest even, CLAMPED to +-65504 first - a finite operand never becomes an infinity.  v_med3_f32 + v_cvt_pk_f16_f32 (gfx950),
+// the conversion as an opaque instruction like cvt_pk_bf16; fp16 subnormals are kept (down to 2^-24).  v_med3_f32 returns the
+// smallest operand when one is a NaN: a NaN operand enters the product as -65504.
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+__device__ __forceinline__ unsigned cvt_pk_f16(float x0, float x1) {
+    unsigned r;
+    asm("v_cvt_pk_f16_f32 %0, %1, %2"
+        : "=v"(r)
+        : "v"(__builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f)), "v"(__builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f)));
+    return r;
+}
+
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 

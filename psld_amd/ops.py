@@ -157,6 +157,23 @@ def record_math() -> str:
     return MATH_MODES[lib().psld_get_record_math()]
 
 
+EVAL_MATHS = ("limb", "f16")     # PSLD_EVAL_MATH_* of include/psld_hip.h
+
+
+def set_eval_math(kind: str):
+    """Arithmetic of the forwards that record no backward pass: 'limb' (default: they follow the math mode) or 'f16' (opt-in;
+    under a limb math mode they run the one-product fp16 ``*_f16`` launches where one exists - Winograd 3x3 forward, eight-wave
+    pointwise forward - and the 'bf16x3' launches elsewhere).  fp16 operands carry 11 significant bits: ~1e-3 rel-L2 on a
+    network forward, what the reference's default TF32 convolutions give - NOT fp32-equivalent.  Process-wide."""
+    if kind not in EVAL_MATHS:
+        raise ValueError(f"eval math must be 'limb' or 'f16', got {kind!r}")
+    check(lib().psld_set_eval_math(EVAL_MATHS.index(kind)), "psld_set_eval_math")
+
+
+def eval_math() -> str:
+    return EVAL_MATHS[lib().psld_get_eval_math()]
+
+
 @functools.lru_cache(maxsize=None)
 def conv3x3_split_supported(c1: int, c2: int, b: int, h: int, w: int, cout: int) -> bool:
     return bool(lib().psld_conv3x3_split_supported(c1, c2, b, h, w, cout))
@@ -290,6 +307,37 @@ def conv3x3_wino_gn_x3(x1: Tensor, st1: "GNStats", x2: Optional[Tensor], st2: Op
                        cout: int, y: Tensor, epi: Optional[Epilogue] = None, allow_split: bool = False):
     """conv3x3_wino_gn on two-limb fragments (conv3x3_wino_frag_x3)."""
     _wino("psld_conv3x3_wino_gn_x3_f32", None, x1, x2, ufrag, cout, y, epi, y.shape[-1], allow_split, (st1, st2, act))
+
+
+# ---- one fp16 plane (eval math 'f16'): same shapes and tables again ----------------------------------------------------------
+def conv3x3_wino_frag_bytes_f16(cout: int, cin: int) -> int:
+    return int(lib().psld_conv3x3_wino_frag_bytes_f16(cout, cin))
+
+
+def conv3x3_wino_frag_f16(w_oihw: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """3x3 weights -> G g G^T rounded once to fp16, one plane in MFMA operand order (psld_conv3x3_wino_frag_bytes_f16 bytes)."""
+    co, ci = w_oihw.shape[0], w_oihw.shape[1]
+    if out is None:
+        out = torch.empty(conv3x3_wino_frag_bytes_f16(co, ci), dtype=torch.uint8, device=w_oihw.device)
+    check(lib().psld_pack_conv3x3_wino_f16(w_oihw.data_ptr(), out.data_ptr(), co, ci, _stream()), "psld_pack_conv3x3_wino_f16")
+    return out
+
+
+def pack_wino_batch_f16(table: Tensor, entries: int, total_items: int):
+    """pack_wino_batch into fp16 fragment buffers (rows: conv3x3_wino_frag_entry(w, False, out) + [first work item])."""
+    check(lib().psld_pack_wino_batch_f16(table.data_ptr(), entries, total_items, _stream()), "psld_pack_wino_batch_f16")
+
+
+def conv3x3_wino_f16(x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: Tensor,
+                     epi: Optional[Epilogue] = None, ldy: Optional[int] = None, allow_split: bool = False):
+    """conv3x3_wino on fp16 fragments (conv3x3_wino_frag_f16): V and U rounded once to fp16, one product each."""
+    _wino("psld_conv3x3_wino_f16_f32", None, x1, x2, ufrag, cout, y, epi, ldy, allow_split)
+
+
+def conv3x3_wino_gn_f16(x1: Tensor, st1: "GNStats", x2: Optional[Tensor], st2: Optional["GNStats"], act: bool, ufrag: Tensor,
+                        cout: int, y: Tensor, epi: Optional[Epilogue] = None, allow_split: bool = False):
+    """conv3x3_wino_gn on fp16 fragments (conv3x3_wino_frag_f16)."""
+    _wino("psld_conv3x3_wino_gn_f16_f32", None, x1, x2, ufrag, cout, y, epi, y.shape[-1], allow_split, (st1, st2, act))
 
 
 _WINO_MODE = None     # 0: never, 1: where it pays (default), 2: wherever the kernel takes the shape (tests)
@@ -483,6 +531,45 @@ def gemm_split_x3(a1: Tensor, a2: Optional[Tensor], m: int, bfrag: Tensor, n: in
     check(lib().psld_gemm_split_x3_f32(a1.data_ptr(), k1, _p(a2), k2, m, bfrag.data_ptr(), n, y.data_ptr(),
                                        ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
                                        _stream()), "psld_gemm_split_x3_f32")
+
+
+# ---- one fp16 plane (eval math 'f16'): the same GEMMs on the eight-wave kernel's one-product form ---------------------------
+@functools.lru_cache(maxsize=None)
+def gemm_split_f16_supported(k1: int, k2: int, m: int, n: int) -> bool:
+    return bool(lib().psld_gemm_split_f16_supported(k1, k2, m, n))
+
+
+def gemm_split_f16_wanted(k1: int, k2: int, m: int, n: int) -> bool:
+    """Policy of eval math 'f16': gemm_split_x3_wanted's - the forward GEMMs of at least 128 tiles of 128 x 256."""
+    return gemm_split_f16_supported(k1, k2, m, n) and -(-m // 128) * (n // 256) >= 128
+
+
+def gemm_frag_bytes_f16(n: int, k: int) -> int:
+    return int(lib().psld_gemm_frag_bytes_f16(n, k))
+
+
+def gemm_frag_f16(b: Tensor, n: int, k: int, stride_n: int, stride_k: int, out: Optional[Tensor] = None) -> Tensor:
+    """gemm_frag as one plane of fp16 values (psld_gemm_frag_bytes_f16 bytes)."""
+    if out is None:
+        out = torch.empty(gemm_frag_bytes_f16(n, k), dtype=torch.uint8, device=b.device)
+    check(lib().psld_pack_gemm_frag_f16(b.data_ptr(), out.data_ptr(), n, k, stride_n, stride_k, _stream()),
+          "psld_pack_gemm_frag_f16")
+    return out
+
+
+def pack_frag_batch_f16(table: Tensor, entries: int, total_items: int):
+    """pack_frag_batch into fp16 fragment buffers (pointwise rows: taps = 1)."""
+    check(lib().psld_pack_frag_batch_f16(table.data_ptr(), entries, total_items, _stream()), "psld_pack_frag_batch_f16")
+
+
+def gemm_split_f16(a1: Tensor, a2: Optional[Tensor], m: int, bfrag: Tensor, n: int, y: Tensor,
+                   epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
+    """gemm_split on fp16 fragments (gemm_frag_f16), for the shapes gemm_split_f16_supported takes."""
+    k1 = a1.shape[-1]
+    k2 = a2.shape[-1] if a2 is not None else 0
+    check(lib().psld_gemm_split_f16_f32(a1.data_ptr(), k1, _p(a2), k2, m, bfrag.data_ptr(), n, y.data_ptr(),
+                                        ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
+                                        _stream()), "psld_gemm_split_f16_f32")
 
 
 @functools.lru_cache(maxsize=None)

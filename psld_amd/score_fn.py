@@ -35,7 +35,7 @@ from .score_modules import (NIN, AttnBlockpp, Downsample, GaussianFourierProject
                             _Affine, _conv, _groupnorm, _linear, default_init)
 from .score_routes import _pick_nsplit  # noqa: F401  (tests / tools import it from here)
 from .score_tape import _SLAB_FLUSH_BYTES, _CatNode, _Node  # noqa: F401
-from .score_weights import (_frag_entry, _packed_entry, _pfrag_entry, _qkv_entry, _temb_entry, _wfrag_x3_entry, pfrag_tail)
+from .score_weights import (_frag_entry, _packed_entry, _pfrag_entry, _qkv_entry, _temb_entry, _wfrag_f16_entry, _wfrag_x3_entry, pfrag_tail)
 from .weight_cache import Entry, WeightCache
 
 Tensor = torch.Tensor
@@ -233,6 +233,7 @@ class NCSNpp(nn.Module):
         self._wcache = WeightCache({"limb": (ops.pack_frag_batch, 2), "limb_tail": (ops.pack_frag_batch_tail, 2),
                                     "wino": (ops.pack_wino_batch, 2),
                                     "limb_x3": (ops.pack_frag_batch_x3, 2), "wino_x3": (ops.pack_wino_batch_x3, 2),
+                                    "limb_f16": (ops.pack_frag_batch_f16, 2), "wino_f16": (ops.pack_wino_batch_f16, 2),
                                     "qkv_bias": (ops.copy_batch, 1), "temb": (ops.copy_batch, 1)})
         self._anchor = None
         self._reducer = None
@@ -386,12 +387,17 @@ class NCSNpp(nn.Module):
         """Two-limb Winograd fragments of a 3x3 weight (ops.conv3x3_wino_frag_x3 / conv3x3_wino_dgrad_frag_x3)."""
         return self._wcache.get(conv.weight, "wfrag_d_x3" if dgrad else "wfrag_x3", _wfrag_x3_entry, dgrad)
 
+    def _wfrag_f16(self, conv: _Affine) -> Tensor:
+        """One-plane fp16 Winograd fragments of a 3x3 weight (ops.conv3x3_wino_frag_f16; eval math 'f16')."""
+        return self._wcache.get(conv.weight, "wfrag_f16", _wfrag_f16_entry)
+
     def _pfrag(self, owner: nn.Parameter, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor] = None,
                chunk0: int = 0, chunks_total: int = 0, n0: int = 0, n_total: int = 0) -> Tensor:
         """Limb fragments (ops.gemm_frag) of the [n][k] view of ONE parameter (element (i, j) at i*sn + j*sk), refreshed
         together with the 3x3 fragments by the batched launch.  ``into``: the buffer to fill (several parameters that
         share one fragment set: q | k | v) - then ``chunk0`` / ``chunks_total`` place this parameter's K range inside the
-        set's K dimension (psld_pack_frag_batch).  A ``tag`` ending in ``_x3``: two-limb fragments (ops.gemm_frag_x3).
+        set's K dimension (psld_pack_frag_batch).  A ``tag`` ending in ``_x3``: two-limb fragments (ops.gemm_frag_x3), in ``_f16``:
+        one fp16 plane (ops.gemm_frag_f16).
         A set that is no whole number of 128 x 64 tiles (score_weights.pfrag_tail: channel widths in steps of 32) is packed
         as padded three-limb tail fragments (ops.gemm_frag_tail); ``n0`` / ``n_total`` then place the parameter's rows
         inside a shared set's N dimension."""
@@ -420,11 +426,18 @@ class NCSNpp(nn.Module):
             self._pfrag(nin.W, "qkv_d", c, c, c, 1, into=pd, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
         return self._wcache.fresh(e)
 
-    def _qkv_frags_x3(self, mod, dgrad: bool = False):
+    def _qkv_frags_x3(self, mod, dgrad: bool = False, f16: bool = False):
         """The forward (``dgrad``: data-gradient) q | k | v fragment set of _qkv_frags in two-limb form (math mode / record
-        math 'bf16x3'; whole-tile sets only: c % 128 == 0)."""
+        math 'bf16x3'; whole-tile sets only: c % 128 == 0).  ``f16``: the forward set as one fp16 plane (eval math 'f16')."""
         n0 = mod.NIN_0
         c = n0.W.shape[0]
+        if f16:
+            fb = ops.gemm_frag_bytes_f16(c, c)
+            pf = self._wcache.entry(n0.W, "qkv_set_f16", lambda w: Entry(
+                w, out=torch.empty(3 * fb, dtype=torch.uint8, device=w.device), build=lambda prev: prev)).out
+            for i, nin in enumerate((n0, mod.NIN_1, mod.NIN_2)):
+                self._pfrag(nin.W, "qkv_f_f16", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
+            return pf
         fb = ops.gemm_frag_bytes_x3(c, c)
         # the holder of the shared buffer (no family: the "qkv_d_x3" / "qkv_f_x3" entries of the three projections fill it)
         pf = self._wcache.entry(n0.W, "qkv_set_d_x3" if dgrad else "qkv_set_x3", lambda w: Entry(
@@ -587,7 +600,7 @@ class NCSNpp(nn.Module):
             self._graphs = {}
 
     def _graph_forward(self, x: Tensor, t: Tensor) -> Tensor:
-        key = (tuple(x.shape), x.device.index, ops.math_mode())     # a capture replays the launches of its math mode
+        key = (tuple(x.shape), x.device.index, ops.math_mode(), ops.eval_math())     # a capture replays the launches of its math mode and eval math
         ent = self._graphs.get(key)
         if ent is None:
             sx, st = x.clone(), t.clone()

@@ -108,6 +108,10 @@ class _ExecBase:
         # math mode, its forward launches, its Winograd / pointwise data gradients and its Winograd-domain weight gradients are
         # the two-limb ones (direct limb 3x3 kernels, pointwise / NIN weight gradients and attention products have no such form)
         self.x3 = (mode == "bf16x3" and not record) or (record and self.split and ops.record_math() == "bf16x3")
+        # eval math 'f16' (ops.set_eval_math, opt-in; PSLD_MATH=f16 sets it together with math mode 'bf16x3'): a forward that
+        # records no backward pass runs the one-product fp16 form of the Winograd-forward and eight-wave pointwise launches;
+        # everything else, and every recording pass, runs as without it.  NOT fp32-equivalent (~1e-3 rel-L2: DESIGN 4b''')
+        self.f16 = self.split and not record and ops.eval_math() == "f16"
         self.limb_planes = os.environ.get("PSLD_LIMB_PLANES", "1") != "0"    # A/B switch for tools/bench_sample.py
         # forward attention in one kernel (attention.hip) wherever it takes the shape (B=128: 8x8 maps 17 vs 54 us of the
         # three-kernel path, 16x16 maps 62-65 vs 72 us, tools/bench_attn.py); PSLD_FUSED_ATTN=0: the three kernels
@@ -408,7 +412,9 @@ class _ExecBase:
         if route is None:
             route = R.conv3_route(self.split, c, c2, b, h, w, cout, isinstance(x, ops.LimbPlanes), self.wino_wanted)
         if route == R.WINO:
-            if self.x3:
+            if self.f16:
+                ops.conv3x3_wino_f16(x, x2, self.net._wfrag_f16(conv), cout, out, epi, allow_split=True)
+            elif self.x3:
                 ops.conv3x3_wino_x3(x, x2, self.net._wfrag_x3(conv), cout, out, epi, allow_split=True)
             else:
                 ops.conv3x3_wino(x, x2, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)   # Winograd F(2x2, 3x3)
@@ -420,18 +426,23 @@ class _ExecBase:
     def conv3_gn(self, x: Tensor, st, x2: Optional[Tensor], st2, conv: _Affine, out: Tensor, epi):
         """SiLU(GroupNorm(.)) + 3x3 convolution in one launch (ops.conv3x3_wino_gn; inference forward only)."""
         cout = conv.weight.shape[0]
-        if self.x3:
+        if self.f16:
+            ops.conv3x3_wino_gn_f16(x, st, x2, st2, True, self.net._wfrag_f16(conv), cout, out, epi, allow_split=True)
+        elif self.x3:
             ops.conv3x3_wino_gn_x3(x, st, x2, st2, True, self.net._wfrag_x3(conv), cout, out, epi, allow_split=True)
         else:
             ops.conv3x3_wino_gn(x, st, x2, st2, True, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)
 
     # -- pointwise GEMMs (1x1 shortcuts, NIN projections, the pyramid's im2col GEMM) on a score_routes.pointwise_* route ------
     def pw_fwd(self, route: str, a1: Tensor, a2: Optional[Tensor], m: int, w: PointwiseWeight, y: Tensor, epi):
-        """y[m][w.n] = epi([a1 | a2] W^T).  LIMB runs the two-limb form where math mode 'bf16x3' wants it (LIMB_TAIL has none);
+        """y[m][w.n] = epi([a1 | a2] W^T).  LIMB runs the fp16 form where eval math 'f16', else the two-limb form where math mode
+        'bf16x3', wants it (LIMB_TAIL has neither);
         TILE is the tile engine's 1x1 convolution for an "oi" weight (it alone takes a second source), its GEMM for NIN."""
         n = w.n
         if route == R.LIMB_TAIL:
             ops.gemm_split_tail(a1, m, w.frag(tail=True), n, y, epi)
+        elif route == R.LIMB and self.f16 and ops.gemm_split_f16_wanted(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n):
+            ops.gemm_split_f16(a1, a2, m, w.frag(f16=True), n, y, epi)
         elif route == R.LIMB and self.x3 and ops.gemm_split_x3_wanted(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n):
             ops.gemm_split_x3(a1, a2, m, w.frag(x3=True), n, y, epi)
         elif route == R.LIMB:

@@ -38,6 +38,12 @@ def _wfrag_x3_entry(w: Tensor, dgrad: bool = False) -> Entry:
                  rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
 
 
+def _wfrag_f16_entry(w: Tensor) -> Entry:
+    """One-plane fp16 Winograd fragments (forward orientation): the 'wino' entries' siblings for eval math 'f16'."""
+    return Entry(w, build=lambda prev: ops.conv3x3_wino_frag_f16(w.detach(), prev), family="wino_f16",
+                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, False, out), w.shape[0] * w.shape[1] // 8)], graph=True)
+
+
 def pfrag_tail(n: int, k: int, n_total: int = 0, chunks_total: int = 0) -> bool:
     """The fragment set of an [n_total or n][32 * chunks_total or k] matrix is no whole number of 128 x 64 tiles: it is
     packed by the tail packers (ops.gemm_frag_tail) and read by ops.gemm_split_tail."""
@@ -64,7 +70,9 @@ def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Op
     if pfrag_tail(n, k, n_total, chunks_total):
         return _pfrag_tail_entry(p, tag, n, k, sn, sk, into, chunk0, chunks_total, n0, n_total)
     x3 = tag.endswith("_x3")        # two-limb fragments (math mode 'bf16x3'): their own packers and batch family
-    pack, pack_batch = (ops.gemm_frag_x3, ops.pack_frag_batch_x3) if x3 else (ops.gemm_frag, ops.pack_frag_batch)
+    f16 = tag.endswith("_f16")      # one fp16 plane (eval math 'f16'): likewise
+    pack, pack_batch = (ops.gemm_frag_x3, ops.pack_frag_batch_x3) if x3 else \
+        (ops.gemm_frag_f16, ops.pack_frag_batch_f16) if f16 else (ops.gemm_frag, ops.pack_frag_batch)
 
     def rows(out):
         return [([p.data_ptr(), out.data_ptr(), n, k | (chunk0 << 20) | (chunks_total << 40), 1, sn, sk], n * k // 8)]
@@ -76,8 +84,8 @@ def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Op
         (row, items), = rows(into)
         pack_batch(torch.tensor(row + [0], dtype=torch.int64, device=p.device), 1, items)
         return into
-    return Entry(p, build=build, family="limb_x3" if x3 else "limb", rows=rows,
-                 graph=tag in ("fwd", "qkv_f", "fwd_x3", "qkv_f_x3"))
+    return Entry(p, build=build, family="limb_x3" if x3 else "limb_f16" if f16 else "limb", rows=rows,
+                 graph=tag in ("fwd", "qkv_f", "fwd_x3", "qkv_f_x3", "fwd_f16", "qkv_f_f16"))
 
 
 def _built_entry(owner: Tensor, build) -> Entry:
@@ -145,16 +153,19 @@ class PointwiseWeight(NamedTuple):
         oi = self.kind == "oi"
         return self.w, int(oi != dgrad), self.k if oi else self.n
 
-    def frag(self, dgrad: bool = False, x3: bool = False, tail: bool = False) -> Tensor:
-        """Three-limb (``x3``: two-limb, whole-tile sets only) fragments of B[n][k], or of B[k][n] for the data gradient."""
+    def frag(self, dgrad: bool = False, x3: bool = False, tail: bool = False, f16: bool = False) -> Tensor:
+        """Three-limb (``x3``: two-limb, ``f16``: one fp16 plane, forward only - both whole-tile sets only) fragments of B[n][k],
+        or of B[k][n] for the data gradient."""
         net, w, kind = self.net, self.w, self.kind
         n, k = (self.k, self.n) if dgrad else (self.n, self.k)
+        assert not (f16 and (dgrad or x3 or tail))
+        sfx = "_x3" if x3 else "_f16" if f16 else ""
         if kind == "qkv":
-            return net._qkv_frags_x3(w, dgrad) if x3 else self.qkv[int(dgrad)]
+            return net._qkv_frags_x3(w, dgrad, f16) if x3 or f16 else self.qkv[int(dgrad)]
         if kind == "ohwi":
-            pack = ops.gemm_frag_x3 if x3 else ops.gemm_frag_tail if tail else ops.gemm_frag
+            pack = ops.gemm_frag_x3 if x3 else ops.gemm_frag_f16 if f16 else ops.gemm_frag_tail if tail else ops.gemm_frag
             sn, sk = (1, n) if dgrad else (k, 1)
-            return net._wcache.get(w.weight, ("s2dgrad" if dgrad else "s2fwd") + ("_x3" if x3 else ""), _built_entry,
+            return net._wcache.get(w.weight, ("s2dgrad" if dgrad else "s2fwd") + sfx, _built_entry,
                                    lambda prev: pack(net._packed(w), n, k, sn, sk, prev))
         _, rows, ld = self.tile(dgrad)          # rows: B's rows are the stored matrix's rows
-        return net._pfrag(w, ("dgrad" if dgrad else "fwd") + ("_x3" if x3 else ""), n, k, *((ld, 1) if rows else (1, ld)))
+        return net._pfrag(w, ("dgrad" if dgrad else "fwd") + sfx, n, k, *((ld, 1) if rows else (1, ld)))
