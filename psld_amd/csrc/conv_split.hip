@@ -301,11 +301,15 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
         bias4[nb] = e_bias ? *reinterpret_cast<const f32x4v*>(e_bias + cn0 + nb * 16) : zero4;
-    float gs[RUNS][2], gss[RUNS][2];     // [64-row run][block column]
+    // GroupNorm sums of the stored values, [64-row run][block column], in fp64 from the first addition on: v * v of an fp32
+    // v is exact in fp64, so sum and sum of squares carry no rounding a group's mean could amplify (var = E[x^2] - E[x]^2
+    // from fp32 sums loses (mean / std)^2 * 2^-24 of its value - 2e-4 of rstd at mean = 100 std)
+    const bool gn_on = uni(a.e.gn_part) != nullptr;
+    double gs[RUNS][2], gss[RUNS][2];
 #pragma unroll
     for (int r = 0; r < RUNS; ++r)
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) gs[r][nb] = gss[r][nb] = 0.f;
+        for (int nb = 0; nb < 2; ++nb) gs[r][nb] = gss[r][nb] = 0.0;
     // STRAIGHT-LINE code, no branch around a memory instruction: loads and stores share one in-order counter on this chip,
     // and behind a branch the compiler can only wait for "everything" (vmcnt(0)) - i.e. for the stores of the previous
     // block row as well.  Absent operands (no residual / previous output / row bias) are read from the 16-byte zero
@@ -343,10 +347,13 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
             o += cv[nb];
             if (ok) {
                 *reinterpret_cast<f32x4v*>(Cb + coff + gn) = o;
+                if (gn_on) {
 #pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    gs[mb >> 2][nb] += o[v];
-                    gss[mb >> 2][nb] += o[v] * o[v];
+                    for (int v = 0; v < 4; ++v) {
+                        const double d = (double)o[v];
+                        gs[mb >> 2][nb] += d;
+                        gss[mb >> 2][nb] = fma(d, d, gss[mb >> 2][nb]);
+                    }
                 }
             }
         }
@@ -364,7 +371,7 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
 #pragma unroll
         for (int mb = 0; mb < MBK; ++mb) row_store(mb, z2, z2, z2);
     }
-    if (e.gn_part) {
+    if (gn_on) {
         // a lane holds 4 channels of a block column (quad kq = lane >> 4), its 16-lane row the 16 pixels of a block row: the
         // butterfly over sft = 1..8 sums the pixels (four-channel sums, gn_fine = 4), sft = 16 adds the partner quad (eight)
         const bool fine4 = e.gn_fine == 4;
@@ -376,7 +383,7 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
             const int img = row0 / e.gn_hw, chunk = (row0 - img * e.gn_hw) >> 6;
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
-                float s1 = gs[r][nb], s2 = gss[r][nb];
+                double s1 = gs[r][nb], s2 = gss[r][nb];
 #pragma unroll
                 for (int sft = 1; sft <= 8; sft <<= 1) {
                     s1 += __shfl_xor(s1, sft, 64);
@@ -386,8 +393,8 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
                     if ((lane & 0xf) == 0) {
                         const int f = ((nw0 + nb * 16) >> 2) + (lane >> 4);
                         double* pp = e.gn_part + (((long long)img * chunks + chunk) * fine + f) * 2;
-                        pp[0] = (double)s1;
-                        pp[1] = (double)s2;
+                        pp[0] = s1;
+                        pp[1] = s2;
                     }
                     continue;
                 }
@@ -396,8 +403,8 @@ __device__ __forceinline__ void dconv_epilogue_n32(const DConvArgs& a, f32x4v (&
                 if ((lane & 0x1f) == 0) {
                     const int f = ((nw0 + nb * 16) >> 3) + (lane >> 5);
                     double* pp = e.gn_part + (((long long)img * chunks + chunk) * fine + f) * 2;
-                    pp[0] = (double)s1;
-                    pp[1] = (double)s2;
+                    pp[0] = s1;
+                    pp[1] = s2;
                 }
             }
         }

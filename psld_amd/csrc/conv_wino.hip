@@ -630,7 +630,10 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
                 if (e.accumulate) x += epi_cv[tb][ya * 2 + xb];
                 o[ya][xb] = x;
             }
-        float gs = 0.f, gss = 0.f;
+        // GroupNorm sums of the stored values in fp64 from the first addition on (v * v of an fp32 v is exact there: no
+        // rounding in sum or sum of squares for a group's mean to amplify - conv_split.hip's epilogue, same reason)
+        const bool gn_on = e.gn_part != nullptr;
+        double gs = 0.0, gss = 0.0;
         if (ok) {
 #pragma unroll
             for (int ya = 0; ya < 2; ++ya)
@@ -639,21 +642,24 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
                     const int px = rel + ya * a.W + xb;
                     if ((ABL & 8) && org + px != 0) continue;
                     *reinterpret_cast<f32x4v*>(c_b + (unsigned)((px * a.ldc + cn) * 4)) = o[ya][xb];
+                    if (gn_on) {
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        gs += o[ya][xb][v];
-                        gss += o[ya][xb][v] * o[ya][xb][v];
+                        for (int v = 0; v < 4; ++v) {
+                            const double d = (double)o[ya][xb][v];
+                            gs += d;
+                            gss = fma(d, d, gss);
+                        }
                     }
                 }
         }
-        if (e.gn_part) {
-            float s1 = gs, s2 = gss;
+        if (gn_on) {
+            double s1 = gs, s2 = gss;
 #pragma unroll
             for (int sft = 1; sft <= 8; sft <<= 1) {
                 s1 += __shfl_xor(s1, sft, 64);
                 s2 += __shfl_xor(s2, sft, 64);
             }
-            const float q1 = s1, q2 = s2;                // four-channel sums of this lane's quad (gn_fine = 4)
+            const double q1 = s1, q2 = s2;               // four-channel sums of this lane's quad (gn_fine = 4)
             s1 += __shfl_xor(s1, 16, 64);
             s2 += __shfl_xor(s2, 16, 64);
             // tile block tb = 64 pixels of one image = one run of the partial-sum table (any fixed partition of an image
@@ -663,14 +669,14 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
                 if ((lane & 0xf) == 0 && img < a.B) {
                     const int f = ((n0 + wave * 16) >> 2) + (lane >> 4);
                     double* pp = e.gn_part + (((long long)img * chunks + chunk) * (a.N >> 2) + f) * 2;
-                    pp[0] = (double)q1;
-                    pp[1] = (double)q2;
+                    pp[0] = q1;
+                    pp[1] = q2;
                 }
             } else if ((lane & 0x1f) == 0 && img < a.B) {
                 const int f = ((n0 + wave * 16) >> 3) + (lane >> 5);
                 double* pp = e.gn_part + (((long long)img * chunks + chunk) * (a.N >> 3) + f) * 2;
-                pp[0] = (double)s1;
-                pp[1] = (double)s2;
+                pp[0] = s1;
+                pp[1] = s2;
             }
         }
     }

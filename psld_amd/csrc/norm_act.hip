@@ -6,8 +6,10 @@
 // Thread mapping for every kernel here: a block owns one image `n` and a contiguous chunk of
 // its pixels.  Thread -> (channel quad q = tid % CQ, pixel lane pl = tid / CQ), CQ = C/4, so a
 // wave reads whole 16-byte-per-lane contiguous runs of the NHWC row (coalesced float4).
-// Reductions: per-thread fp32 partials over <= ~64 pixels, then fp64 across threads (LDS) and
-// across chunks (finalize kernel) — deterministic, no atomics.
+// Reductions: per-thread partials over <= ~64 pixels, then fp64 across threads (LDS) and across chunks (finalize
+// kernel) — deterministic, no atomics.  The forward statistics (sum x, sum x^2) are fp64 from the first addition on: the
+// finalize kernel's var = E[x^2] - E[x]^2 amplifies any rounding of the sums by (mean / std)^2, and x * x of an fp32 x is
+// exact in fp64 (tests/test_conditioning_gpu.py).  The backward partials stay fp32.
 #include "common.h"
 #include "psld_hip.h"
 
@@ -51,22 +53,23 @@ __global__ void gn_partial_kernel(const float* __restrict__ x, int hw, int c, in
     const int q = tid % cq, l = tid / cq;
     const int p0 = chunk * chunk_px, p1 = min(hw, p0 + chunk_px);
     const float* base = x + ((long long)n * hw) * c + q * 4;
-    float s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+    double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
 #pragma unroll 4
     for (int p = p0 + l; p < p1; p += pl) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(base + (long long)p * c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            s[e] += v[e];
-            ss[e] += v[e] * v[e];
+            const double d = (double)v[e];
+            s[e] += d;
+            ss[e] = fma(d, d, ss[e]);
         }
     }
     const int cpg = c / groups;
     double* out = part + (((long long)n * chunks + chunk) * groups) * 2;
     if (cpg % 4 == 0) {
         // a channel quad lies in one group: group g = quads [g*cpg/4, (g+1)*cpg/4) x all pixel lanes
-        ts[tid][0] = (double)s[0] + (double)s[1] + (double)s[2] + (double)s[3];
-        ts[tid][1] = (double)ss[0] + (double)ss[1] + (double)ss[2] + (double)ss[3];
+        ts[tid][0] = s[0] + s[1] + s[2] + s[3];
+        ts[tid][1] = ss[0] + ss[1] + ss[2] + ss[3];
         __syncthreads();
         if (tid < groups * 2) {
             const int g = tid >> 1, w = tid & 1, qpg = cpg / 4;
@@ -78,8 +81,8 @@ __global__ void gn_partial_kernel(const float* __restrict__ x, int hw, int c, in
     } else {
         double t = 0.0;                          // thread (g, w) accumulates over the four element rounds
         for (int e = 0; e < 4; ++e) {
-            ts[tid][0] = (double)s[e];
-            ts[tid][1] = (double)ss[e];
+            ts[tid][0] = s[e];
+            ts[tid][1] = ss[e];
             __syncthreads();
             if (tid < groups * 2) {
                 const int g = tid >> 1, w = tid & 1;

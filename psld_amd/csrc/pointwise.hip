@@ -644,6 +644,9 @@ __global__ void softmax_rows_reg_kernel(const float* __restrict__ x, float* __re
 #pragma unroll
     for (int j = 0; j < V; ++j) yp[lane + 64 * j] = v[j] * inv;
 }
+// backward: dx = y (dy - sum y dy).  On a peaked row (one y next to 1) the sum is next to that entry's dy, and the difference
+// is the whole gradient of the entry: sum and difference are formed in fp64 (an fp32 product is exact there) and rounded once -
+// in fp32 the difference was pure rounding noise, 6e-8 |dy| against a true value below it (tests/test_conditioning_gpu.py)
 template <int V>
 __global__ void softmax_rows_bwd_reg_kernel(const float* __restrict__ y, const float* __restrict__ dy,
                                             float* __restrict__ dx, long long rows, int L) {
@@ -653,17 +656,23 @@ __global__ void softmax_rows_bwd_reg_kernel(const float* __restrict__ y, const f
     const f32x4* yp = reinterpret_cast<const f32x4*>(y + row * L);
     const f32x4* gp = reinterpret_cast<const f32x4*>(dy + row * L);
     f32x4 yv[V], gv[V];
-    float d = 0.f;
+    double d = 0.0;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
         yv[j] = yp[lane + 64 * j];
         gv[j] = gp[lane + 64 * j];
-        d += yv[j][0] * gv[j][0] + yv[j][1] * gv[j][1] + yv[j][2] * gv[j][2] + yv[j][3] * gv[j][3];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d = fma((double)yv[j][e], (double)gv[j][e], d);
     }
-    d = wave_sum(d);
+    d = wave_sum_d(d);
     f32x4* op = reinterpret_cast<f32x4*>(dx + row * L);
 #pragma unroll
-    for (int j = 0; j < V; ++j) op[lane + 64 * j] = yv[j] * (gv[j] - d);
+    for (int j = 0; j < V; ++j) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = yv[j][e] * (float)((double)gv[j][e] - d);
+        op[lane + 64 * j] = o;
+    }
 }
 
 // generic fallback: one wave64 per row
@@ -694,10 +703,10 @@ __global__ void softmax_rows_bwd_kernel(const float* __restrict__ y, const float
     const int lane = threadIdx.x & 63;
     const float* yp = y + row * L;
     const float* gp = dy + row * L;
-    float d = 0.f;
-    for (int i = lane; i < L; i += 64) d += yp[i] * gp[i];
-    d = wave_sum(d);
-    for (int i = lane; i < L; i += 64) dx[row * L + i] = yp[i] * (gp[i] - d);
+    double d = 0.0;
+    for (int i = lane; i < L; i += 64) d = fma((double)yp[i], (double)gp[i], d);
+    d = wave_sum_d(d);
+    for (int i = lane; i < L; i += 64) dx[row * L + i] = yp[i] * (float)((double)gp[i] - d);
 }
 
 // ---- time embedding ---------------------------------------------------------------------------------

@@ -769,17 +769,19 @@ __global__ void conv_reduce_epilogue_kernel(const float* __restrict__ slabs, int
 // sum of squares], float64) - so a split launch no longer costs its GroupNorm a pass over the tensor (gn_partial_kernel: 54
 // launches of the B=128 step, every GroupNorm of the 8x8 level).  Workgroup = one 64-row run x 64 channels; thread = float4
 // column q of the slab, rows rg + 16 i.  Fixed order: rows and components in the thread, the four row groups of a wave by two
-// shuffles, the four waves through LDS - bitwise repeatable.
+// shuffles, the four waves through LDS - bitwise repeatable.  Both sums are fp64 from the first addition on (v * v of an
+// fp32 v is exact there), like every other producer of these sums: fp32 sums would hand the consumer's E[x^2] - E[x]^2 an
+// error of (mean / std)^2 * 2^-24 of the variance.
 __global__ void __launch_bounds__(256) conv_reduce_epilogue_gn_kernel(const float* __restrict__ slabs, int nsplit, int M, int N,
                                                                         float* __restrict__ out, int ldc, const Epilogue e) {
-    __shared__ float red[4][16][2];
+    __shared__ double red[4][16][2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = lane & 15, rg = 4 * wave + (lane >> 4);
     const int run = blockIdx.x, n0 = blockIdx.y * 64 + q * 4;
     const long long slab = (long long)M * N;
     f32x4 bias = {0.f, 0.f, 0.f, 0.f};
     if (e.bias) bias = *reinterpret_cast<const f32x4*>(e.bias + n0);
-    float s1 = 0.f, s2 = 0.f;
+    double s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int m = run * 64 + rg + 16 * i;
@@ -805,8 +807,9 @@ __global__ void __launch_bounds__(256) conv_reduce_epilogue_gn_kernel(const floa
         *reinterpret_cast<f32x4*>(out + (long long)m * ldc + n0) = acc;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-            s1 += acc[v];
-            s2 += acc[v] * acc[v];
+            const double d = (double)acc[v];
+            s1 += d;
+            s2 = fma(d, d, s2);
         }
     }
     s1 += __shfl_xor(s1, 16, 64);
@@ -819,19 +822,19 @@ __global__ void __launch_bounds__(256) conv_reduce_epilogue_gn_kernel(const floa
     }
     __syncthreads();
     if (tid < 16) {
-        float t1 = ((red[0][tid][0] + red[1][tid][0]) + red[2][tid][0]) + red[3][tid][0];
-        float t2 = ((red[0][tid][1] + red[1][tid][1]) + red[2][tid][1]) + red[3][tid][1];
+        const double t1 = ((red[0][tid][0] + red[1][tid][0]) + red[2][tid][0]) + red[3][tid][0];
+        const double t2 = ((red[0][tid][1] + red[1][tid][1]) + red[2][tid][1]) + red[3][tid][1];
         const int c0 = blockIdx.y * 64 + tid * 4;
         if (e.gn_fine == 4) {
             double* pp = e.gn_part + ((long long)run * (N >> 2) + (c0 >> 2)) * 2;
-            pp[0] = (double)t1;
-            pp[1] = (double)t2;
+            pp[0] = t1;
+            pp[1] = t2;
         } else if ((tid & 1) == 0) {
-            const float u1 = ((red[0][tid + 1][0] + red[1][tid + 1][0]) + red[2][tid + 1][0]) + red[3][tid + 1][0];
-            const float u2 = ((red[0][tid + 1][1] + red[1][tid + 1][1]) + red[2][tid + 1][1]) + red[3][tid + 1][1];
+            const double u1 = ((red[0][tid + 1][0] + red[1][tid + 1][0]) + red[2][tid + 1][0]) + red[3][tid + 1][0];
+            const double u2 = ((red[0][tid + 1][1] + red[1][tid + 1][1]) + red[2][tid + 1][1]) + red[3][tid + 1][1];
             double* pp = e.gn_part + ((long long)run * (N >> 3) + (c0 >> 3)) * 2;
-            pp[0] = (double)(t1 + u1);
-            pp[1] = (double)(t2 + u2);
+            pp[0] = t1 + u1;
+            pp[1] = t2 + u2;
         }
     }
 }

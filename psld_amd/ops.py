@@ -203,10 +203,12 @@ def pack_frag_batch(table: Tensor, entries: int, total_items: int):
 
 
 def conv3x3_split(x1: Tensor, x2: Optional[Tensor], wfrag: Tensor, cout: int, y: Tensor,
-                  epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
+                  epi: Optional[Epilogue] = None, ldy: Optional[int] = None, workspace: bool = True):
+    """``workspace=False``: offer no split-K workspace, so that a small grid too runs the kernel's own epilogue (tests)."""
     b, h, w, c1 = x1.shape
     c2 = x2.shape[-1] if x2 is not None else 0
-    ws, wsb = _small_grid_ws(b * h * w, 32768, lambda: lib().psld_conv2d_workspace_bytes(b, h, w, cout), x1.device)
+    ws, wsb = (_small_grid_ws(b * h * w, 32768, lambda: lib().psld_conv2d_workspace_bytes(b, h, w, cout), x1.device)
+               if workspace else (None, 0))
     if isinstance(x1, LimbPlanes):       # pre-split input(s): the LDS-DMA kernel
         assert x2 is None or isinstance(x2, LimbPlanes)
         check(lib().psld_conv3x3_limb_f32(x1.data_ptr(), c1, x2.data_ptr() if x2 is not None else None, c2, b, h, w,
@@ -483,11 +485,12 @@ def gemm_frag(b: Tensor, n: int, k: int, stride_n: int, stride_k: int, out: Opti
 
 
 def gemm_split(a1: Tensor, a2: Optional[Tensor], m: int, bfrag: Tensor, n: int, y: Tensor,
-               epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
-    """y[m][n] = epilogue(concat(a1, a2) @ B^T) on the bf16 limb kernels; a1 / a2 are [m][k1] / [m][k2] contiguous."""
+               epi: Optional[Epilogue] = None, ldy: Optional[int] = None, workspace: bool = True):
+    """y[m][n] = epilogue(concat(a1, a2) @ B^T) on the bf16 limb kernels; a1 / a2 are [m][k1] / [m][k2] contiguous.
+    ``workspace=False``: offer no split-K workspace, so that a small grid too runs the kernel's own epilogue (tests)."""
     k1 = a1.shape[-1]
     k2 = a2.shape[-1] if a2 is not None else 0
-    ws, wsb = _small_grid_ws(m, 32768, lambda: 8 * m * n * 4, a1.device)
+    ws, wsb = _small_grid_ws(m, 32768, lambda: 8 * m * n * 4, a1.device) if workspace else (None, 0)
     check(lib().psld_gemm_split_f32(a1.data_ptr(), k1, _p(a2), k2, m, bfrag.data_ptr(), n, y.data_ptr(),
                                     ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
                                     ws, wsb, _stream()), "psld_gemm_split_f32")

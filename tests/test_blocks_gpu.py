@@ -211,6 +211,66 @@ def test_wide_resblock_against_the_oracle(cin, cout, hw, kw, two, winograd):
         ops.set_wgrad_winograd(None)
 
 
+@pytest.mark.parametrize("winograd", [2, 0])
+def test_wide_resblock_on_offset_groups(winograd):
+    """256 -> 256 @ 16 x 16, b = 2, with group means 30 spreads away from zero (tests/cond_ref.py): in the input, so that
+    GroupNorm_0 reads offset data through the statistics pass, and in Conv_0.bias, so that GroupNorm_1 reads it through the
+    sums of Conv_0's epilogue.  Reference: the oracle on fp64 copies; yardstick: the oracle in fp32; bound: 4 x the
+    yardstick's error + the project's fp32 contraction tolerance (tests/test_kernels_gpu.py: 2e-6 forward, 1e-5 for
+    gradients), since the limb kernels sum in another order than the yardstick.
+    Measured on the MI355X with fp32 statistics sums (before they became fp64), Winograd 2 / 0: output 3.2e-7 / 2.8e-7
+    (yardstick 7.3e-8, quotient 4.3 / 3.8: the floor of 2e-6 decides); grad x 5.9e-6 / 5.1e-6 (yardstick 7.7e-7, quotient 7.6 /
+    6.6); parameter gradients 3.6e-6..1.3e-5 (yardsticks 1.5e-6..4.1e-6, quotients 2.3..6.9; Conv_1.bias 6e-8, 0.16).  At this
+    ratio the case guards the route through the epilogue sums; the statistics tests of tests/test_conditioning_gpu.py are
+    the ones that fail on fp32 sums.  With fp64 sums: output 4.9e-8 / 5.0e-8 (quotient 0.67 / 0.68), grad x 3.6e-7 / 3.7e-7
+    (0.46 / 0.48), parameter gradients 6e-8..1.4e-6, largest quotient 0.73 (GroupNorm_0.bias, Winograd 0)."""
+    import torch.nn.functional as F
+    from psld_amd import ops, score_fn as S
+    from tests import cond_ref as R
+    ops.set_winograd(winograd)
+    ops.set_wgrad_winograd(winograd)
+    try:
+        b, c, hw, ratio = 2, 256, 16, 30
+        mod = S.ResnetBlockBigGANpp(c, c, temb_dim=128, dropout=0.0)
+        sd = synth_state_dict([(k, tuple(v.shape)) for k, v in mod.state_dict().items()], 79)
+        x = R.offset_groups(b, c, hw, hw, 32, ratio, 1.0, seed=9)
+        gen = torch.Generator().manual_seed(10)
+        temb = torch.randn(b, 128, generator=gen)
+        # Conv_0's bias: the same per-group pattern times ratio x the spread of its output
+        h0 = F.conv2d(F.silu(F.group_norm(x.double(), 32, sd["GroupNorm_0.weight"].double(), sd["GroupNorm_0.bias"].double(), 1e-6)),
+                      sd["Conv_0.weight"].double(), padding=1)
+        sd["Conv_0.bias"] = (R.group_offsets(1, 32, ratio, seed=11)[0] * h0.std()).repeat_interleave(c // 32).float()
+        h = Harness(mod, sd)
+        h.set_temb(temb)
+        a = h.S._Node(_nhwc(x))
+        with h.ops.stream_scope():
+            out = h.ex.resblock(a, h.mod)
+        gy = torch.randn(b, c, hw, hw, generator=gen)
+
+        def oracle(dt):
+            osd = {f"m.{k}": v.to(dt).requires_grad_(True) for k, v in sd.items()}
+            xo, to = x.to(dt).requires_grad_(True), temb.to(dt).requires_grad_(True)
+            yo = O.resblock_biggan(xo, to, osd, "m")
+            yo.backward(gy.to(dt))
+            return yo.detach(), xo.grad, to.grad, {k: osd[f"m.{k}"].grad for k in sd}
+        (y64, gx64, gt64, gw64), (y32, gx32, gt32, gw32) = oracle(torch.float64), oracle(torch.float32)
+        h.backward(out, _nhwc(gy))
+        rows = [("output", _nchw(out.v), y64, y32, 2e-6), ("grad x", _nchw(a.g), gx64, gx32, 1e-5),
+                ("grad temb", h.temb_grad(), gt64, gt32, 1e-5)]
+        rows += [(f"grad {k}", h.grad(k), gw64[k], gw32[k], 1e-5) for k in sd]
+        bad = []
+        for name, got, w64, w32, floor in rows:
+            err, yard = rel_l2(got, w64), rel_l2(w32, w64)
+            print(f"resblock ratio {ratio} winograd {winograd} {name}: kernel {err:.3e}, fp32 yardstick {yard:.3e}, "
+                  f"quotient {err / max(yard, 1e-300):.2f}")
+            if err > 4.0 * yard + floor:
+                bad.append(name)
+        assert not bad, bad
+    finally:
+        ops.set_winograd(None)
+        ops.set_wgrad_winograd(None)
+
+
 @pytest.mark.parametrize("c,hw", [(256, 16), (256, 8)])
 def test_wide_attention_against_the_oracle(c, hw):
     from psld_amd import score_fn as S
