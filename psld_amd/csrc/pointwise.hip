@@ -521,8 +521,10 @@ __global__ void silu_bwd_kernel(const float* __restrict__ x, const float* __rest
 
 // out[b][c] = alpha * sum_p x[(b*hw+p)*ld + c].
 // Vector path (c % 4 == 0, 16-B aligned): block = (channel quads) x (pixel lanes) like the GroupNorm
-// kernels, grid (chunks, batch); per-thread fp32 partials over <= 64 rows, fp64 across lanes; chunk
-// partials are combined by colsum_final_kernel (deterministic, no atomics).
+// kernels, grid (chunks, batch); per-thread fp32 partials over hw / (chunks * lanes) rows, fp64 across lanes; chunk
+// partials are combined by colsum_final_kernel (deterministic, no atomics).  chunks <= 16, so a thread's fp32 run is
+// 128 rows on a 128 x 128 map at c = 128 (8 lanes): measured rel-L2 2.2e-7 of the fp64 sums on unit-normal data, 1.5e-7
+// over 64 rows at c = 1024 (tests/test_reduce_geometry_gpu.py; the gate is 1e-6).
 __global__ void colsum_partial_kernel(const float* __restrict__ x, int ld, int hw, int c, int cq, int pl,
                                       int chunk_px, int chunks, double* __restrict__ part) {
     extern __shared__ double red[];  // [pl][cq*4]

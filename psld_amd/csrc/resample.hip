@@ -61,7 +61,8 @@ __global__ void upfirdn_nhwc_kernel(const float* __restrict__ x, float* __restri
 
 // Fast NHWC forms of the two resamplers the network uses with the 4x4 FIR (up_or_down_sampling.py:195-257): x2 up
 // (2x2 contributing taps per output) and x2 down (all 16 taps); compile-time tap structure, one block row per output
-// row so that no thread divides by a run-time extent.  grid = (ceil(out_w*cq / 256), batch*out_h).
+// row so that no thread divides by a run-time extent.  grid = (ceil(out_w*cq / 256), batch*out_h).  Only <1, 2> is
+// launched: x2 up runs on the 2 x 2-outputs-per-thread kernel below.
 template <int UP, int DOWN>
 __global__ void upfirdn4_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, const Fir f, int c, int in_h,
                                      int in_w, int out_h, int out_w, int accumulate) {
@@ -206,9 +207,12 @@ extern "C" int psld_upfirdn2d_f32(const float* x, float* y, int batch, int c, in
     PSLD_CHECK_ARG(x && y && kernel_host, "psld_upfirdn2d_f32: null pointer");
     PSLD_CHECK_ARG(kh >= 1 && kw >= 1 && kh * kw <= MAX_TAPS, "psld_upfirdn2d_f32: kernel %dx%d too large", kh, kw);
     PSLD_CHECK_ARG(up_x >= 1 && up_y >= 1 && down_x >= 1 && down_y >= 1, "psld_upfirdn2d_f32: bad factors");
-    const int out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;  // op/upfirdn2d_kernel.cu:237-240
-    const int out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
-    PSLD_CHECK_ARG(out_h > 0 && out_w > 0, "psld_upfirdn2d_f32: empty output");
+    const int span_h = in_h * up_y + pad_y0 + pad_y1 - kh, span_w = in_w * up_x + pad_x0 + pad_x1 - kw;
+    // a padded extent shorter than the kernel has no output: C division rounds a negative span towards zero, which
+    // would make one row / column out of -1 / 2 where the caller's floor division sizes an empty buffer
+    PSLD_CHECK_ARG(span_h >= 0 && span_w >= 0, "psld_upfirdn2d_f32: empty output");
+    const int out_h = span_h / down_y + 1;  // op/upfirdn2d_kernel.cu:237-240
+    const int out_w = span_w / down_x + 1;
     Fir f;
     f.kh = kh; f.kw = kw; f.up_x = up_x; f.up_y = up_y; f.down_x = down_x; f.down_y = down_y;
     f.pad_x0 = pad_x0; f.pad_y0 = pad_y0;
@@ -235,14 +239,10 @@ extern "C" int psld_upfirdn2d_f32(const float* x, float* y, int batch, int c, in
             PSLD_CHECK_LAUNCH("psld_upfirdn2d_f32");
             return PSLD_OK;
         }
-        if (k4 && ((up_x == 2 && down_x == 1) || (up_x == 1 && down_x == 2))) {
+        if (k4 && up_x == 1 && down_x == 2) {
             const dim3 grid((unsigned)cdiv((long long)out_w * (c / 4), 256), (unsigned)(batch * out_h));
-            if (up_x == 2)
-                hipLaunchKernelGGL((upfirdn4_nhwc_kernel<2, 1>), grid, dim3(256), 0, stream, x, y, f, c, in_h, in_w, out_h,
-                                   out_w, accumulate);
-            else
-                hipLaunchKernelGGL((upfirdn4_nhwc_kernel<1, 2>), grid, dim3(256), 0, stream, x, y, f, c, in_h, in_w, out_h,
-                                   out_w, accumulate);
+            hipLaunchKernelGGL((upfirdn4_nhwc_kernel<1, 2>), grid, dim3(256), 0, stream, x, y, f, c, in_h, in_w, out_h,
+                               out_w, accumulate);
             PSLD_CHECK_LAUNCH("psld_upfirdn2d_f32");
             return PSLD_OK;
         }

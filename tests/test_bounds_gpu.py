@@ -951,6 +951,38 @@ for _up, _down, _pad in [(2, 1, (2, 1)), (1, 2, (1, 1)), (1, 1, (2, 2)), (3, 2, 
                 _upfirdn_case(_up, _down, _pad, _l, _bwd)
 
 
+# A 4 x 3 kernel only reaches the generic NHWC form.  With 4 x 4 taps x2 up takes the kernel that writes 2 x 2 outputs per
+# thread from a 3 x 3 / 2 x 2 neighbourhood (four pad-parity instantiations, `ok ? load : 0` at the borders) and x2 down
+# the one-output kernel with compile-time taps; the gradient of either runs on the other.  Pads are (x0, x1, y0, y1).
+FIR_K4 = np.array([[1, 2, -1, .75], [.5, 3, .25, -1.25], [-2, 1.5, 4, .6], [.1, .2, .3, -.4]], dtype=np.float32)
+
+
+def _upfirdn4_case(up, down, pads, shape, bwd, accumulate):
+    def build(ops):
+        b, c, h, w_ = shape
+        oh, ow = ops.upfirdn2d_out_size(h, w_, 4, 4, up, down, pads)
+        assert oh > 0 and ow > 0
+        x = R(b, oh, ow, c, seed=50) if bwd else R(b, h, w_, c, seed=50)
+        out = (R(b, h, w_, c, seed=51) if bwd else R(b, oh, ow, c, seed=51)) if accumulate else None
+        if bwd:
+            return spec(lambda x, out: ops.upfirdn2d_bwd_raw(x, FIR_K4, up, down, pads, (h, w_), 1, out=out, accumulate=accumulate),
+                        dict(x=x, out=out), ["out"] if accumulate else [])
+        return spec(lambda x, out: ops.upfirdn2d_raw(x, FIR_K4, up, down, pads, 1, out=out, accumulate=accumulate),
+                    dict(x=x, out=out), ["out"] if accumulate else [])
+    return build
+
+
+for _up, _down, _pads, _shape, _acc in (
+        [(2, 1, _p, (2, 8, 5, 7), False) for _p in [(2, 1, 2, 1), (1, 2, 1, 2), (2, 1, 1, 2), (1, 2, 2, 1),      # the four parities
+                                                    (2, 2, 2, 2), (-1, 3, 2, -1)]] +                             # odd output; crop
+        [(1, 2, _p, (2, 8, 9, 7), False) for _p in [(1, 1, 1, 1), (2, 1, 1, 2)]] +
+        [(2, 1, (2, 1, 2, 1), (2, 8, 5, 7), True), (2, 1, (1, 2, 1, 2), (1, 132, 3, 3), False)]):
+    for _bwd in (False, True):
+        CASES["upfirdn2d%s-4x4-up%d-down%d-pad%d_%d_%d_%d-%dx%dx%dx%d%s" % (("_bwd" if _bwd else "", _up, _down) + _pads + _shape +
+                                                                         ("-accumulate" if _acc else "",))] = \
+            _upfirdn4_case(_up, _down, _pads, _shape, _bwd, _acc)
+
+
 @case("fused_bias_act")
 def _(ops):
     return spec(lambda x, b: ops.fused_bias_act(x, b), dict(x=R(2, 5, 4, 4, seed=52), b=R(5, seed=53)))
