@@ -46,7 +46,7 @@ const char* psld_last_error(void);
  *                    points is the caller's choice (psld_amd: forwards that record no backward pass).
  * Process-wide; the initial value comes from the environment variable PSLD_MATH ("f32" | "bf16x6" | "bf16x3" |
  * "bf16x3_train": mode PSLD_MATH_BF16X3 with record math PSLD_MATH_BF16X3, below | "f16": mode PSLD_MATH_BF16X3 with eval math
- * PSLD_EVAL_MATH_F16, below). */
+ * PSLD_EVAL_MATH_F16, below | "f16_train": "bf16x3_train" with record f16 on, below). */
 #define PSLD_MATH_F32 0
 #define PSLD_MATH_BF16X6 1
 #define PSLD_MATH_BF16X3 2
@@ -72,6 +72,19 @@ int psld_get_record_math(void);
 #define PSLD_EVAL_MATH_F16 1
 int psld_set_eval_math(int kind);
 int psld_get_eval_math(void);
+/* Record f16: a fourth, independent setting (0 = off, the default; 1 = on; any other value is refused).  Meaningful under a limb
+ * math mode with record math PSLD_MATH_BF16X3: a pass that records a backward pass then takes the one-product fp16 entry points
+ * where one exists - Winograd 3x3 forward (psld_conv3x3_wino_f16_f32) and data gradient (psld_conv3x3_wino_f16s_f32 on fragments of
+ * psld_pack_conv3x3_wino_dgrad_f16), eight-wave pointwise forward (psld_gemm_split_f16_f32) and data gradient
+ * (psld_gemm_split_f16s_f32) - and the two-limb ones elsewhere; every weight gradient stays on limbs (the Winograd one is bound by
+ * its producers, not by its MFMAs).  With record math PSLD_MATH_BF16X6 the flag has no effect.  Gradients of a mean-reduced loss
+ * are ~2/N, below fp16's normal range: the *_f16s entries multiply their activation-side operand by 2^shift in fp32 before the one
+ * rounding (clamped to +-65504) and fold 2^-shift into alpha - exact, so the rounding stays the only error; the caller chooses the
+ * shift (psld_amd: ceil(log2 N) of the loss's divisor, at most 24).  11 significant bits, the arithmetic the reference trains in on
+ * its own GPUs (TF32 convolutions): reference-GPU-equivalent, NOT fp32-equivalent, outside the 1e-4 parity contract, strictly
+ * opt-in.  The library only stores the value.  Initial value: 1 when PSLD_MATH is "f16_train", else 0. */
+int psld_set_record_f16(int on);
+int psld_get_record_f16(void);
 
 /* ---- fused epilogue of every MFMA tile kernel ------------------------------------------
  * value = ((alpha * acc + bias[n] + rowbias[m / rows_per_img][n] + residual[m][n]) * out_scale)
@@ -251,6 +264,15 @@ int psld_conv3x3_wino_gn_f16_f32(const float* x1, int c1, const float* scale1, c
                                  int c2, const float* scale2, const float* shift2, int act, int batch, int h, int w,
                                  const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi,
                                  void* workspace, long long ws_bytes, hipStream_t stream);
+/* Record f16 (above): the data-gradient orientation of psld_pack_conv3x3_wino_f16 - the transposed, rotated weights as one fp16
+ * plane, psld_conv3x3_wino_frag_bytes_f16(cin, cout) bytes (psld_pack_wino_batch_f16 takes rows of either orientation) - and
+ * psld_conv3x3_wino_f16_f32 with an operand shift, 0 <= shift <= 24: V = B^T (x1 | x2) B times 2^shift, in fp32, is what is
+ * rounded to fp16, and the epilogue's alpha is multiplied by 2^-shift (plain, channel-tail and split-chunk forms; in the last the
+ * reduction pass applies it).  shift = 0 returns psld_conv3x3_wino_f16_f32's result bit for bit. */
+int psld_pack_conv3x3_wino_dgrad_f16(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream);
+int psld_conv3x3_wino_f16s_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
+                               const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi, int shift,
+                               void* workspace, long long ws_bytes, hipStream_t stream);
 
 /* "Limb planes": an NHWC activation [rows][c] (c a multiple of 32) stored already decomposed, as bf16
  * [rows][c/32 chunks][3 limbs hi|mid|lo][32 channels] (6 bytes per element; hi + mid + lo == x bit for bit).  The
@@ -299,6 +321,11 @@ int psld_pack_gemm_frag_f16(const float* b, void* bfrag, int n, int k, long long
 int psld_pack_frag_batch_f16(const long long* table_dev, int entries, long long total_items, hipStream_t stream);
 int psld_gemm_split_f16_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
                             float* y, int ldy, const psld_epilogue_t* epi, hipStream_t stream);
+/* Record f16: the same launch with an operand shift, 0 <= shift <= 24 (the pointwise data gradient, on fragments packed with n and
+ * k swapped through psld_pack_gemm_frag_f16's strides): the rows times 2^shift, in fp32, are what is rounded to fp16, alpha is
+ * multiplied by 2^-shift.  Shapes: psld_gemm_split_f16_supported.  shift = 0 returns psld_gemm_split_f16_f32's result bit for bit. */
+int psld_gemm_split_f16s_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
+                             float* y, int ldy, const psld_epilogue_t* epi, int shift, hipStream_t stream);
 
 /* Fused single-head spatial self-attention, forward: o[b][i][:] = sum_j softmax_j(scale * q[b][i] . k[b][j]) v[b][j][:] in
  * one kernel, the hw x hw score matrix never written (unless p != NULL: the probabilities [batch][hw][hw] fp32, what the

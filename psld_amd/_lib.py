@@ -77,6 +77,8 @@ SIGNATURES = {
     "psld_get_record_math": (I, []),
     "psld_set_eval_math": (I, [I]),
     "psld_get_eval_math": (I, []),
+    "psld_set_record_f16": (I, [I]),
+    "psld_get_record_f16": (I, []),
     "psld_set_gn_bwd_kernel": (I, [I]),
     "psld_get_gn_bwd_kernel": (I, []),
     "psld_gemm_f32": (I, [I, I, I, I, I, P, I, LL, P, I, LL, P, I, LL, I, EP, P]),
@@ -114,6 +116,8 @@ SIGNATURES = {
     "psld_pack_wino_batch_f16": (I, [P, I, LL, P]),
     "psld_conv3x3_wino_f16_f32": (I, [P, I, P, I, I, I, I, P, I, P, I, EP, P, LL, P]),
     "psld_conv3x3_wino_gn_f16_f32": (I, [P, I, P, P, P, I, P, P, I, I, I, I, P, I, P, I, EP, P, LL, P]),
+    "psld_pack_conv3x3_wino_dgrad_f16": (I, [P, P, I, I, P]),
+    "psld_conv3x3_wino_f16s_f32": (I, [P, I, P, I, I, I, I, P, I, P, I, EP, I, P, LL, P]),
     "psld_gn_apply_limb_nhwc": (I, [P, P, P, P, I, I, I, I, F, C.c_ulonglong, P, P]),
     "psld_limb_bytes": (LL, [LL, I]),
     "psld_f32_to_limb": (I, [P, LL, I, P, P]),
@@ -133,6 +137,7 @@ SIGNATURES = {
     "psld_pack_gemm_frag_f16": (I, [P, P, I, I, LL, LL, P]),
     "psld_pack_frag_batch_f16": (I, [P, I, LL, P]),
     "psld_gemm_split_f16_f32": (I, [P, I, P, I, I, P, I, P, I, EP, P]),
+    "psld_gemm_split_f16s_f32": (I, [P, I, P, I, I, P, I, P, I, EP, I, P]),
     "psld_conv3x3_wgrad_split_supported": (I, [I, I, I, I, I]),
     "psld_conv3x3_wgrad_split_cout_tile": (I, [I]),
     "psld_conv3x3_wgrad_split_f32": (I, [P, I, I, P, I, P, I, I, I, I, P, I, I, I, P]),

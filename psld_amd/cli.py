@@ -506,10 +506,16 @@ def build_parser() -> argparse.ArgumentParser:
                                 "wide pointwise forwards on ONE fp16 product (ops.set_eval_math): ~1e-3 rel-L2 from fp32, the "
                                 "precision of the reference's default TF32 convolutions, outside the 1e-4 parity contract")
         if name in ("train", "train_clf"):
-            p.add_argument("--train-math", default=None, choices=["bf16x6", "bf16x3"],
+            p.add_argument("--train-math", default=None, choices=["bf16x6", "bf16x3", "f16"],
                            help="arithmetic of the passes that record a backward pass (ops.set_record_math; default: the "
                                 "process's setting); bf16x3 = two-limb forward, data-gradient and Winograd weight-gradient "
-                                "launches, gradients ~1e-5 rel-L2 from fp32")
+                                "launches, gradients ~1e-5 rel-L2 from fp32; f16 = bf16x3 with the Winograd and wide pointwise "
+                                "forwards and data gradients on ONE fp16 product (ops.set_record_f16): 11 significant bits, the "
+                                "precision of the reference's default TF32 convolutions, outside the 1e-4 parity contract")
+        if name == "train":
+            p.add_argument("--grad-shift", type=int, default=None, metavar="N",
+                           help="--train-math f16: multiply the gradients entering the fp16 data-gradient launches by 2^N "
+                                "(0..24; ops.set_grad_shift).  Default: automatic, ceil(log2) of the loss's divisor")
     return ap
 
 
@@ -523,7 +529,11 @@ def main(argv=None):
         ops.set_eval_math("f16" if args.math == "f16" else "limb")
     if getattr(args, "train_math", None):
         from psld_amd import ops
-        ops.set_record_math(args.train_math)
+        ops.set_record_math("bf16x3" if args.train_math == "f16" else args.train_math)
+        ops.set_record_f16(args.train_math == "f16")
+    if getattr(args, "grad_shift", None) is not None:
+        from psld_amd import ops
+        ops.set_grad_shift(args.grad_shift)
     {"train": train, "sample": sample, "inpaint": inpaint, "train_clf": train_clf,
      "cc_sample": cc_sample}[args.cmd](args, overrides)
 

@@ -44,16 +44,19 @@ constexpr int TAP_U4 = 4 * 3 * 64;   // uint4 per (wave column, tap, 32-channel 
 int g_math_mode = -1;
 int g_record_math = -1;     // arithmetic of passes that record a backward pass (psld_set_record_math)
 int g_eval_math = -1;       // arithmetic of forwards that record none (psld_set_eval_math): 0 follows the math mode, 1 = f16
+int g_record_f16 = -1;      // recording passes under record math bf16x3 take the fp16 launches where one exists (psld_set_record_f16)
 // PSLD_MATH is read once, by whichever getter runs first: "bf16x3_train" = math mode bf16x3 + record math bf16x3, "f16" = math
-// mode bf16x3 + eval math f16.  A value set through the C ABI before that stays.
+// mode bf16x3 + eval math f16, "f16_train" = "bf16x3_train" + record f16.  A value set through the C ABI before that stays.
 inline void math_from_env() {
     const char* e = getenv("PSLD_MATH");
-    const bool train = e && !strcmp(e, "bf16x3_train");
+    const bool f16_train = e && !strcmp(e, "f16_train");
+    const bool train = (e && !strcmp(e, "bf16x3_train")) || f16_train;
     const bool f16 = e && !strcmp(e, "f16");
     if (g_math_mode < 0)
         g_math_mode = (e && !strcmp(e, "f32")) ? PSLD_MATH_F32 : ((e && !strcmp(e, "bf16x3")) || train || f16) ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
     if (g_record_math < 0) g_record_math = train ? PSLD_MATH_BF16X3 : PSLD_MATH_BF16X6;
     if (g_eval_math < 0) g_eval_math = f16 ? PSLD_EVAL_MATH_F16 : PSLD_EVAL_MATH_LIMB;
+    if (g_record_f16 < 0) g_record_f16 = f16_train ? 1 : 0;
 }
 inline int math_mode() {
     if (g_math_mode < 0) math_from_env();
@@ -243,6 +246,7 @@ struct DConvArgs {
     PsldEpilogue e;
     const float* zero;
     int v4;                 // rows of C / residual / bias / row bias are 16-byte aligned: dwordx4 epilogue (set by plan_split)
+    float opscale;          // pw8_kernel<., NL = 1, SH = true>: the rows are multiplied by this power of two before they are rounded to fp16
 };
 
 // Fused epilogue of the limb kernels.  They issue the MFMAs with the WEIGHT fragment as the first operand, i.e. they
@@ -1581,7 +1585,9 @@ constexpr int PW8_LIMB = PW8_ROWS * ROWB;           // bytes per limb of one ima
 // six (hi*hi + (hi*lo + lo*hi), smallest first), images of two limb planes, fragments of psld_pack_gemm_frag_x3.
 // NL = 1 (eval math f16): rows and weights rounded once to fp16 (cvt_pk_f16), one product per accumulator, images of one
 // plane, fragments of psld_pack_gemm_frag_f16.
-template <int ABL = 0, int NL = 3>      // timing-only ablations (PSLD_PW8_ABL): 1 no staging after the prologue, 2 weights loaded once, 4 no epilogue
+// SH (NL = 1 only; record f16: the data gradient on fragments packed with n and k swapped): the rows (dy) are multiplied by
+// a.opscale = 2^shift in fp32 - exact - before the one rounding; the host folds 2^-shift into the epilogue's alpha.
+template <int ABL = 0, int NL = 3, bool SH = false>      // timing-only ablations (PSLD_PW8_ABL): 1 no staging after the prologue, 2 weights loaded once, 4 no epilogue
 __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int IMG = NL * PW8_LIMB;          // bytes of one image
@@ -1636,6 +1642,9 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
             } else if constexpr (NL == 2) {
                 split2(hv[i][0], hv[i][1], h0, m0_);
                 split2(hv[i][2], hv[i][3], h1, m1);
+            } else if constexpr (SH) {
+                h0 = cvt_pk_f16(hv[i][0] * a.opscale, hv[i][1] * a.opscale);
+                h1 = cvt_pk_f16(hv[i][2] * a.opscale, hv[i][3] * a.opscale);
             } else {
                 h0 = cvt_pk_f16(hv[i][0], hv[i][1]);
                 h1 = cvt_pk_f16(hv[i][2], hv[i][3]);
@@ -1757,12 +1766,12 @@ __global__ void __launch_bounds__(512) pw8_kernel(const DConvArgs a) {
     }
 }
 
-template <int ABL = 0, int NL = 3>
+template <int ABL = 0, int NL = 3, bool SH = false>
 int launch_pw8(const DConvArgs& a, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)2 * NL * PW8_LIMB;
-    if (int st = psld_lds_once<&pw8_kernel<ABL, NL>>(LDS, name)) return st;
+    if (int st = psld_lds_once<&pw8_kernel<ABL, NL, SH>>(LDS, name)) return st;
     const int total = cdiv(a.M, 128) * (a.N / 256);
-    hipLaunchKernelGGL((pw8_kernel<ABL, NL>), dim3((unsigned)(total < 256 ? total : 256)), dim3(512), LDS, stream, a);
+    hipLaunchKernelGGL((pw8_kernel<ABL, NL, SH>), dim3((unsigned)(total < 256 ? total : 256)), dim3(512), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
 }
@@ -2055,6 +2064,17 @@ extern "C" int psld_get_eval_math(void) {
     return g_eval_math;
 }
 
+extern "C" int psld_set_record_f16(int on) {
+    PSLD_CHECK_ARG(on == 0 || on == 1, "psld_set_record_f16: %d is neither 0 nor 1", on);
+    g_record_f16 = on;
+    return PSLD_OK;
+}
+
+extern "C" int psld_get_record_f16(void) {
+    if (g_record_f16 < 0) math_from_env();
+    return g_record_f16;
+}
+
 extern "C" long long psld_conv3x3_frag_bytes(int cout, int cin) { return (long long)cout * cin * 9 * 6; }
 
 extern "C" int psld_conv3x3_split_supported(int c1, int c2, int batch, int h, int w, int cout) {
@@ -2336,6 +2356,20 @@ extern "C" int psld_gemm_split_f16_f32(const float* a1, int k1, const float* a2,
                          nullptr, 0))
         return st;
     return launch_pw8<0, 1>(p.a, stream, name);
+}
+
+// The same with an operand shift (record f16: pointwise data gradients): rows times 2^shift before the rounding, 2^-shift in alpha
+extern "C" int psld_gemm_split_f16s_f32(const float* a1, int k1, const float* a2, int k2, int m, const void* bfrag, int n,
+                                        float* y, int ldy, const psld_epilogue_t* epi, int shift, hipStream_t stream) {
+    const char* name = "psld_gemm_split_f16s_f32";
+    PSLD_CHECK_ARG(shift >= 0 && shift <= 24, "%s: shift %d outside 0..24", name, shift);
+    DConvPlan p;
+    if (int st = pw_plan(p, name, false, psld_gemm_split_f16_supported(k1, k2, m, n), a1, k1, a2, k2, m, bfrag, n, y, ldy, epi,
+                         nullptr, 0))
+        return st;
+    p.a.opscale = ldexpf(1.f, shift);       // powers of two on both sides: the rounding to fp16 is the only error
+    p.a.e.alpha *= ldexpf(1.f, -shift);     // no workspace, no K ranges: a.e is the caller's epilogue
+    return launch_pw8<0, 1, true>(p.a, stream, name);
 }
 
 // ---- pointwise, channel widths in steps of 32 ("tail": the shapes psld_gemm_split_supported refuses for n % 128 or k % 64) ----

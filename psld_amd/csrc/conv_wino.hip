@@ -71,6 +71,7 @@ struct WinoArgs {
     int lg_rpi;                 // log2 of the regions per image (H * W / 128), -1: not a power of two (non-square maps)
     int mul_seg, mul_w2;        // wino_div16 multipliers of seg_px = (rps + 2) * (cw + 2) and of W2 = cw + 2
     int rb_img;                 // the row bias is one row per image (rows_per_img == H * W): its row is the image index
+    float opscale;              // wino_conv8s_kernel<..., NL = 1, SH = true>: V is multiplied by this power of two before it is rounded to fp16
 };
 
 // x / d for 0 <= x < 256 as (x * wino_mul16(d)) >> 16: exact for every divisor the halo decomposition meets
@@ -231,7 +232,10 @@ __global__ void wino_pack_batch_kernel(const long long* __restrict__ tab, int nt
 // and a product is one v_mfma_f32_16x16x32_f16 - exact in fp32 (11 + 11 significant bits), so the operand rounding is the mode's
 // only error.  V image [pos][1][tile][32 ch] (32 KB), fragments [...][16 pos][1][64 lanes], per chunk and wave 16 positions x
 // (2 ds_read_b128 + 1 fragment load + 2 MFMAs).  fp32 transforms, accumulation, output transform and epilogue are the NL = 3 kernel's.
-template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3>
+// SH (NL = 1 only; record f16: the data gradient is this kernel on dgrad = 1 fragments): V is multiplied by a.opscale = 2^shift in
+// fp32 - exact - before the one rounding, so that gradients of a mean-reduced loss (~2/N, fp16 subnormals or zero) keep 11
+// significant bits; the host folds 2^-shift into the epilogue's alpha.  One v_mul_f32 per V value, nothing else changes.
+template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3, bool SH = false>
 __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NI = 4;                     // raw image: 256 halo pixels
@@ -366,6 +370,9 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
             } else if constexpr (NL == 2) {
                 split2(v[0], v[1], h0, m0_);
                 split2(v[2], v[3], h1, m1);
+            } else if constexpr (SH) {
+                h0 = cvt_pk_f16(v[0] * a.opscale, v[1] * a.opscale);
+                h1 = cvt_pk_f16(v[2] * a.opscale, v[3] * a.opscale);
             } else {
                 h0 = cvt_pk_f16(v[0], v[1]);
                 h1 = cvt_pk_f16(v[2], v[3]);
@@ -686,16 +693,16 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
 #include "conv_wino_abl.inc"
 #endif
 
-template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3>
+template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3, bool SH = false>
 int launch_wino8s(const WinoArgs& a, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)VBYTES / 3 * NL + 2 * (size_t)4 * 64 * 128;
     static_assert(LDS <= 163840, "LDS budget");
-    if (int st = psld_lds_once<&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>>(LDS, name)) return st;
+    if (int st = psld_lds_once<&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL, SH>>(LDS, name)) return st;
     // the kernel finds its (chunk range, channel tile, pixel tile) from tiles_m and lg_ksplit, not from gridDim
     PSLD_CHECK_ARG(a.tiles_m == cdiv(a.M, 128) && (1 << a.lg_ksplit) == (a.ksplit > 1 ? a.ksplit : 1),
                    "%s: launch geometry not filled in (tiles_m %d, ksplit %d)", name, a.tiles_m, a.ksplit);
     dim3 grid((unsigned)(a.tiles_m * cdiv(a.N, 128) * (a.ksplit > 1 ? a.ksplit : 1)));
-    hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL>), grid, dim3(WINO_THREADS), LDS, stream, a);
+    hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL, SH>), grid, dim3(WINO_THREADS), LDS, stream, a);
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;
 }
@@ -791,6 +798,18 @@ extern "C" int psld_pack_conv3x3_wino_f16(const float* w_oihw, void* ufrag, int 
     return PSLD_OK;
 }
 
+// the data-gradient orientation as one fp16 plane (record f16): the transposed, rotated weights, U rounded once
+extern "C" int psld_pack_conv3x3_wino_dgrad_f16(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream) {
+    PSLD_CHECK_ARG(w_oihw && ufrag && aligned16(ufrag), "psld_pack_conv3x3_wino_dgrad_f16: null / unaligned pointer");
+    PSLD_CHECK_ARG(cin >= 128 && cout > 0 && cin % 32 == 0 && cout % 32 == 0,
+                   "psld_pack_conv3x3_wino_dgrad_f16: needs in channels %%32 (>= 128) and out channels %%32 (got %d, %d)", cin, cout);
+    const long long items = (long long)(cin / 16) * (cout / 32) * 64;
+    hipLaunchKernelGGL(wino_pack_kernel<1>, dim3(psld_grid_blocks(items, 64, 16384)), dim3(64), 0, stream, w_oihw,
+                       reinterpret_cast<u32x4*>(ufrag), cin, cout, 9LL, (long long)cin * 9, 1);
+    PSLD_CHECK_LAUNCH("psld_pack_conv3x3_wino_dgrad_f16");
+    return PSLD_OK;
+}
+
 // the data-gradient orientation on two limbs (record math PSLD_MATH_BF16X3): psld_pack_conv3x3_wino(..., dgrad = 1)'s planes 0 and 1
 extern "C" int psld_pack_conv3x3_wino_dgrad_x3(const float* w_oihw, void* ufrag, int cout, int cin, hipStream_t stream) {
     PSLD_CHECK_ARG(w_oihw && ufrag && aligned16(ufrag), "psld_pack_conv3x3_wino_dgrad_x3: null / unaligned pointer");
@@ -840,7 +859,7 @@ struct WinoGn {
 };
 int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w, const void* ufrag, int cout, float* y,
               int ldy, const psld_epilogue_t* epi, const WinoGn* gn, void* workspace, long long ws_bytes, hipStream_t stream,
-              int nl = 3);
+              int nl = 3, int shift = -1);
 }  // namespace
 
 extern "C" int psld_conv3x3_wino_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
@@ -941,12 +960,26 @@ extern "C" int psld_conv3x3_wino_gn_f16_f32(const float* x1, int c1, const float
     return wino_conv(x1, c1, x2, c2, batch, h, w, ufrag, cout, y, ldy, epi, &gn, workspace, ws_bytes, stream, 1);
 }
 
+// ---- the same with an operand shift (record f16: data gradients): x1 | x2 times 2^shift before the rounding, 2^-shift in alpha ----
+extern "C" int psld_conv3x3_wino_f16s_f32(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w,
+                                          const void* ufrag, int cout, float* y, int ldy, const psld_epilogue_t* epi, int shift,
+                                          void* workspace, long long ws_bytes, hipStream_t stream) {
+    PSLD_CHECK_ARG(shift >= 0 && shift <= 24, "psld_conv3x3_wino_f16s_f32: shift %d outside 0..24", shift);
+    return wino_conv(x1, c1, x2, c2, batch, h, w, ufrag, cout, y, ldy, epi, nullptr, workspace, ws_bytes, stream, 1, shift);
+}
+
 namespace {
 // LA = 3: a position is two MFMAs here (six on two limbs), so the fragments are requested one position further ahead
 int wino_launch_f16(const WinoArgs& a, bool gn, hipStream_t stream) {
     if (gn) return launch_wino8s<0, true, false, 3, false, 1>(a, stream, "psld_conv3x3_wino_gn_f16_f32");
     if (a.N % 128) return launch_wino8s<0, false, false, 3, true, 1>(a, stream, "psld_conv3x3_wino_f16_f32");
     return launch_wino8s<0, false, false, 3, false, 1>(a, stream, "psld_conv3x3_wino_f16_f32");
+}
+
+// operand shift (no GroupNorm-fused form: a recording pass has none)
+int wino_launch_f16s(const WinoArgs& a, hipStream_t stream) {
+    if (a.N % 128) return launch_wino8s<0, false, false, 3, true, 1, true>(a, stream, "psld_conv3x3_wino_f16s_f32");
+    return launch_wino8s<0, false, false, 3, false, 1, true>(a, stream, "psld_conv3x3_wino_f16s_f32");
 }
 
 int wino_launch_x3(const WinoArgs& a, bool gn, hipStream_t stream) {
@@ -957,7 +990,7 @@ int wino_launch_x3(const WinoArgs& a, bool gn, hipStream_t stream) {
 
 int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h, int w, const void* ufrag, int cout, float* y,
               int ldy, const psld_epilogue_t* epi, const WinoGn* gn, void* workspace, long long ws_bytes, hipStream_t stream,
-              int nl) {
+              int nl, int shift) {
     PSLD_CHECK_ARG(x1 && ufrag && y && (c2 == 0 || x2), "psld_conv3x3_wino_f32: null pointer");
     PSLD_CHECK_ARG(psld_conv3x3_wino_supported(c1, c2, batch, h, w, cout),
                    "psld_conv3x3_wino_f32: unsupported shape c1=%d c2=%d %dx%d cout=%d", c1, c2, h, w, cout);
@@ -972,6 +1005,10 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
     int halo_px = 0;
     wino_geometry(h, w, &a.nseg, &a.rps, &halo_px);
     a.e = make_epilogue(epi);
+    if (shift >= 0) {       // psld_conv3x3_wino_f16s_f32: both factors are powers of two - the rounding to fp16 is the only error
+        a.opscale = ldexpf(1.f, shift);
+        a.e.alpha *= ldexpf(1.f, -shift);       // the split-chunk form applies e in its reduction pass: covered as well
+    }
     const PsldEpilogue& e = a.e;
     PSLD_CHECK_ARG(!e.gn_part || (e.gn_hw == h * w && e.gn_hw % 64 == 0 && !e.accumulate && cout % 128 == 0),
                    "psld_conv3x3_wino_f32: gn_part needs gn_hw = h*w, a multiple of 64, no accumulation and cout %% 128 == 0");
@@ -1019,13 +1056,15 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
         s.C = reinterpret_cast<float*>(workspace);
         s.ldc = cout;
         s.e = make_epilogue(nullptr);
-        const int rc = nl == 1 ? wino_launch_f16(s, gn != nullptr, stream)
+        const int rc = shift >= 0 ? wino_launch_f16s(s, stream)
+                       : nl == 1 ? wino_launch_f16(s, gn != nullptr, stream)
                        : nl == 2 ? wino_launch_x3(s, gn != nullptr, stream)
                        : gn    ? launch_wino8s<0, true>(s, stream, "psld_conv3x3_wino_gn_f32")
                                : (cout % 128 ? launch_wino8s<0, false, false, 2, true>(s, stream, name) : launch_wino8s<0>(s, stream, name));
         if (rc != PSLD_OK) return rc;
         return psld_detail_conv_reduce_epilogue(s.C, ks, a.M, cout, y, ldy, e, stream);
     }
+    if (shift >= 0) return wino_launch_f16s(a, stream);
     if (nl == 1) return wino_launch_f16(a, gn != nullptr, stream);
     if (nl == 2) return wino_launch_x3(a, gn != nullptr, stream);
     if (gn) return launch_wino8s<0, true>(a, stream, "psld_conv3x3_wino_gn_f32");

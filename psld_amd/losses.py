@@ -21,11 +21,15 @@ class _SqErr(torch.autograd.Function):
     def forward(ctx, pred, target, reduce_mean):
         loss, grad = ops.sqerr_loss(target, pred.contiguous(), reduce_mean, want_grad=True)
         ctx.save_for_backward(grad)
+        ctx.divisor = pred.numel() if reduce_mean else 1
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
+        # the gradient handed on carries 1 / divisor: the network's backward pass, which runs next, places its fp16 data
+        # gradients by it (record f16: ops.take_grad_shift; a host integer, nothing else reads it)
+        ops.set_loss_divisor(ctx.divisor)
         return grad * g, None, None   # g is the 0-d upstream gradient (1.0 for loss.backward())
 
 
@@ -83,11 +87,13 @@ class _VpScoreLoss(torch.autograd.Function):
     def forward(ctx, pred, target, t, beta0, beta1, mode, reduce_mean):
         loss, grad = ops.vp_score_loss(target, pred.contiguous(), t, beta0, beta1, mode, reduce_mean, want_grad=True)
         ctx.save_for_backward(grad)
+        ctx.divisor = pred.numel() if reduce_mean else 1
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
+        ops.set_loss_divisor(ctx.divisor)       # as _SqErr
         return grad * g.to(grad.dtype), None, None, None, None, None, None
 
 
@@ -132,11 +138,13 @@ class _SoftmaxXent(torch.autograd.Function):
         loss, grad, correct = ops.softmax_xent(logits.contiguous(), labels.contiguous(), scale, scale)
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(correct)
+        ctx.divisor = logits.shape[0] if reduce_mean else 1
         return loss, correct
 
     @staticmethod
     def backward(ctx, g, _g_correct):
         (grad,) = ctx.saved_tensors
+        ops.set_loss_divisor(ctx.divisor)       # as _SqErr: the batch for the mean, 1 for the sum
         return grad * g, None, None
 
 

@@ -174,6 +174,71 @@ def eval_math() -> str:
     return EVAL_MATHS[lib().psld_get_eval_math()]
 
 
+def set_record_f16(on: bool):
+    """Record f16 (opt-in, process-wide; a fourth setting next to math mode, record math and eval math): under a limb math mode
+    with record math 'bf16x3', a pass that records a backward pass runs the one-product fp16 launches where one exists - Winograd
+    3x3 forward and data gradient, eight-wave pointwise forward and data gradient - and the two-limb ones elsewhere (every weight
+    gradient, attention, launches below 128 tiles).  With record math 'bf16x6' it has no effect.  11 significant bits, what the
+    reference trains in on its own GPUs (TF32): NOT fp32-equivalent, outside the 1e-4 parity contract."""
+    if on not in (False, True, 0, 1):
+        raise ValueError(f"record f16 must be a bool, got {on!r}")
+    check(lib().psld_set_record_f16(int(on)), "psld_set_record_f16")
+
+
+def record_f16() -> bool:
+    return bool(lib().psld_get_record_f16())
+
+
+# ---- gradient shift of record f16 ---------------------------------------------------------------------------------------------
+# Gradients of a mean-reduced loss enter the network at ~2/N - fp16 subnormals or zero at training sizes.  The fp16 data-gradient
+# launches multiply dy by 2^s before their one rounding and fold 2^-s into alpha (exact: the rounding stays the only error).  s is a
+# HOST integer: the losses publish the divisor N they apply (set_loss_divisor), the next recorded backward takes
+# s = min(24, ceil(log2 N)) and clears it; a backward nobody published a divisor for (a user's own loss, the guidance pass) takes 0.
+GRAD_SHIFT_MAX = 24
+_GRAD_SHIFT = None          # set_grad_shift: None = automatic
+_LOSS_DIVISOR = None        # set_loss_divisor: the divisor of the loss whose backward comes next
+
+
+def set_grad_shift(shift: Optional[int]):
+    """Operand shift of the fp16 data-gradient launches: None (default) = automatic, from the published loss divisor; an int is
+    clamped to 0..24 and used for every recorded backward."""
+    global _GRAD_SHIFT
+    _GRAD_SHIFT = None if shift is None else max(0, min(GRAD_SHIFT_MAX, int(shift)))
+
+
+def grad_shift_setting() -> Optional[int]:
+    return _GRAD_SHIFT
+
+
+def grad_shift_for(divisor) -> int:
+    """The shift rule: min(24, ceil(log2 N)) for a divisor N >= 1 (integer arithmetic: exact at powers of two), else 0."""
+    n = int(divisor) if divisor else 0
+    return min(GRAD_SHIFT_MAX, (n - 1).bit_length()) if n > 1 else 0
+
+
+def set_loss_divisor(n):
+    """Host-side note of a loss: the gradient it hands to the network carries 1/n (element count of a mean, batch of the
+    cross-entropy, 1 for a sum).  Consumed by the next recorded backward (take_grad_shift)."""
+    global _LOSS_DIVISOR
+    _LOSS_DIVISOR = None if n is None else int(n)
+
+
+def loss_divisor() -> Optional[int]:
+    return _LOSS_DIVISOR
+
+
+def current_grad_shift() -> int:
+    """The shift the next recorded backward uses (no device value is read)."""
+    return _GRAD_SHIFT if _GRAD_SHIFT is not None else grad_shift_for(_LOSS_DIVISOR)
+
+
+def take_grad_shift() -> int:
+    """current_grad_shift(), consuming the published divisor: a later backward with no loss of ours in front of it takes 0."""
+    s = current_grad_shift()
+    set_loss_divisor(None)
+    return s
+
+
 @functools.lru_cache(maxsize=None)
 def conv3x3_split_supported(c1: int, c2: int, b: int, h: int, w: int, cout: int) -> bool:
     return bool(lib().psld_conv3x3_split_supported(c1, c2, b, h, w, cout))
@@ -279,9 +344,10 @@ def pack_wino_batch_x3(table: Tensor, entries: int, total_items: int):
 
 
 def _wino(name: str, ws_name: Optional[str], x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: Tensor, epi, ldy,
-          allow_split: bool, gn=None):
+          allow_split: bool, gn=None, shift: Optional[int] = None):
     """One Winograd forward launch: entry point ``name`` - or, when ``allow_split`` finds the grid small enough for a split-chunk
-    workspace, ``ws_name`` (None: ``name`` itself takes the (ws, wsb) pair).  ``gn`` = (st1, st2, act): the fused GroupNorm's."""
+    workspace, ``ws_name`` (None: ``name`` itself takes the (ws, wsb) pair).  ``gn`` = (st1, st2, act): the fused GroupNorm's.
+    ``shift``: the operand shift of the ``*_f16s`` entry (it follows the epilogue)."""
     b, h, w, c1 = x1.shape
     c2 = x2.shape[-1] if x2 is not None else 0
     wsb = conv3x3_wino_ws_bytes(c1, c2, b, h, w, cout) if allow_split else 0
@@ -293,6 +359,8 @@ def _wino(name: str, ws_name: Optional[str], x1: Tensor, x2: Optional[Tensor], u
                 1 if act else 0]
     args += [b, h, w, ufrag.data_ptr(), cout, y.data_ptr(), ldy if ldy is not None else cout,
              C.byref(epi) if epi is not None else None]
+    if shift is not None:
+        args.append(int(shift))
     if wsb or ws_name is None:
         name = ws_name or name
         args += [workspace(wsb, x1.device).data_ptr() if wsb else None, wsb]
@@ -340,6 +408,24 @@ def conv3x3_wino_gn_f16(x1: Tensor, st1: "GNStats", x2: Optional[Tensor], st2: O
                         cout: int, y: Tensor, epi: Optional[Epilogue] = None, allow_split: bool = False):
     """conv3x3_wino_gn on fp16 fragments (conv3x3_wino_frag_f16)."""
     _wino("psld_conv3x3_wino_gn_f16_f32", None, x1, x2, ufrag, cout, y, epi, y.shape[-1], allow_split, (st1, st2, act))
+
+
+# ---- record f16: the data gradients of a recording pass on one fp16 product, with an operand shift ---------------------------
+def conv3x3_wino_dgrad_frag_f16(w_oihw: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """conv3x3_wino_frag(w, True) - the data gradient's fragments - as one fp16 plane (psld_pack_conv3x3_wino_dgrad_f16)."""
+    co, ci = w_oihw.shape[0], w_oihw.shape[1]
+    if out is None:
+        out = torch.empty(conv3x3_wino_frag_bytes_f16(ci, co), dtype=torch.uint8, device=w_oihw.device)
+    check(lib().psld_pack_conv3x3_wino_dgrad_f16(w_oihw.data_ptr(), out.data_ptr(), co, ci, _stream()),
+          "psld_pack_conv3x3_wino_dgrad_f16")
+    return out
+
+
+def conv3x3_wino_f16s(x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int, y: Tensor, shift: int,
+                      epi: Optional[Epilogue] = None, ldy: Optional[int] = None, allow_split: bool = False):
+    """conv3x3_wino_f16 with an operand shift: V times 2^shift (fp32, exact) is what is rounded to fp16, alpha takes 2^-shift.
+    shift = 0 is conv3x3_wino_f16 bit for bit."""
+    _wino("psld_conv3x3_wino_f16s_f32", None, x1, x2, ufrag, cout, y, epi, ldy, allow_split, shift=shift)
 
 
 _WINO_MODE = None     # 0: never, 1: where it pays (default), 2: wherever the kernel takes the shape (tests)
@@ -573,6 +659,17 @@ def gemm_split_f16(a1: Tensor, a2: Optional[Tensor], m: int, bfrag: Tensor, n: i
     check(lib().psld_gemm_split_f16_f32(a1.data_ptr(), k1, _p(a2), k2, m, bfrag.data_ptr(), n, y.data_ptr(),
                                         ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
                                         _stream()), "psld_gemm_split_f16_f32")
+
+
+def gemm_split_f16s(a1: Tensor, a2: Optional[Tensor], m: int, bfrag: Tensor, n: int, y: Tensor, shift: int,
+                    epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
+    """gemm_split_f16 with an operand shift (record f16: pointwise data gradients): the rows times 2^shift are what is rounded
+    to fp16, alpha takes 2^-shift.  Shapes and policy: gemm_split_f16_supported / gemm_split_f16_wanted."""
+    k1 = a1.shape[-1]
+    k2 = a2.shape[-1] if a2 is not None else 0
+    check(lib().psld_gemm_split_f16s_f32(a1.data_ptr(), k1, _p(a2), k2, m, bfrag.data_ptr(), n, y.data_ptr(),
+                                         ldy if ldy is not None else n, C.byref(epi) if epi is not None else None,
+                                         int(shift), _stream()), "psld_gemm_split_f16s_f32")
 
 
 @functools.lru_cache(maxsize=None)

@@ -387,9 +387,10 @@ class NCSNpp(nn.Module):
         """Two-limb Winograd fragments of a 3x3 weight (ops.conv3x3_wino_frag_x3 / conv3x3_wino_dgrad_frag_x3)."""
         return self._wcache.get(conv.weight, "wfrag_d_x3" if dgrad else "wfrag_x3", _wfrag_x3_entry, dgrad)
 
-    def _wfrag_f16(self, conv: _Affine) -> Tensor:
-        """One-plane fp16 Winograd fragments of a 3x3 weight (ops.conv3x3_wino_frag_f16; eval math 'f16')."""
-        return self._wcache.get(conv.weight, "wfrag_f16", _wfrag_f16_entry)
+    def _wfrag_f16(self, conv: _Affine, dgrad: bool = False) -> Tensor:
+        """One-plane fp16 Winograd fragments of a 3x3 weight (ops.conv3x3_wino_frag_f16: eval math 'f16', record f16;
+        ``dgrad``: ops.conv3x3_wino_dgrad_frag_f16, record f16's data gradient)."""
+        return self._wcache.get(conv.weight, "wfrag_d_f16" if dgrad else "wfrag_f16", _wfrag_f16_entry, dgrad)
 
     def _pfrag(self, owner: nn.Parameter, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor] = None,
                chunk0: int = 0, chunks_total: int = 0, n0: int = 0, n_total: int = 0) -> Tensor:
@@ -428,15 +429,18 @@ class NCSNpp(nn.Module):
 
     def _qkv_frags_x3(self, mod, dgrad: bool = False, f16: bool = False):
         """The forward (``dgrad``: data-gradient) q | k | v fragment set of _qkv_frags in two-limb form (math mode / record
-        math 'bf16x3'; whole-tile sets only: c % 128 == 0).  ``f16``: the forward set as one fp16 plane (eval math 'f16')."""
+        math 'bf16x3'; whole-tile sets only: c % 128 == 0).  ``f16``: the set as one fp16 plane (eval math 'f16', record f16)."""
         n0 = mod.NIN_0
         c = n0.W.shape[0]
         if f16:
             fb = ops.gemm_frag_bytes_f16(c, c)
-            pf = self._wcache.entry(n0.W, "qkv_set_f16", lambda w: Entry(
+            pf = self._wcache.entry(n0.W, "qkv_set_d_f16" if dgrad else "qkv_set_f16", lambda w: Entry(
                 w, out=torch.empty(3 * fb, dtype=torch.uint8, device=w.device), build=lambda prev: prev)).out
             for i, nin in enumerate((n0, mod.NIN_1, mod.NIN_2)):
-                self._pfrag(nin.W, "qkv_f_f16", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
+                if dgrad:       # concatenated along K, as in _qkv_frags
+                    self._pfrag(nin.W, "qkv_d_f16", c, c, c, 1, into=pf, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
+                else:
+                    self._pfrag(nin.W, "qkv_f_f16", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
             return pf
         fb = ops.gemm_frag_bytes_x3(c, c)
         # the holder of the shared buffer (no family: the "qkv_d_x3" / "qkv_f_x3" entries of the three projections fill it)

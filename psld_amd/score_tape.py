@@ -112,6 +112,13 @@ class _ExecBase:
         # records no backward pass runs the one-product fp16 form of the Winograd-forward and eight-wave pointwise launches;
         # everything else, and every recording pass, runs as without it.  NOT fp32-equivalent (~1e-3 rel-L2: DESIGN 4b''')
         self.f16 = self.split and not record and ops.eval_math() == "f16"
+        # record f16 (ops.set_record_f16, opt-in; PSLD_MATH=f16_train): a recording pass under record math 'bf16x3' takes the
+        # one-product fp16 launch where one exists - Winograd forward and data gradient, eight-wave pointwise forward and data
+        # gradient - and stays on two limbs elsewhere (every weight gradient, LIMB_TAIL, direct limb 3x3, attention products,
+        # the tile engine, launches below 128 tiles).  The data gradients shift dy by 2^gshift before their one rounding
+        # (ops.take_grad_shift, read once when the backward pass starts).  Reference-GPU-equivalent, NOT fp32-equivalent
+        self.f16r = record and self.split and ops.record_math() == "bf16x3" and ops.record_f16()
+        self.gshift = 0
         self.limb_planes = os.environ.get("PSLD_LIMB_PLANES", "1") != "0"    # A/B switch for tools/bench_sample.py
         # forward attention in one kernel (attention.hip) wherever it takes the shape (B=128: 8x8 maps 17 vs 54 us of the
         # three-kernel path, 16x16 maps 62-65 vs 72 us, tools/bench_attn.py); PSLD_FUSED_ATTN=0: the three kernels
@@ -412,7 +419,7 @@ class _ExecBase:
         if route is None:
             route = R.conv3_route(self.split, c, c2, b, h, w, cout, isinstance(x, ops.LimbPlanes), self.wino_wanted)
         if route == R.WINO:
-            if self.f16:
+            if self.f16 or self.f16r:
                 ops.conv3x3_wino_f16(x, x2, self.net._wfrag_f16(conv), cout, out, epi, allow_split=True)
             elif self.x3:
                 ops.conv3x3_wino_x3(x, x2, self.net._wfrag_x3(conv), cout, out, epi, allow_split=True)
@@ -435,13 +442,13 @@ class _ExecBase:
 
     # -- pointwise GEMMs (1x1 shortcuts, NIN projections, the pyramid's im2col GEMM) on a score_routes.pointwise_* route ------
     def pw_fwd(self, route: str, a1: Tensor, a2: Optional[Tensor], m: int, w: PointwiseWeight, y: Tensor, epi):
-        """y[m][w.n] = epi([a1 | a2] W^T).  LIMB runs the fp16 form where eval math 'f16', else the two-limb form where math mode
-        'bf16x3', wants it (LIMB_TAIL has neither);
+        """y[m][w.n] = epi([a1 | a2] W^T).  LIMB runs the fp16 form where eval math 'f16' (a recording pass: record f16), else the
+        two-limb form where math mode 'bf16x3', wants it (LIMB_TAIL has neither);
         TILE is the tile engine's 1x1 convolution for an "oi" weight (it alone takes a second source), its GEMM for NIN."""
         n = w.n
         if route == R.LIMB_TAIL:
             ops.gemm_split_tail(a1, m, w.frag(tail=True), n, y, epi)
-        elif route == R.LIMB and self.f16 and ops.gemm_split_f16_wanted(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n):
+        elif route == R.LIMB and (self.f16 or self.f16r) and ops.gemm_split_f16_wanted(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n):
             ops.gemm_split_f16(a1, a2, m, w.frag(f16=True), n, y, epi)
         elif route == R.LIMB and self.x3 and ops.gemm_split_x3_wanted(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n):
             ops.gemm_split_x3(a1, a2, m, w.frag(x3=True), n, y, epi)
@@ -457,17 +464,21 @@ class _ExecBase:
         """dx[m][w.k] = epi(dy[m][w.n] W).  ``cols`` = (lo, hi), limb routes: input channels lo .. hi alone, into a dx that wide
         (one source of an unmaterialised concatenation: a data gradient's fragments are ordered by output-channel tile, so a
         source's share is a contiguous slice of them).  LIMB runs the two-limb form where a recording pass under record math
-        'bf16x3' wants it (the policy of pw_fwd, on the launch's own width)."""
+        'bf16x3' wants it (the policy of pw_fwd, on the launch's own width) - under record f16 the fp16 form with the pass's
+        operand shift."""
         n = w.k
         if route == R.TILE:
             wt, tb, ld = w.tile(True)
             return ops.gemm_raw(0, tb, m, n, w.n, dy, w.n, 0, wt, ld, 0, dx, n, 0, epi=epi)
-        x3 = route == R.LIMB and self.x3 and ops.gemm_split_x3_wanted(w.n, 0, m, n if cols is None else cols[1] - cols[0])
-        frag = w.frag(True, x3=x3, tail=route == R.LIMB_TAIL)
+        f16 = route == R.LIMB and self.f16r and ops.gemm_split_f16_wanted(w.n, 0, m, n if cols is None else cols[1] - cols[0])
+        x3 = not f16 and route == R.LIMB and self.x3 and ops.gemm_split_x3_wanted(w.n, 0, m, n if cols is None else cols[1] - cols[0])
+        frag = w.frag(True, x3=x3, tail=route == R.LIMB_TAIL, f16=f16)
         if cols is not None:
             frag, n = frag[frag.numel() * cols[0] // n:frag.numel() * cols[1] // n], cols[1] - cols[0]
         if route == R.LIMB_TAIL:
             ops.gemm_split_tail(dy, m, frag, n, dx, epi)
+        elif f16:
+            ops.gemm_split_f16s(dy, None, m, frag, n, dx, self.gshift, epi)
         elif x3:
             ops.gemm_split_x3(dy, None, m, frag, n, dx, epi)
         else:
@@ -557,7 +568,9 @@ class _ExecBase:
         if route is None and (k, stride, pad) == (3, 1, 1):
             route = R.conv3_route(self.split, dy.shape[-1], 0, dy.shape[0], ih, iw, cin, wino=self.wino_wanted)
         if route == R.WINO:
-            if self.x3:
+            if self.f16r:
+                ops.conv3x3_wino_f16s(dy, None, self.net._wfrag_f16(conv, True), cin, out, self.gshift, epi, allow_split=True)
+            elif self.x3:
                 ops.conv3x3_wino_x3(dy, None, self.net._wfrag_x3(conv, True), cin, out, epi, allow_split=True)
             else:
                 ops.conv3x3_wino(dy, None, self.net._wfrag(conv, True), cin, out, epi, allow_split=True)     # Winograd F(2x2, 3x3)
@@ -585,6 +598,9 @@ class _ExecBase:
 
     def _backward(self, grad_out_nchw: Tensor):
         net = self.net
+        # the operand shift of this pass's fp16 data gradients: a host integer from the divisor the loss published (consumed here)
+        shift = ops.take_grad_shift()
+        self.gshift = shift if self.f16r else 0
         g_out = grad_out_nchw.contiguous()
         self.head_grad.g = g_out if net.is_classifier else ops.nchw_to_nhwc(g_out)
         # every pass: gn_backward and the resblock column sums allocate from the arena whether or not the reductions are

@@ -38,10 +38,12 @@ def _wfrag_x3_entry(w: Tensor, dgrad: bool = False) -> Entry:
                  rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
 
 
-def _wfrag_f16_entry(w: Tensor) -> Entry:
-    """One-plane fp16 Winograd fragments (forward orientation): the 'wino' entries' siblings for eval math 'f16'."""
-    return Entry(w, build=lambda prev: ops.conv3x3_wino_frag_f16(w.detach(), prev), family="wino_f16",
-                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, False, out), w.shape[0] * w.shape[1] // 8)], graph=True)
+def _wfrag_f16_entry(w: Tensor, dgrad: bool = False) -> Entry:
+    """One-plane fp16 Winograd fragments: the 'wino' entries' siblings for eval math 'f16' (forward orientation) and record
+    f16 (both orientations)."""
+    pack = ops.conv3x3_wino_dgrad_frag_f16 if dgrad else ops.conv3x3_wino_frag_f16
+    return Entry(w, build=lambda prev: pack(w.detach(), prev), family="wino_f16",
+                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
 
 
 def pfrag_tail(n: int, k: int, n_total: int = 0, chunks_total: int = 0) -> bool:
@@ -70,7 +72,7 @@ def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Op
     if pfrag_tail(n, k, n_total, chunks_total):
         return _pfrag_tail_entry(p, tag, n, k, sn, sk, into, chunk0, chunks_total, n0, n_total)
     x3 = tag.endswith("_x3")        # two-limb fragments (math mode 'bf16x3'): their own packers and batch family
-    f16 = tag.endswith("_f16")      # one fp16 plane (eval math 'f16'): likewise
+    f16 = tag.endswith("_f16")      # one fp16 plane (eval math 'f16', record f16): likewise
     pack, pack_batch = (ops.gemm_frag_x3, ops.pack_frag_batch_x3) if x3 else \
         (ops.gemm_frag_f16, ops.pack_frag_batch_f16) if f16 else (ops.gemm_frag, ops.pack_frag_batch)
 
@@ -154,11 +156,11 @@ class PointwiseWeight(NamedTuple):
         return self.w, int(oi != dgrad), self.k if oi else self.n
 
     def frag(self, dgrad: bool = False, x3: bool = False, tail: bool = False, f16: bool = False) -> Tensor:
-        """Three-limb (``x3``: two-limb, ``f16``: one fp16 plane, forward only - both whole-tile sets only) fragments of B[n][k],
-        or of B[k][n] for the data gradient."""
+        """Three-limb (``x3``: two-limb, ``f16``: one fp16 plane - both whole-tile sets only) fragments of B[n][k], or of B[k][n]
+        for the data gradient."""
         net, w, kind = self.net, self.w, self.kind
         n, k = (self.k, self.n) if dgrad else (self.n, self.k)
-        assert not (f16 and (dgrad or x3 or tail))
+        assert not (f16 and (x3 or tail))
         sfx = "_x3" if x3 else "_f16" if f16 else ""
         if kind == "qkv":
             return net._qkv_frags_x3(w, dgrad, f16) if x3 or f16 else self.qkv[int(dgrad)]

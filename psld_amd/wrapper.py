@@ -139,8 +139,11 @@ class SDEWrapper(_Base):
         if not hasattr(self, "_graph_steps"):
             self._graph_steps = {}
         # a capture replays its own launches: which ones a recording pass issues depends on the math mode (limb kernels or the
-        # fp32 tile engine) and on the record math (three or two limbs)
-        key = (tuple(batch.shape), batch.device.index, bool(net.training), ops.math_mode(), ops.record_math())
+        # fp32 tile engine), on the record math (three or two limbs) and on record f16 with its gradient shift (fp16 launches;
+        # the shift is a launch argument.  The automatic one follows from the batch shape and this wrapper's loss, so the
+        # setting itself - None or the forced value - is the key)
+        key = (tuple(batch.shape), batch.device.index, bool(net.training), ops.record_f16(), ops.grad_shift_setting(),
+               ops.math_mode(), ops.record_math())
         ent = self._graph_steps.get(key)
         if ent is None:
             ent = self._graph_steps[key] = {"seen": 0}
