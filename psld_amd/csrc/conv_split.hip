@@ -16,8 +16,14 @@
 // k-depth per instruction.  Every fp32 value x is decomposed EXACTLY into hi + mid + lo (bf16 each, 8 significant
 // bits apiece, 24 in total) and a product a*b is accumulated in fp32 from the six limb products of weight
 // >= 2^-16: lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi.  The three dropped products are < 2^-23 |a*b| —
-// below the rounding of the fp32 product itself — so results agree with the fp32 MFMA path to fp32 rounding
-// (tests/test_kernels_gpu.py runs every parity case in both modes).
+// below the rounding of the fp32 product itself — so results agree with the fp32 MFMA path to fp32 rounding.
+// tests/test_limb_probe_gpu.py holds every launch form of this file, conv_wino.hip and wgrad_wino.hip to that: on
+// operands whose limb products and partial sums are all exact in fp32 the output EQUALS the six-product model
+// (tests/limb_probe.py) element by element — a missing, doubled or misplaced product changes named bits of named
+// elements — and on dense operands the error against that model stays within 4x that of plain fp32, per output column
+// and per band of 16 rows.  (The rel-L2 gates of tests/test_kernels_gpu.py, 3e-6, would pass a kernel that drops one of
+// the three small products everywhere.  Only test_conv3x3_split_forward there runs the fp32 MFMA kernel beside the
+// limb kernel on the same inputs; the other parity cases run the limb kernels alone, against fp64.)
 //
 // Why a direct convolution rather than the im2col tile engine: the limb split costs VALU work and LDS stores,
 // so the A operand is converted ONCE per 32-channel chunk — a halo tile of (rows+2) x (W+2) pixels kept in LDS
