@@ -448,6 +448,53 @@ int psld_conv2d_wgrad_nhwc_f32(const float* dy, int lddy, int cout,
                                float* slabs, int cin_total, int col0, int nsplit,
                                hipStream_t stream);
 
+/* ---- launch plans of the fp32 tile engine ------------------------------------------------------------------------
+ * Which kernel form psld_gemm_f32 / psld_gemm_tn_splitk_f32 / psld_conv2d_nhwc_ws_f32 / psld_conv2d_wgrad_nhwc_f32 take for
+ * a call: the launches select their kernel through the same host code these queries run, so a test (or a caller sizing a
+ * workspace) can see the form a shape reaches.  Each query takes the launch's own arguments without the stream.  Host
+ * arithmetic only: device pointers (those inside *epi included) are looked at for 16-byte alignment and null-ness and are
+ * never dereferenced; nothing is launched and no HIP call is made.  Returns a form code, or -1 for arguments the launch
+ * refuses (psld_last_error has the message).
+ * Form code = kernel kind | operand flags:
+ *   PSLD_TILE_GENERIC       128 x 128 tile, one LDS buffer, any shape / alignment (every TT GEMM, K % 32 != 0, channel counts
+ *                           that are no multiple of 32, transposed stride, more than 31 taps, non-power-of-two weight-gradient maps)
+ *   PSLD_TILE_FAST128       128 x 128 tile of the branch-free kernel (all operands float4-addressable)
+ *   PSLD_TILE_FAST256       128 x 256 tile of it (K-contiguous B: NT GEMM and convolution; N % 256 == 0 and >= 512 such tiles)
+ *   PSLD_TILE_FAST64        64 x 128 tile of it (NT GEMM / convolution of more than 64 rows whose 128-row grid has <= 256 tiles)
+ *   PSLD_TILE_FAST64_SPLITK convolution only: the 64 x 128 kernel over 2..8 K ranges into the workspace, then the reduction +
+ *                           epilogue pass (psld_conv2d_plan also returns the range count and the K values per range)
+ *   PSLD_TILE_A_VEC / PSLD_TILE_B_VEC: the A / B operand (GEMM: A / B; convolution: input / weights; weight gradients: dy / x) is
+ *                           loaded as float4 (set on every fast form; on the generic form one flag per operand). */
+enum psld_tile_form {
+    PSLD_TILE_GENERIC = 0,
+    PSLD_TILE_FAST128 = 1,
+    PSLD_TILE_FAST256 = 2,
+    PSLD_TILE_FAST64 = 3,
+    PSLD_TILE_FAST64_SPLITK = 4,
+    PSLD_TILE_KIND_MASK = 15,
+    PSLD_TILE_A_VEC = 16,
+    PSLD_TILE_B_VEC = 32
+};
+int psld_gemm_plan(int trans_a, int trans_b, int M, int N, int K,
+                   const float* A, int lda, long long stride_a,
+                   const float* B, int ldb, long long stride_b,
+                   const float* C, int ldc, long long stride_c, int batch,
+                   const psld_epilogue_t* epi);
+int psld_gemm_tn_splitk_plan(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
+                             const float* slabs, int nsplit);
+/* *nsplit / *kper (either may be NULL): K ranges of the launch (1: not split) and K values per range. */
+int psld_conv2d_plan(const float* x1, int c1, const float* x2, int c2,
+                     int batch, int ih, int iw,
+                     const float* w_ohwi, int cout, int kh, int kw,
+                     int stride, int pad, int transposed_stride,
+                     int oh, int ow, const float* y, int ldy,
+                     const psld_epilogue_t* epi, const void* workspace, long long ws_bytes,
+                     int* nsplit, int* kper);
+int psld_conv2d_wgrad_plan(const float* dy, int lddy, int cout,
+                           const float* x, int cin, int batch, int ih, int iw,
+                           int kh, int kw, int stride, int pad, int oh, int ow,
+                           const float* slabs, int cin_total, int col0, int nsplit);
+
 /* out[perm(i)] = alpha * sum_s slabs[s][i]; layout: 0 = keep [co][tap][ci], 1 = write OIHW [co][ci][tap]. */
 int psld_reduce_slabs_f32(const float* slabs, int nsplit, long long n, float* out,
                           int layout, int cout, int taps, int cin, float alpha, hipStream_t stream);

@@ -64,6 +64,11 @@ class SscsCoeffs(C.Structure):
 
 I, F, D, LL, P = C.c_int, C.c_float, C.c_double, C.c_longlong, C.c_void_p
 EP = C.POINTER(Epilogue)
+IP = C.POINTER(C.c_int)
+
+# enum psld_tile_form: kernel kind | operand flags, what the psld_*_plan queries return
+TILE_GENERIC, TILE_FAST128, TILE_FAST256, TILE_FAST64, TILE_FAST64_SPLITK = 0, 1, 2, 3, 4
+TILE_KIND_MASK, TILE_A_VEC, TILE_B_VEC = 15, 16, 32
 
 ABI_VERSION = 14   # PSLD_ABI_VERSION of include/psld_hip.h these signatures were written against
 
@@ -87,6 +92,11 @@ SIGNATURES = {
     "psld_conv2d_workspace_bytes": (LL, [I, I, I, I]),
     "psld_conv2d_nhwc_ws_f32": (I, [P, I, P, I, I, I, I, P, I, I, I, I, I, I, I, I, P, I, EP, P, LL, P]),
     "psld_conv2d_wgrad_nhwc_f32": (I, [P, I, I, P, I, I, I, I, I, I, I, I, I, I, P, I, I, I, P]),
+    # launch plans of the fp32 tile engine: the launch's arguments without the stream -> form code (TILE_* below)
+    "psld_gemm_plan": (I, [I, I, I, I, I, P, I, LL, P, I, LL, P, I, LL, I, EP]),
+    "psld_gemm_tn_splitk_plan": (I, [I, I, I, P, I, P, I, P, I]),
+    "psld_conv2d_plan": (I, [P, I, P, I, I, I, I, P, I, I, I, I, I, I, I, I, P, I, EP, P, LL, IP, IP]),
+    "psld_conv2d_wgrad_plan": (I, [P, I, I, P, I, I, I, I, I, I, I, I, I, I, P, I, I, I]),
     "psld_conv3x3_frag_bytes": (LL, [I, I]),
     "psld_conv3x3_split_supported": (I, [I, I, I, I, I, I]),
     "psld_pack_conv3x3_frag": (I, [P, P, I, I, I, P]),

@@ -714,17 +714,21 @@ int launch_fast_impl(const TileArgs& a, FastGeom fg, int nz, hipStream_t stream,
     return PSLD_OK;
 }
 
+// 128x256 block tile (wave 64x128) when N is a multiple of 256 and the grid still fills the chip (K-contiguous B and 128-row
+// tiles only): measured +2..3 % on the 32x32 layers and the 4096^3 GEMM (134 TF), neutral-to-worse on smaller grids
+inline bool fast_tile256(const TileArgs& a, int nz) {
+    return a.N % 256 == 0 && (long long)cdiv(a.M, 128) * (a.N / 256) * nz >= 512;
+}
+
+// `wide`: the plan's choice of the 128x256 tile (fast_tile256; the form functions below are its only callers)
 template <int AMODE, int BMODE, int TBM = 128>
-int launch_fast(const TileArgs& a, FastGeom fg, int nz, hipStream_t stream, const char* name) {
+int launch_fast(const TileArgs& a, FastGeom fg, int nz, hipStream_t stream, const char* name, bool wide = false) {
     // Measured on MI355X (tools/bench_tile.py): the conv / wgrad loaders prefer one LDS buffer at 3 workgroups
     // per CU (+1.5 % / +3 %), the plain GEMM prefers two buffers at 2 per CU (+3 %).
     constexpr int NBUF = (AMODE == OP_IM2COL || BMODE == OP_SHIFT) ? 1 : 2;
     constexpr bool B_KC = (BMODE == OP_KC || BMODE == OP_IM2COL);
     if constexpr (B_KC && TBM == 128) {
-        // 128x256 block tile (wave 64x128) when N is a multiple of 256 and the grid still fills the chip:
-        // measured +2..3 % on the 32x32 layers and the 4096^3 GEMM (134 TF), neutral-to-worse on smaller grids
-        if (a.N % 256 == 0 && (long long)cdiv(a.M, 128) * (a.N / 256) * nz >= 512)
-            return launch_fast_impl<AMODE, BMODE, TBM, 1, 256>(a, fg, nz, stream, name);
+        if (wide) return launch_fast_impl<AMODE, BMODE, TBM, 1, 256>(a, fg, nz, stream, name);
     }
     return launch_fast_impl<AMODE, BMODE, TBM, NBUF, 128>(a, fg, nz, stream, name);
 }
@@ -880,14 +884,21 @@ int psld_detail_conv_reduce_epilogue(const float* slabs, int nsplit, int M, int 
 // ---------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------
-extern "C" int psld_gemm_f32(int trans_a, int trans_b, int M, int N, int K,
-                             const float* A, int lda, long long stride_a,
-                             const float* B, int ldb, long long stride_b,
-                             float* C, int ldc, long long stride_c, int batch,
-                             const psld_epilogue_t* epi, hipStream_t stream) {
+namespace {
+
+// ---- launch plans: ONE body of code per entry point fills the kernel arguments and selects the form; the launch below
+// switches on that form and the exported psld_*_plan query returns it.  Host arithmetic only: device pointers are looked at
+// for alignment and null-ness, never dereferenced, and no HIP call is made.
+inline int with_vec(int kind, const TileArgs& a) {
+    return kind | (a.A.vec ? PSLD_TILE_A_VEC : 0) | (a.B.vec ? PSLD_TILE_B_VEC : 0);
+}
+
+int gemm_setup(int trans_a, int trans_b, int M, int N, int K, const float* A, int lda, long long stride_a,
+               const float* B, int ldb, long long stride_b, float* C, int ldc, long long stride_c, int batch,
+               const psld_epilogue_t* epi, TileArgs& a, int& form) {
     PSLD_CHECK_ARG(A && B && C, "psld_gemm_f32: null pointer");
     PSLD_CHECK_ARG(M >= 0 && N >= 0 && K > 0 && batch >= 1, "psld_gemm_f32: bad shape %d %d %d x%d", M, N, K, batch);
-    TileArgs a{};
+    a = TileArgs{};
     a.M = M; a.N = N; a.K = K;
     a.A = {A, nullptr, stride_a, lda, 0};
     a.B = {B, nullptr, stride_b, ldb, 0};
@@ -902,14 +913,145 @@ extern "C" int psld_gemm_f32(int trans_a, int trans_b, int M, int N, int K,
     if (trans_b)  a.B.vec = aligned16(B) && ldb % 4 == 0 && K % 4 == 0 && stride_b % 4 == 0;
     else          a.B.vec = aligned16(B) && ldb % 4 == 0 && N % 4 == 0 && stride_b % 4 == 0;
     const bool fastok = a.A.vec && a.B.vec && K % BK == 0 && M > 0 && N > 0;
-    FastGeom fg{1, 0, 0, 0, nullptr};
-    if (fastok) {
+    int kind = PSLD_TILE_GENERIC;
+    if (fastok && !(trans_a && trans_b)) {
         const bool small = (long long)cdiv(M, BM) * cdiv(N, BN) * batch <= 256;
-        if (!trans_a && trans_b && small && M > 64)
-            return launch_fast<OP_KC, OP_KC, 64>(a, fg, batch, stream, "psld_gemm_f32[NT,fast64]");
-        if (!trans_a && trans_b)  return launch_fast<OP_KC, OP_KC>(a, fg, batch, stream, "psld_gemm_f32[NT,fast]");
+        if (!trans_a && trans_b && small && M > 64) kind = PSLD_TILE_FAST64;
+        else if (!trans_a && trans_b && fast_tile256(a, batch)) kind = PSLD_TILE_FAST256;   // NT: the only layout with a K-contiguous B
+        else kind = PSLD_TILE_FAST128;
+    }
+    form = with_vec(kind, a);
+    return PSLD_OK;
+}
+
+int gemm_tn_splitk_setup(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* slabs, int nsplit,
+                         TileArgs& a, int& form) {
+    PSLD_CHECK_ARG(A && B && slabs && nsplit >= 1, "psld_gemm_tn_splitk_f32: bad args");
+    a = TileArgs{};
+    a.M = M; a.N = N; a.K = K;
+    a.A = {A, nullptr, 0, lda, aligned16(A) && lda % 4 == 0 && M % 4 == 0};
+    a.B = {B, nullptr, 0, ldb, aligned16(B) && ldb % 4 == 0 && N % 4 == 0};
+    a.C = slabs; a.c_stride_z = 0; a.c_stride_split = (long long)M * N; a.ldc = N;
+    a.nsplit = nsplit; a.kper = cdiv(cdiv(K, nsplit), BK) * BK;
+    a.e = make_epilogue(nullptr);
+    form = with_vec((a.A.vec && a.B.vec && M > 0 && N > 0) ? PSLD_TILE_FAST128 : PSLD_TILE_GENERIC, a);
+    return PSLD_OK;
+}
+
+// Split count of a fast64 convolution whose 64-row tiling leaves most of the 256 CUs x 3 slots empty (1: no split).
+// No split range may come out empty: the workgroups of an empty range would still stage K-step `ksteps`, one past the
+// weight rows and - through the chunk -> source mapping - past the last source (ksteps = 49 at 8 splits: 7 x 7 = 49).
+inline int conv_split_count(long long tiles64, int ksteps, long long slab_bytes, long long ws_bytes) {
+    int ns = (int)(768 / tiles64);
+    if (ns > 8) ns = 8;
+    if (ns > ksteps / 6) ns = ksteps / 6;
+    while (ns >= 2 && (long long)(ns - 1) * cdiv(ksteps, ns) >= ksteps) --ns;
+    if ((long long)ns * slab_bytes > ws_bytes) ns = 1;
+    return ns < 1 ? 1 : ns;
+}
+
+// a: the launch's arguments; p: those of the split-K launch into the workspace (meaningful when form is FAST64_SPLITK)
+int conv2d_setup(const float* x1, int c1, const float* x2, int c2, int batch, int ih, int iw, const float* w_ohwi, int cout,
+                 int kh, int kw, int stride, int pad, int transposed_stride, int oh, int ow, float* y, int ldy,
+                 const psld_epilogue_t* epi, void* workspace, long long ws_bytes, TileArgs& a, TileArgs& p, FastGeom& fg,
+                 int& form) {
+    PSLD_CHECK_ARG(x1 && w_ohwi && y, "psld_conv2d_nhwc_f32: null pointer");
+    PSLD_CHECK_ARG(c1 > 0 && c2 >= 0 && (c2 == 0 || x2), "psld_conv2d_nhwc_f32: bad channel split");
+    PSLD_CHECK_ARG(stride >= 1 && transposed_stride >= 1, "psld_conv2d_nhwc_f32: bad stride");
+    const int ct = c1 + c2;
+    a = TileArgs{};
+    a.M = batch * oh * ow; a.N = cout; a.K = kh * kw * ct;
+    a.A = {x1, x2, 0, 0, 0};
+    a.A.vec = aligned16(x1) && (!x2 || aligned16(x2)) && c1 % 4 == 0 && c2 % 4 == 0;
+    a.B = {w_ohwi, nullptr, 0, a.K, aligned16(w_ohwi) && a.K % 4 == 0};
+    a.C = y; a.ldc = ldy; a.c_stride_z = 0; a.c_stride_split = 0;
+    a.nsplit = 1; a.kper = cdiv(a.K, BK) * BK;
+    a.g = {ih, iw, c1, c2, oh, ow, kh, kw, stride, pad, transposed_stride};
+    a.e = make_epilogue(epi);
+    PSLD_CHECK_ARG(!a.e.gn_part, "fp32 tile engine: psld_epilogue_t.gn_part is a limb-kernel feature");
+    p = a;
+    fg = FastGeom{kh * kw, 0, 0, ct / BK, nullptr};
+    int kind = PSLD_TILE_GENERIC;
+    if (a.A.vec && a.B.vec && c1 % BK == 0 && c2 % BK == 0 && transposed_stride == 1 && a.M > 0 && kh * kw <= 31) {
+        const long long tiles128 = (long long)cdiv(a.M, BM) * cdiv(a.N, BN);
+        const long long tiles64 = (long long)cdiv(a.M, 64) * cdiv(a.N, BN);
+        const int ksteps = a.K / BK;
+        // split-K when even the 64-row tiling leaves most of the 256 CUs x 3 slots empty
+        int ns = 1;
+        if (workspace && tiles64 <= 256 && a.M > 64 && cout % 4 == 0 && ldy % 4 == 0 && aligned16(y) &&
+            (!a.e.bias || aligned16(a.e.bias)) && (!a.e.rowbias || (aligned16(a.e.rowbias) && a.e.ld_rowbias % 4 == 0)) &&
+            (!a.e.res || (aligned16(a.e.res) && a.e.ldres % 4 == 0)))
+            ns = conv_split_count(tiles64, ksteps, (long long)a.M * a.N * (long long)sizeof(float), ws_bytes);
+        if (ns >= 2) {
+            p.C = reinterpret_cast<float*>(workspace);
+            p.ldc = a.N;
+            p.c_stride_split = (long long)a.M * a.N;
+            p.nsplit = ns;
+            p.kper = cdiv(ksteps, ns) * BK;
+            p.e = make_epilogue(nullptr);
+            kind = PSLD_TILE_FAST64_SPLITK;
+        } else if (tiles128 <= 256 && a.M > 64) {
+            kind = PSLD_TILE_FAST64;
+        } else {
+            kind = fast_tile256(a, 1) ? PSLD_TILE_FAST256 : PSLD_TILE_FAST128;
+        }
+    }
+    form = with_vec(kind, a);
+    return PSLD_OK;
+}
+
+int conv2d_wgrad_setup(const float* dy, int lddy, int cout, const float* x, int cin, int batch, int ih, int iw, int kh, int kw,
+                       int stride, int pad, int oh, int ow, float* slabs, int cin_total, int col0, int nsplit, TileArgs& a,
+                       FastGeom& fg, int& form) {
+    PSLD_CHECK_ARG(dy && x && slabs && nsplit >= 1, "psld_conv2d_wgrad_nhwc_f32: bad args");
+    a = TileArgs{};
+    a.M = cout; a.N = cin; a.K = batch * oh * ow;
+    a.A = {dy, nullptr, 0, lddy, aligned16(dy) && lddy % 4 == 0 && cout % 4 == 0};
+    a.B = {x, nullptr, 0, cin, aligned16(x) && cin % 4 == 0};
+    a.C = slabs + col0;
+    a.ldc = kh * kw * cin_total;
+    a.c_stride_z = cin_total;                                  // tap -> column block
+    a.c_stride_split = (long long)cout * kh * kw * cin_total;  // slab
+    a.nsplit = nsplit; a.kper = cdiv(cdiv(a.K, nsplit), BK) * BK;
+    a.g = {ih, iw, cin, 0, oh, ow, kh, kw, stride, pad, 1};
+    a.e = make_epilogue(nullptr);
+    const int ows = ilog2_exact(ow), ohs = ilog2_exact(oh);
+    const bool fast = a.A.vec && a.B.vec && ows >= 0 && ohs >= 0 && cout > 0 && cin > 0;
+    fg = FastGeom{kh * kw, fast ? ows : 0, fast ? ohs : 0, 0, nullptr};
+    form = with_vec(fast ? PSLD_TILE_FAST128 : PSLD_TILE_GENERIC, a);
+    return PSLD_OK;
+}
+
+}  // namespace
+
+extern "C" int psld_gemm_plan(int trans_a, int trans_b, int M, int N, int K, const float* A, int lda, long long stride_a,
+                              const float* B, int ldb, long long stride_b, const float* C, int ldc, long long stride_c,
+                              int batch, const psld_epilogue_t* epi) {
+    TileArgs a;
+    int form = 0;
+    if (gemm_setup(trans_a, trans_b, M, N, K, A, lda, stride_a, B, ldb, stride_b, const_cast<float*>(C), ldc, stride_c, batch,
+                   epi, a, form) != PSLD_OK)
+        return -1;
+    return form;
+}
+
+extern "C" int psld_gemm_f32(int trans_a, int trans_b, int M, int N, int K,
+                             const float* A, int lda, long long stride_a,
+                             const float* B, int ldb, long long stride_b,
+                             float* C, int ldc, long long stride_c, int batch,
+                             const psld_epilogue_t* epi, hipStream_t stream) {
+    TileArgs a;
+    int form = 0;
+    if (int st = gemm_setup(trans_a, trans_b, M, N, K, A, lda, stride_a, B, ldb, stride_b, C, ldc, stride_c, batch, epi, a, form))
+        return st;
+    const int kind = form & PSLD_TILE_KIND_MASK;
+    FastGeom fg{1, 0, 0, 0, nullptr};
+    if (kind == PSLD_TILE_FAST64) return launch_fast<OP_KC, OP_KC, 64>(a, fg, batch, stream, "psld_gemm_f32[NT,fast64]");
+    if (kind != PSLD_TILE_GENERIC) {
+        if (!trans_a && trans_b)
+            return launch_fast<OP_KC, OP_KC>(a, fg, batch, stream, "psld_gemm_f32[NT,fast]", kind == PSLD_TILE_FAST256);
         if (!trans_a && !trans_b) return launch_fast<OP_KC, OP_MC>(a, fg, batch, stream, "psld_gemm_f32[NN,fast]");
-        if (trans_a && !trans_b)  return launch_fast<OP_MC, OP_MC>(a, fg, batch, stream, "psld_gemm_f32[TN,fast]");
+        return launch_fast<OP_MC, OP_MC>(a, fg, batch, stream, "psld_gemm_f32[TN,fast]");
     }
     if (!trans_a && trans_b)  return launch<OP_KC, OP_KC>(a, batch, stream, "psld_gemm_f32[NT]");
     if (!trans_a && !trans_b) return launch<OP_KC, OP_MC>(a, batch, stream, "psld_gemm_f32[NN]");
@@ -917,18 +1059,21 @@ extern "C" int psld_gemm_f32(int trans_a, int trans_b, int M, int N, int K,
     return launch<OP_MC, OP_KC>(a, batch, stream, "psld_gemm_f32[TT]");
 }
 
+extern "C" int psld_gemm_tn_splitk_plan(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
+                                        const float* slabs, int nsplit) {
+    TileArgs a;
+    int form = 0;
+    if (gemm_tn_splitk_setup(M, N, K, A, lda, B, ldb, const_cast<float*>(slabs), nsplit, a, form) != PSLD_OK) return -1;
+    return form;
+}
+
 // Split-K TN GEMM into slabs: slabs[s][M][N] = A[ks..ke]^T B[ks..ke]; caller reduces.
 extern "C" int psld_gemm_tn_splitk_f32(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                                        float* slabs, int nsplit, hipStream_t stream) {
-    PSLD_CHECK_ARG(A && B && slabs && nsplit >= 1, "psld_gemm_tn_splitk_f32: bad args");
-    TileArgs a{};
-    a.M = M; a.N = N; a.K = K;
-    a.A = {A, nullptr, 0, lda, aligned16(A) && lda % 4 == 0 && M % 4 == 0};
-    a.B = {B, nullptr, 0, ldb, aligned16(B) && ldb % 4 == 0 && N % 4 == 0};
-    a.C = slabs; a.c_stride_z = 0; a.c_stride_split = (long long)M * N; a.ldc = N;
-    a.nsplit = nsplit; a.kper = cdiv(cdiv(K, nsplit), BK) * BK;
-    a.e = make_epilogue(nullptr);
-    if (a.A.vec && a.B.vec && M > 0 && N > 0) {
+    TileArgs a;
+    int form = 0;
+    if (int st = gemm_tn_splitk_setup(M, N, K, A, lda, B, ldb, slabs, nsplit, a, form)) return st;
+    if ((form & PSLD_TILE_KIND_MASK) == PSLD_TILE_FAST128) {
         FastGeom fg{1, 0, 0, 0, nullptr};
         return launch_fast<OP_MC, OP_MC>(a, fg, 1, stream, "psld_gemm_tn_splitk_f32[fast]");
     }
@@ -937,6 +1082,21 @@ extern "C" int psld_gemm_tn_splitk_f32(int M, int N, int K, const float* A, int 
 
 extern "C" long long psld_conv2d_workspace_bytes(int batch, int oh, int ow, int cout) {
     return 8LL * batch * oh * ow * cout * (long long)sizeof(float);
+}
+
+extern "C" int psld_conv2d_plan(const float* x1, int c1, const float* x2, int c2, int batch, int ih, int iw,
+                                const float* w_ohwi, int cout, int kh, int kw, int stride, int pad, int transposed_stride,
+                                int oh, int ow, const float* y, int ldy, const psld_epilogue_t* epi, const void* workspace,
+                                long long ws_bytes, int* nsplit, int* kper) {
+    TileArgs a, p;
+    FastGeom fg;
+    int form = 0;
+    if (conv2d_setup(x1, c1, x2, c2, batch, ih, iw, w_ohwi, cout, kh, kw, stride, pad, transposed_stride, oh, ow,
+                     const_cast<float*>(y), ldy, epi, const_cast<void*>(workspace), ws_bytes, a, p, fg, form) != PSLD_OK)
+        return -1;
+    if (nsplit) *nsplit = p.nsplit;
+    if (kper) *kper = p.kper;
+    return form;
 }
 
 // Same as psld_conv2d_nhwc_f32 plus an optional workspace: when the output grid cannot fill the chip
@@ -949,52 +1109,27 @@ extern "C" int psld_conv2d_nhwc_ws_f32(const float* x1, int c1, const float* x2,
                                        int oh, int ow, float* y, int ldy,
                                        const psld_epilogue_t* epi, void* workspace, long long ws_bytes,
                                        hipStream_t stream) {
-    PSLD_CHECK_ARG(x1 && w_ohwi && y, "psld_conv2d_nhwc_f32: null pointer");
-    PSLD_CHECK_ARG(c1 > 0 && c2 >= 0 && (c2 == 0 || x2), "psld_conv2d_nhwc_f32: bad channel split");
-    PSLD_CHECK_ARG(stride >= 1 && transposed_stride >= 1, "psld_conv2d_nhwc_f32: bad stride");
-    const int ct = c1 + c2;
-    TileArgs a{};
-    a.M = batch * oh * ow; a.N = cout; a.K = kh * kw * ct;
-    a.A = {x1, x2, 0, 0, 0};
-    a.A.vec = aligned16(x1) && (!x2 || aligned16(x2)) && c1 % 4 == 0 && c2 % 4 == 0;
-    a.B = {w_ohwi, nullptr, 0, a.K, aligned16(w_ohwi) && a.K % 4 == 0};
-    a.C = y; a.ldc = ldy; a.c_stride_z = 0; a.c_stride_split = 0;
-    a.nsplit = 1; a.kper = cdiv(a.K, BK) * BK;
-    a.g = {ih, iw, c1, c2, oh, ow, kh, kw, stride, pad, transposed_stride};
-    a.e = make_epilogue(epi);
-    PSLD_CHECK_ARG(!a.e.gn_part, "fp32 tile engine: psld_epilogue_t.gn_part is a limb-kernel feature");
-    if (a.A.vec && a.B.vec && c1 % BK == 0 && c2 % BK == 0 && transposed_stride == 1 && a.M > 0 && kh * kw <= 31) {
-        FastGeom fg{kh * kw, 0, 0, ct / BK, nullptr};
-        const long long tiles128 = (long long)cdiv(a.M, BM) * cdiv(a.N, BN);
-        const long long tiles64 = (long long)cdiv(a.M, 64) * cdiv(a.N, BN);
-        const int ksteps = a.K / BK;
-        // split-K when even the 64-row tiling leaves most of the 256 CUs x 3 slots empty
-        int ns = 1;
-        if (workspace && tiles64 <= 256 && a.M > 64 && cout % 4 == 0 && ldy % 4 == 0 && aligned16(y) &&
-            (!a.e.bias || aligned16(a.e.bias)) && (!a.e.rowbias || (aligned16(a.e.rowbias) && a.e.ld_rowbias % 4 == 0)) &&
-            (!a.e.res || (aligned16(a.e.res) && a.e.ldres % 4 == 0))) {
-            ns = (int)(768 / tiles64);
-            if (ns > 8) ns = 8;
-            if (ns > ksteps / 6) ns = ksteps / 6;
-            if ((long long)ns * a.M * a.N * (long long)sizeof(float) > ws_bytes) ns = 1;
-        }
-        if (ns >= 2) {
-            TileArgs p = a;
-            p.C = reinterpret_cast<float*>(workspace);
-            p.ldc = a.N;
-            p.c_stride_split = (long long)a.M * a.N;
-            p.nsplit = ns;
-            p.kper = cdiv(ksteps, ns) * BK;
-            p.e = make_epilogue(nullptr);
-            int st = launch_fast<OP_IM2COL, OP_KC, 64>(p, fg, 1, stream, "psld_conv2d_nhwc_f32[fast64,splitK]");
-            if (st != PSLD_OK) return st;
-            return psld_detail_conv_reduce_epilogue(p.C, ns, a.M, a.N, y, ldy, a.e, stream);
-        }
-        if (tiles128 <= 256 && a.M > 64)
-            return launch_fast<OP_IM2COL, OP_KC, 64>(a, fg, 1, stream, "psld_conv2d_nhwc_f32[fast64]");
-        return launch_fast<OP_IM2COL, OP_KC>(a, fg, 1, stream, "psld_conv2d_nhwc_f32[fast]");
+    TileArgs a, p;
+    FastGeom fg;
+    int form = 0;
+    if (int st = conv2d_setup(x1, c1, x2, c2, batch, ih, iw, w_ohwi, cout, kh, kw, stride, pad, transposed_stride, oh, ow, y, ldy,
+                              epi, workspace, ws_bytes, a, p, fg, form))
+        return st;
+    switch (form & PSLD_TILE_KIND_MASK) {
+    case PSLD_TILE_FAST64_SPLITK: {
+        int st = launch_fast<OP_IM2COL, OP_KC, 64>(p, fg, 1, stream, "psld_conv2d_nhwc_f32[fast64,splitK]");
+        if (st != PSLD_OK) return st;
+        return psld_detail_conv_reduce_epilogue(p.C, p.nsplit, a.M, a.N, y, ldy, a.e, stream);
     }
-    return launch<OP_IM2COL, OP_KC>(a, 1, stream, "psld_conv2d_nhwc_f32");
+    case PSLD_TILE_FAST64:
+        return launch_fast<OP_IM2COL, OP_KC, 64>(a, fg, 1, stream, "psld_conv2d_nhwc_f32[fast64]");
+    case PSLD_TILE_FAST128:
+    case PSLD_TILE_FAST256:
+        return launch_fast<OP_IM2COL, OP_KC>(a, fg, 1, stream, "psld_conv2d_nhwc_f32[fast]",
+                                             (form & PSLD_TILE_KIND_MASK) == PSLD_TILE_FAST256);
+    default:
+        return launch<OP_IM2COL, OP_KC>(a, 1, stream, "psld_conv2d_nhwc_f32");
+    }
 }
 
 extern "C" int psld_conv2d_nhwc_f32(const float* x1, int c1, const float* x2, int c2,
@@ -1007,28 +1142,31 @@ extern "C" int psld_conv2d_nhwc_f32(const float* x1, int c1, const float* x2, in
                                    oh, ow, y, ldy, epi, nullptr, 0, stream);
 }
 
+extern "C" int psld_conv2d_wgrad_plan(const float* dy, int lddy, int cout, const float* x, int cin, int batch, int ih, int iw,
+                                      int kh, int kw, int stride, int pad, int oh, int ow, const float* slabs, int cin_total,
+                                      int col0, int nsplit) {
+    TileArgs a;
+    FastGeom fg;
+    int form = 0;
+    if (conv2d_wgrad_setup(dy, lddy, cout, x, cin, batch, ih, iw, kh, kw, stride, pad, oh, ow, const_cast<float*>(slabs),
+                           cin_total, col0, nsplit, a, fg, form) != PSLD_OK)
+        return -1;
+    return form;
+}
+
 // dW slabs: slabs[s][cout][kh*kw][cin_total] restricted to columns [col0, col0+cin) for input x.
 extern "C" int psld_conv2d_wgrad_nhwc_f32(const float* dy, int lddy, int cout,
                                           const float* x, int cin, int batch, int ih, int iw,
                                           int kh, int kw, int stride, int pad, int oh, int ow,
                                           float* slabs, int cin_total, int col0, int nsplit,
                                           hipStream_t stream) {
-    PSLD_CHECK_ARG(dy && x && slabs && nsplit >= 1, "psld_conv2d_wgrad_nhwc_f32: bad args");
-    TileArgs a{};
-    a.M = cout; a.N = cin; a.K = batch * oh * ow;
-    a.A = {dy, nullptr, 0, lddy, aligned16(dy) && lddy % 4 == 0 && cout % 4 == 0};
-    a.B = {x, nullptr, 0, cin, aligned16(x) && cin % 4 == 0};
-    a.C = slabs + col0;
-    a.ldc = kh * kw * cin_total;
-    a.c_stride_z = cin_total;                                  // tap -> column block
-    a.c_stride_split = (long long)cout * kh * kw * cin_total;  // slab
-    a.nsplit = nsplit; a.kper = cdiv(cdiv(a.K, nsplit), BK) * BK;
-    a.g = {ih, iw, cin, 0, oh, ow, kh, kw, stride, pad, 1};
-    a.e = make_epilogue(nullptr);
-    const int ows = ilog2_exact(ow), ohs = ilog2_exact(oh);
-    if (a.A.vec && a.B.vec && ows >= 0 && ohs >= 0 && cout > 0 && cin > 0) {
-        FastGeom fg{kh * kw, ows, ohs, 0, nullptr};
+    TileArgs a;
+    FastGeom fg;
+    int form = 0;
+    if (int st = conv2d_wgrad_setup(dy, lddy, cout, x, cin, batch, ih, iw, kh, kw, stride, pad, oh, ow, slabs, cin_total, col0,
+                                    nsplit, a, fg, form))
+        return st;
+    if ((form & PSLD_TILE_KIND_MASK) == PSLD_TILE_FAST128)
         return launch_fast<OP_MC, OP_SHIFT>(a, fg, kh * kw, stream, "psld_conv2d_wgrad_nhwc_f32[fast]");
-    }
     return launch<OP_MC, OP_SHIFT>(a, kh * kw, stream, "psld_conv2d_wgrad_nhwc_f32");
 }

@@ -95,6 +95,18 @@ def gemm_raw(ta: int, tb: int, M: int, N: int, K: int, A: Tensor, lda: int, sa: 
                               C.byref(epi) if epi is not None else None, _stream()), "psld_gemm_f32")
 
 
+def gemm_plan(ta: int, tb: int, M: int, N: int, K: int, A: Tensor, lda: int, sa: int, B: Tensor, ldb: int,
+              sb: int, Cc: Tensor, ldc: int, sc: int, batch: int = 1, epi: Optional[Epilogue] = None,
+              a_off: int = 0, b_off: int = 0, c_off: int = 0) -> int:
+    """The form code (_lib.TILE_*) gemm_raw's launch takes for these arguments (psld_gemm_plan: host arithmetic on shapes and
+    pointer alignment - the tensors may live anywhere, nothing is read or launched)."""
+    form = lib().psld_gemm_plan(ta, tb, M, N, K, A.data_ptr() + 4 * a_off, lda, sa, B.data_ptr() + 4 * b_off, ldb, sb,
+                                Cc.data_ptr() + 4 * c_off, ldc, sc, batch, C.byref(epi) if epi is not None else None)
+    if form < 0:
+        check(1, "psld_gemm_plan")
+    return form
+
+
 def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """y[M,N] = x[M,K] w[N,K]^T + bias  (nn.Linear / 1x1 conv with OI weights)."""
     M, K = x.shape[0], x.shape[-1]
@@ -119,11 +131,38 @@ def gemm_tn_splitk(M: int, N: int, K: int, A: Tensor, lda: int, B: Tensor, ldb: 
                                         _stream()), "psld_gemm_tn_splitk_f32")
 
 
+def gemm_tn_splitk_plan(M: int, N: int, K: int, A: Tensor, lda: int, B: Tensor, ldb: int, slabs: Tensor, nsplit: int) -> int:
+    """The form code gemm_tn_splitk's launch takes (psld_gemm_tn_splitk_plan; host only)."""
+    form = lib().psld_gemm_tn_splitk_plan(M, N, K, A.data_ptr(), lda, B.data_ptr(), ldb, slabs.data_ptr(), nsplit)
+    if form < 0:
+        check(1, "psld_gemm_tn_splitk_plan")
+    return form
+
+
+def conv2d_plan(x1: Tensor, x2: Optional[Tensor], w_ohwi: Tensor, cout: int, kh: int, kw: int, stride: int, pad: int,
+                tstride: int, oh: int, ow: int, y: Tensor, epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
+    """(form code, K ranges, K values per range) of conv2d_nhwc's launch for these arguments (psld_conv2d_plan; host only:
+    the workspace conv2d_nhwc would pass is stood in for by its size and a non-null address)."""
+    b, ih, iw, c1 = x1.shape
+    c2 = x2.shape[-1] if x2 is not None else 0
+    ws, wsb = (256, int(lib().psld_conv2d_workspace_bytes(b, oh, ow, cout))) if b * oh * ow <= _CONV_WS_ROWS else (None, 0)
+    ns, kper = C.c_int(0), C.c_int(0)
+    form = lib().psld_conv2d_plan(x1.data_ptr(), c1, _p(x2), c2, b, ih, iw, w_ohwi.data_ptr(), cout, kh, kw, stride, pad,
+                                  tstride, oh, ow, y.data_ptr(), ldy if ldy is not None else cout,
+                                  C.byref(epi) if epi is not None else None, ws, wsb, C.byref(ns), C.byref(kper))
+    if form < 0:
+        check(1, "psld_conv2d_plan")
+    return form, ns.value, kper.value
+
+
+_CONV_WS_ROWS = 16384      # conv2d_nhwc hands a split-K workspace to launches of at most this many output rows
+
+
 def conv2d_nhwc(x1: Tensor, x2: Optional[Tensor], w_ohwi: Tensor, cout: int, kh: int, kw: int, stride: int, pad: int,
                 tstride: int, oh: int, ow: int, y: Tensor, epi: Optional[Epilogue] = None, ldy: Optional[int] = None):
     b, ih, iw, c1 = x1.shape
     c2 = x2.shape[-1] if x2 is not None else 0
-    ws, wsb = _small_grid_ws(b * oh * ow, 16384, lambda: lib().psld_conv2d_workspace_bytes(b, oh, ow, cout), x1.device)
+    ws, wsb = _small_grid_ws(b * oh * ow, _CONV_WS_ROWS, lambda: lib().psld_conv2d_workspace_bytes(b, oh, ow, cout), x1.device)
     check(lib().psld_conv2d_nhwc_ws_f32(x1.data_ptr(), c1, _p(x2), c2, b, ih, iw, w_ohwi.data_ptr(), cout, kh, kw,
                                         stride, pad, tstride, oh, ow, y.data_ptr(), ldy if ldy is not None else cout,
                                         C.byref(epi) if epi is not None else None, ws, wsb, _stream()),
@@ -872,11 +911,23 @@ def conv3x3_wgrad_wino_x3(dy: Tensor, cout: int, x: Tensor, dw: Tensor, x2: Opti
 
 
 def conv2d_wgrad_nhwc(dy: Tensor, cout: int, x: Tensor, kh: int, kw: int, stride: int, pad: int, oh: int, ow: int,
-                      slabs: Tensor, cin_total: int, col0: int, nsplit: int):
+                      slabs: Tensor, cin_total: int, col0: int, nsplit: int, lddy: Optional[int] = None):
+    """``lddy``: row stride of dy in floats (default cout: dense rows)."""
     b, ih, iw, cin = x.shape
-    check(lib().psld_conv2d_wgrad_nhwc_f32(dy.data_ptr(), cout, cout, x.data_ptr(), cin, b, ih, iw, kh, kw, stride,
-                                           pad, oh, ow, slabs.data_ptr(), cin_total, col0, nsplit, _stream()),
+    check(lib().psld_conv2d_wgrad_nhwc_f32(dy.data_ptr(), lddy if lddy is not None else cout, cout, x.data_ptr(), cin, b, ih, iw,
+                                           kh, kw, stride, pad, oh, ow, slabs.data_ptr(), cin_total, col0, nsplit, _stream()),
           "psld_conv2d_wgrad_nhwc_f32")
+
+
+def conv2d_wgrad_plan(dy: Tensor, cout: int, x: Tensor, kh: int, kw: int, stride: int, pad: int, oh: int, ow: int,
+                      slabs: Tensor, cin_total: int, col0: int, nsplit: int, lddy: Optional[int] = None) -> int:
+    """The form code conv2d_wgrad_nhwc's launch takes (psld_conv2d_wgrad_plan; host only)."""
+    b, ih, iw, cin = x.shape
+    form = lib().psld_conv2d_wgrad_plan(dy.data_ptr(), lddy if lddy is not None else cout, cout, x.data_ptr(), cin, b, ih, iw,
+                                        kh, kw, stride, pad, oh, ow, slabs.data_ptr(), cin_total, col0, nsplit)
+    if form < 0:
+        check(1, "psld_conv2d_wgrad_plan")
+    return form
 
 
 def reduce_slabs(slabs: Tensor, nsplit: int, n: int, out: Tensor, layout: int = 0, cout: int = 0, taps: int = 0,
