@@ -228,6 +228,31 @@ def record_f16() -> bool:
     return bool(lib().psld_get_record_f16())
 
 
+# ---- the arithmetic of a limb launch ------------------------------------------------------------------------------------------
+# 'x6': three bf16 limbs per operand, six products (fp32-equivalent); 'x3': two limbs, three products; 'f16': one fp16 product (NOT
+# fp32-equivalent).  The suffix names a family's front-end (conv3x3_wino_x3), a derived weight's cache tag and its batch family.
+ARITHS = ("x6", "x3", "f16")
+ARITH_SUFFIX = {"x6": "", "x3": "_x3", "f16": "_f16"}
+
+
+def pass_arith(record: bool) -> tuple:
+    """The preference ladder over ARITHS of a pass that records a backward pass (``record``) or of one that does not: most
+    preferred first, ending in 'x6'; () under math mode 'f32' (no limb kernels).  The ONE place that reads the four settings
+    for dispatch; a launch site takes the first rung it has a form for (score_tape._ExecBase: a_wino, a_wgrad, pw_arith).
+        recording nothing:   'f16' if eval math is 'f16';  then 'x3' if the math mode is 'bf16x3';  then 'x6'
+        recording:           'f16' if record math is 'bf16x3' and record f16 is on;  then 'x3' if record math is 'bf16x3';  then 'x6'
+                             (record f16 without record math 'bf16x3' has no effect; the math mode only has to be a limb mode)"""
+    mode = math_mode()
+    if mode == "f32":
+        return ()
+    if record:
+        x3 = record_math() == "bf16x3"
+        f16 = x3 and record_f16()
+    else:
+        x3, f16 = mode == "bf16x3", eval_math() == "f16"
+    return (("f16",) if f16 else ()) + (("x3",) if x3 else ()) + ("x6",)
+
+
 # ---- gradient shift of record f16 ---------------------------------------------------------------------------------------------
 # Gradients of a mean-reduced loss enter the network at ~2/N - fp16 subnormals or zero at training sizes.  The fp16 data-gradient
 # launches multiply dy by 2^s before their one rounding and fold 2^-s into alpha (exact: the rounding stays the only error).  s is a

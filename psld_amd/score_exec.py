@@ -322,10 +322,8 @@ class _Exec(_ExecBase):
         cin = c1 + xb.v.shape[-1]
         wino = routes[0] == R.WINO
         # [cin/128 tiles][...]: data gradient of the 3x3 (Winograd fragments carry read-ahead padding at the end)
-        f16 = wino and self.f16r    # record f16: one fp16 plane, sliced the same way, launched with the pass's operand shift
-        x3 = wino and self.x3 and not f16       # record math 'bf16x3': two-limb fragments, sliced the same way
-        f3 = net._wfrag_f16(mod.Conv_0, True) if f16 else net._wfrag_x3(mod.Conv_0, True) if x3 else \
-            net._wfrag(mod.Conv_0, True) if wino else net._frag(mod.Conv_0, True)
+        a = self.a_wino if wino else "x6"       # two-limb / fp16 fragments are sliced the same way
+        f3 = net._wfrag(mod.Conv_0, True, a) if wino else net._frag(mod.Conv_0, True)
         cut3 = (f3.numel() - (R.WINO_FRAG_PAD_BYTES if wino else 0)) * c1 // cin
         gam, bet = gn0.weight.detach(), gn0.bias.detach()
         dgam, dbet = self.g(gn0.weight), self.g(gn0.bias)
@@ -335,12 +333,8 @@ class _Exec(_ExecBase):
             xg, acc = _gbuf(node)
             self.pw_dgrad(R.LIMB, dout, m, w2, xg, ops.epilogue(alpha=s, accumulate=acc), cols=(lo, hi))
             da0 = torch.empty_like(node.v)
-            if route == R.WINO and f16:
-                ops.conv3x3_wino_f16s(dh1, None, fr3, c, da0, self.gshift, allow_split=True)
-            elif route == R.WINO and x3:
-                ops.conv3x3_wino_x3(dh1, None, fr3, c, da0, allow_split=True)
-            elif route == R.WINO:
-                ops.conv3x3_wino(dh1, None, fr3, c, da0, allow_split=True)
+            if route == R.WINO:
+                self.wino_dgrad(dh1, fr3, c, da0)
             else:
                 ops.conv3x3_split(dh1, None, fr3, c, da0)
             self.gn_backward(da0, node.v, st, gam[lo:hi], bet[lo:hi], dgam[lo:hi], dbet[lo:hi], True, xg,

@@ -35,10 +35,12 @@ from .score_modules import (NIN, AttnBlockpp, Downsample, GaussianFourierProject
                             _Affine, _conv, _groupnorm, _linear, default_init)
 from .score_routes import _pick_nsplit  # noqa: F401  (tests / tools import it from here)
 from .score_tape import _SLAB_FLUSH_BYTES, _CatNode, _Node  # noqa: F401
-from .score_weights import (_frag_entry, _packed_entry, _pfrag_entry, _qkv_entry, _temb_entry, _wfrag_f16_entry, _wfrag_x3_entry, pfrag_tail)
+from .score_weights import _frag_entry, _packed_entry, _pfrag_entry, _qkv_entry, _temb_entry, pfrag_tail
 from .weight_cache import Entry, WeightCache
 
 Tensor = torch.Tensor
+# arith -> (forward tag, data-gradient tag) of NCSNpp._wfrag: the three-limb pair predates the suffix scheme
+_WFRAG_TAG = {a: ("wfrag" + sfx, "wfrag_d" + sfx) if sfx else ("wfrag", "dwfrag") for a, sfx in ops.ARITH_SUFFIX.items()}
 _ALIGN = 64  # floats: every parameter starts on a 256-byte boundary inside the flat buffers
 
 
@@ -379,30 +381,23 @@ class NCSNpp(nn.Module):
         """bf16 limb fragments of a 3x3 weight (ops.conv3x3_frag)."""
         return self._wcache.get(conv.weight, "dfrag" if dgrad else "frag", _frag_entry, dgrad, False)
 
-    def _wfrag(self, conv: _Affine, dgrad: bool) -> Tensor:
-        """Winograd-transformed bf16 limb fragments of a 3x3 weight (ops.conv3x3_wino_frag)."""
-        return self._wcache.get(conv.weight, "dwfrag" if dgrad else "wfrag", _frag_entry, dgrad, True)
-
-    def _wfrag_x3(self, conv: _Affine, dgrad: bool = False) -> Tensor:
-        """Two-limb Winograd fragments of a 3x3 weight (ops.conv3x3_wino_frag_x3 / conv3x3_wino_dgrad_frag_x3)."""
-        return self._wcache.get(conv.weight, "wfrag_d_x3" if dgrad else "wfrag_x3", _wfrag_x3_entry, dgrad)
-
-    def _wfrag_f16(self, conv: _Affine, dgrad: bool = False) -> Tensor:
-        """One-plane fp16 Winograd fragments of a 3x3 weight (ops.conv3x3_wino_frag_f16: eval math 'f16', record f16;
-        ``dgrad``: ops.conv3x3_wino_dgrad_frag_f16, record f16's data gradient)."""
-        return self._wcache.get(conv.weight, "wfrag_d_f16" if dgrad else "wfrag_f16", _wfrag_f16_entry, dgrad)
+    def _wfrag(self, conv: _Affine, dgrad: bool = False, arith: str = "x6") -> Tensor:
+        """Winograd-transformed fragments of a 3x3 weight (ops.conv3x3_wino_frag) in ``arith``: tags "wfrag" / "dwfrag", and
+        "wfrag_x3" / "wfrag_d_x3", "wfrag_f16" / "wfrag_d_f16"."""
+        return self._wcache.get(conv.weight, _WFRAG_TAG[arith][dgrad], _frag_entry, dgrad, True, arith)
 
     def _pfrag(self, owner: nn.Parameter, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor] = None,
-               chunk0: int = 0, chunks_total: int = 0, n0: int = 0, n_total: int = 0) -> Tensor:
+               chunk0: int = 0, chunks_total: int = 0, n0: int = 0, n_total: int = 0, arith: str = "x6") -> Tensor:
         """Limb fragments (ops.gemm_frag) of the [n][k] view of ONE parameter (element (i, j) at i*sn + j*sk), refreshed
         together with the 3x3 fragments by the batched launch.  ``into``: the buffer to fill (several parameters that
         share one fragment set: q | k | v) - then ``chunk0`` / ``chunks_total`` place this parameter's K range inside the
-        set's K dimension (psld_pack_frag_batch).  A ``tag`` ending in ``_x3``: two-limb fragments (ops.gemm_frag_x3), in ``_f16``:
-        one fp16 plane (ops.gemm_frag_f16).
+        set's K dimension (psld_pack_frag_batch).  ``arith``: the fragments' form; the entry's tag is ``tag`` with its suffix
+        ("fwd_x3", "qkv_d_f16", ...).
         A set that is no whole number of 128 x 64 tiles (score_weights.pfrag_tail: channel widths in steps of 32) is packed
         as padded three-limb tail fragments (ops.gemm_frag_tail); ``n0`` / ``n_total`` then place the parameter's rows
         inside a shared set's N dimension."""
-        return self._wcache.get(owner, tag, _pfrag_entry, tag, n, k, sn, sk, into, chunk0, chunks_total, n0, n_total)
+        return self._wcache.get(owner, tag + ops.ARITH_SUFFIX[arith], _pfrag_entry, tag, arith, n, k, sn, sk, into, chunk0,
+                                chunks_total, n0, n_total)
 
     def _qkv_frags(self, mod):
         """Fragments of an attention block's q | k | v projections as ONE GEMM operand each way - forward B[n][k] =
@@ -428,29 +423,20 @@ class NCSNpp(nn.Module):
         return self._wcache.fresh(e)
 
     def _qkv_frags_x3(self, mod, dgrad: bool = False, f16: bool = False):
-        """The forward (``dgrad``: data-gradient) q | k | v fragment set of _qkv_frags in two-limb form (math mode / record
-        math 'bf16x3'; whole-tile sets only: c % 128 == 0).  ``f16``: the set as one fp16 plane (eval math 'f16', record f16)."""
-        n0 = mod.NIN_0
+        """The forward (``dgrad``: data-gradient) q | k | v fragment set of _qkv_frags in a reduced arithmetic: two limbs, or
+        (``f16``) one fp16 plane (whole-tile sets only: c % 128 == 0)."""
+        arith = "f16" if f16 else "x3"
+        n0, sfx = mod.NIN_0, ops.ARITH_SUFFIX[arith]
         c = n0.W.shape[0]
-        if f16:
-            fb = ops.gemm_frag_bytes_f16(c, c)
-            pf = self._wcache.entry(n0.W, "qkv_set_d_f16" if dgrad else "qkv_set_f16", lambda w: Entry(
-                w, out=torch.empty(3 * fb, dtype=torch.uint8, device=w.device), build=lambda prev: prev)).out
-            for i, nin in enumerate((n0, mod.NIN_1, mod.NIN_2)):
-                if dgrad:       # concatenated along K, as in _qkv_frags
-                    self._pfrag(nin.W, "qkv_d_f16", c, c, c, 1, into=pf, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
-                else:
-                    self._pfrag(nin.W, "qkv_f_f16", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
-            return pf
-        fb = ops.gemm_frag_bytes_x3(c, c)
-        # the holder of the shared buffer (no family: the "qkv_d_x3" / "qkv_f_x3" entries of the three projections fill it)
-        pf = self._wcache.entry(n0.W, "qkv_set_d_x3" if dgrad else "qkv_set_x3", lambda w: Entry(
+        fb = ops.gemm_frag_bytes_f16(c, c) if f16 else ops.gemm_frag_bytes_x3(c, c)
+        # the holder of the shared buffer (no family: the "qkv_d" / "qkv_f" entries of the three projections fill it)
+        pf = self._wcache.entry(n0.W, ("qkv_set_d" if dgrad else "qkv_set") + sfx, lambda w: Entry(
             w, out=torch.empty(3 * fb, dtype=torch.uint8, device=w.device), build=lambda prev: prev)).out
         for i, nin in enumerate((n0, mod.NIN_1, mod.NIN_2)):
             if dgrad:       # concatenated along K, as in _qkv_frags
-                self._pfrag(nin.W, "qkv_d_x3", c, c, c, 1, into=pf, chunk0=i * (c // 32), chunks_total=3 * (c // 32))
+                self._pfrag(nin.W, "qkv_d", c, c, c, 1, into=pf, chunk0=i * (c // 32), chunks_total=3 * (c // 32), arith=arith)
             else:
-                self._pfrag(nin.W, "qkv_f_x3", c, c, 1, c, into=pf[i * fb:(i + 1) * fb])
+                self._pfrag(nin.W, "qkv_f", c, c, 1, c, into=pf[i * fb:(i + 1) * fb], arith=arith)
         return pf
 
     def _temb_plan(self):
@@ -604,7 +590,7 @@ class NCSNpp(nn.Module):
             self._graphs = {}
 
     def _graph_forward(self, x: Tensor, t: Tensor) -> Tensor:
-        key = (tuple(x.shape), x.device.index, ops.math_mode(), ops.eval_math())     # a capture replays the launches of its math mode and eval math
+        key = (tuple(x.shape), x.device.index, ops.pass_arith(False))     # a capture replays the launches of its arithmetic
         ent = self._graphs.get(key)
         if ent is None:
             sx, st = x.clone(), t.clone()

@@ -100,24 +100,20 @@ class _ExecBase:
         self.side_queue = []        # (fn, tensors) waiting for the next fork
         self.side_group = net.side_group
         self.want_dx = False        # gradient w.r.t. the network input requested (x.requires_grad)
-        mode = ops.math_mode()
-        self.split = mode in ("bf16x6", "bf16x3")   # 3x3 convs on the bf16 limb kernels (csrc/conv_split.hip)
-        # 'bf16x3' (reduced-precision inference): a forward that records no backward pass runs the two-limb form of every
-        # Winograd-forward / pointwise-forward launch that has one; a recording pass is the 'bf16x6' one, launch for launch -
-        # unless record math 'bf16x3' (ops.set_record_math, opt-in) asks for two limbs there as well: then, under either limb
-        # math mode, its forward launches, its Winograd / pointwise data gradients and its Winograd-domain weight gradients are
-        # the two-limb ones (direct limb 3x3 kernels, pointwise / NIN weight gradients and attention products have no such form)
-        self.x3 = (mode == "bf16x3" and not record) or (record and self.split and ops.record_math() == "bf16x3")
-        # eval math 'f16' (ops.set_eval_math, opt-in; PSLD_MATH=f16 sets it together with math mode 'bf16x3'): a forward that
-        # records no backward pass runs the one-product fp16 form of the Winograd-forward and eight-wave pointwise launches;
-        # everything else, and every recording pass, runs as without it.  NOT fp32-equivalent (~1e-3 rel-L2: DESIGN 4b''')
-        self.f16 = self.split and not record and ops.eval_math() == "f16"
-        # record f16 (ops.set_record_f16, opt-in; PSLD_MATH=f16_train): a recording pass under record math 'bf16x3' takes the
-        # one-product fp16 launch where one exists - Winograd forward and data gradient, eight-wave pointwise forward and data
-        # gradient - and stays on two limbs elsewhere (every weight gradient, LIMB_TAIL, direct limb 3x3, attention products,
-        # the tile engine, launches below 128 tiles).  The data gradients shift dy by 2^gshift before their one rounding
-        # (ops.take_grad_shift, read once when the backward pass starts).  Reference-GPU-equivalent, NOT fp32-equivalent
-        self.f16r = record and self.split and ops.record_math() == "bf16x3" and ops.record_f16()
+        # this pass's arithmetic, most preferred first (ops.pass_arith: the one reader of math mode, record math, eval math and
+        # record f16).  A launch site takes the first rung it has a form for (pick):
+        #   Winograd forward, GroupNorm-fused forward                'f16', 'x3', 'x6'
+        #   Winograd data gradient                                   'f16' with the pass's operand shift, 'x3', 'x6'
+        #   Winograd-domain weight gradient                          'x3', 'x6'
+        #   LIMB pointwise forward / data gradient                   'f16' / 'x3' where its gemm_split_*_wanted holds, else 'x6'
+        #                                                            (the data gradient's 'f16' form carries the shift)
+        #   everything else (LIMB_TAIL, direct limb 3x3, attention products, tile engine, NIN / pointwise weight gradients)  'x6'
+        # 'x3' and 'f16' are NOT fp32-equivalent; the forward of a recording fp16 pass is unshifted
+        self.arith = ops.pass_arith(record)
+        self.split = bool(self.arith)       # a limb math mode: the bf16 limb kernels (csrc/conv_split.hip) where a route names them
+        # the sites without a policy, resolved once for the pass
+        self.a_wino = self.pick(ops.ARITHS)
+        self.a_wgrad = self.pick(("x3", "x6"))
         self.gshift = 0
         self.limb_planes = os.environ.get("PSLD_LIMB_PLANES", "1") != "0"    # A/B switch for tools/bench_sample.py
         # forward attention in one kernel (attention.hip) wherever it takes the shape (B=128: 8x8 maps 17 vs 54 us of the
@@ -339,7 +335,8 @@ class _ExecBase:
             # Winograd domain (wgrad_wino.hip): 16 limb products per 2x2 tile instead of 36; its own slabs and reduction
             # (G^T . G over 16 positions), written straight into the flat gradient
             # (the stream's workspace: the reduction follows at once, nothing is parked in the slab arena)
-            (ops.conv3x3_wgrad_wino_x3 if self.x3 else ops.conv3x3_wgrad_wino)(dy, cout, x, self.g(conv.weight), x2=x2, alpha=alpha)
+            launch = ops.conv3x3_wgrad_wino_x3 if self.a_wgrad == "x3" else ops.conv3x3_wgrad_wino
+            launch(dy, cout, x, self.g(conv.weight), x2=x2, alpha=alpha)
             return
         if route == R.LIMB:
             nsplit = R.wgrad_limb_nsplit(cout, cin, b, oh, ow, isinstance(x, ops.LimbPlanes))
@@ -405,6 +402,26 @@ class _ExecBase:
         ops.colsum(tmp, c, 1, b, c, out, alpha)
         return tmp
 
+    def pick(self, forms) -> str:
+        """The first rung of the pass's ladder among the ``forms`` a site has ('x6' under math mode 'f32', where none is used)."""
+        return next((a for a in self.arith if a in forms), "x6")
+
+    def pw_arith(self, k1: int, k2: int, m: int, n: int) -> str:
+        """The arithmetic of a LIMB pointwise launch [m][k1 + k2] -> [m][n]: the first reduced rung whose policy wants it."""
+        for a in self.arith:
+            if (a == "f16" and ops.gemm_split_f16_wanted(k1, k2, m, n)) or (a == "x3" and ops.gemm_split_x3_wanted(k1, k2, m, n)):
+                return a
+        return "x6"
+
+    def wino_dgrad(self, dy: Tensor, frag: Tensor, cin: int, out: Tensor, epi=None):
+        """A Winograd data-gradient launch on fragments in the pass's arithmetic; the fp16 form carries its operand shift."""
+        if self.a_wino == "f16":
+            ops.conv3x3_wino_f16s(dy, None, frag, cin, out, self.gshift, epi, allow_split=True)
+        elif self.a_wino == "x3":
+            ops.conv3x3_wino_x3(dy, None, frag, cin, out, epi, allow_split=True)
+        else:
+            ops.conv3x3_wino(dy, None, frag, cin, out, epi, allow_split=True)
+
     def wino_wanted(self, c1: int, c2: int, b: int, h: int, w: int, cout: int) -> bool:
         """The ONE place the executor asks whether a convolution runs in Winograd form (score_routes.wino_wanted): every
         route lookup and block plan of this executor receives this method."""
@@ -419,12 +436,9 @@ class _ExecBase:
         if route is None:
             route = R.conv3_route(self.split, c, c2, b, h, w, cout, isinstance(x, ops.LimbPlanes), self.wino_wanted)
         if route == R.WINO:
-            if self.f16 or self.f16r:
-                ops.conv3x3_wino_f16(x, x2, self.net._wfrag_f16(conv), cout, out, epi, allow_split=True)
-            elif self.x3:
-                ops.conv3x3_wino_x3(x, x2, self.net._wfrag_x3(conv), cout, out, epi, allow_split=True)
-            else:
-                ops.conv3x3_wino(x, x2, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)   # Winograd F(2x2, 3x3)
+            a = self.a_wino
+            launch = ops.conv3x3_wino_f16 if a == "f16" else ops.conv3x3_wino_x3 if a == "x3" else ops.conv3x3_wino
+            launch(x, x2, self.net._wfrag(conv, False, a), cout, out, epi, allow_split=True)      # Winograd F(2x2, 3x3)
         elif route == R.LIMB:
             ops.conv3x3_split(x, x2, self.net._frag(conv, False), cout, out, epi)
         else:
@@ -433,27 +447,22 @@ class _ExecBase:
     def conv3_gn(self, x: Tensor, st, x2: Optional[Tensor], st2, conv: _Affine, out: Tensor, epi):
         """SiLU(GroupNorm(.)) + 3x3 convolution in one launch (ops.conv3x3_wino_gn; inference forward only)."""
         cout = conv.weight.shape[0]
-        if self.f16:
-            ops.conv3x3_wino_gn_f16(x, st, x2, st2, True, self.net._wfrag_f16(conv), cout, out, epi, allow_split=True)
-        elif self.x3:
-            ops.conv3x3_wino_gn_x3(x, st, x2, st2, True, self.net._wfrag_x3(conv), cout, out, epi, allow_split=True)
-        else:
-            ops.conv3x3_wino_gn(x, st, x2, st2, True, self.net._wfrag(conv, False), cout, out, epi, allow_split=True)
+        a = self.a_wino
+        launch = ops.conv3x3_wino_gn_f16 if a == "f16" else ops.conv3x3_wino_gn_x3 if a == "x3" else ops.conv3x3_wino_gn
+        launch(x, st, x2, st2, True, self.net._wfrag(conv, False, a), cout, out, epi, allow_split=True)
 
     # -- pointwise GEMMs (1x1 shortcuts, NIN projections, the pyramid's im2col GEMM) on a score_routes.pointwise_* route ------
     def pw_fwd(self, route: str, a1: Tensor, a2: Optional[Tensor], m: int, w: PointwiseWeight, y: Tensor, epi):
-        """y[m][w.n] = epi([a1 | a2] W^T).  LIMB runs the fp16 form where eval math 'f16' (a recording pass: record f16), else the
-        two-limb form where math mode 'bf16x3', wants it (LIMB_TAIL has neither);
+        """y[m][w.n] = epi([a1 | a2] W^T).  LIMB runs the first reduced form of the pass's ladder that its policy (pw_arith)
+        wants, else three limbs (LIMB_TAIL has three limbs only);
         TILE is the tile engine's 1x1 convolution for an "oi" weight (it alone takes a second source), its GEMM for NIN."""
         n = w.n
         if route == R.LIMB_TAIL:
             ops.gemm_split_tail(a1, m, w.frag(tail=True), n, y, epi)
-        elif route == R.LIMB and (self.f16 or self.f16r) and ops.gemm_split_f16_wanted(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n):
-            ops.gemm_split_f16(a1, a2, m, w.frag(f16=True), n, y, epi)
-        elif route == R.LIMB and self.x3 and ops.gemm_split_x3_wanted(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n):
-            ops.gemm_split_x3(a1, a2, m, w.frag(x3=True), n, y, epi)
         elif route == R.LIMB:
-            ops.gemm_split(a1, a2, m, w.frag(), n, y, epi)
+            a = self.pw_arith(a1.shape[-1], a2.shape[-1] if a2 is not None else 0, m, n)
+            launch = ops.gemm_split_f16 if a == "f16" else ops.gemm_split_x3 if a == "x3" else ops.gemm_split
+            launch(a1, a2, m, w.frag(arith=a), n, y, epi)
         elif w.kind == "oi":
             ops.conv2d_nhwc(a1, a2, w.w, n, 1, 1, 1, 0, 1, a1.shape[1], a1.shape[2], y, epi)
         else:
@@ -463,23 +472,21 @@ class _ExecBase:
     def pw_dgrad(self, route: str, dy: Tensor, m: int, w: PointwiseWeight, dx: Tensor, epi=None, cols=None):
         """dx[m][w.k] = epi(dy[m][w.n] W).  ``cols`` = (lo, hi), limb routes: input channels lo .. hi alone, into a dx that wide
         (one source of an unmaterialised concatenation: a data gradient's fragments are ordered by output-channel tile, so a
-        source's share is a contiguous slice of them).  LIMB runs the two-limb form where a recording pass under record math
-        'bf16x3' wants it (the policy of pw_fwd, on the launch's own width) - under record f16 the fp16 form with the pass's
-        operand shift."""
+        source's share is a contiguous slice of them).  LIMB: the arithmetic by the policy of pw_fwd, on the launch's own width;
+        the fp16 form with the pass's operand shift."""
         n = w.k
         if route == R.TILE:
             wt, tb, ld = w.tile(True)
             return ops.gemm_raw(0, tb, m, n, w.n, dy, w.n, 0, wt, ld, 0, dx, n, 0, epi=epi)
-        f16 = route == R.LIMB and self.f16r and ops.gemm_split_f16_wanted(w.n, 0, m, n if cols is None else cols[1] - cols[0])
-        x3 = not f16 and route == R.LIMB and self.x3 and ops.gemm_split_x3_wanted(w.n, 0, m, n if cols is None else cols[1] - cols[0])
-        frag = w.frag(True, x3=x3, tail=route == R.LIMB_TAIL, f16=f16)
+        a = self.pw_arith(w.n, 0, m, n if cols is None else cols[1] - cols[0]) if route == R.LIMB else "x6"
+        frag = w.frag(True, a, tail=route == R.LIMB_TAIL)
         if cols is not None:
             frag, n = frag[frag.numel() * cols[0] // n:frag.numel() * cols[1] // n], cols[1] - cols[0]
         if route == R.LIMB_TAIL:
             ops.gemm_split_tail(dy, m, frag, n, dx, epi)
-        elif f16:
+        elif a == "f16":        # a data gradient's fp16 form carries the pass's operand shift
             ops.gemm_split_f16s(dy, None, m, frag, n, dx, self.gshift, epi)
-        elif x3:
+        elif a == "x3":
             ops.gemm_split_x3(dy, None, m, frag, n, dx, epi)
         else:
             ops.gemm_split(dy, None, m, frag, n, dx, epi)
@@ -568,12 +575,7 @@ class _ExecBase:
         if route is None and (k, stride, pad) == (3, 1, 1):
             route = R.conv3_route(self.split, dy.shape[-1], 0, dy.shape[0], ih, iw, cin, wino=self.wino_wanted)
         if route == R.WINO:
-            if self.f16r:
-                ops.conv3x3_wino_f16s(dy, None, self.net._wfrag_f16(conv, True), cin, out, self.gshift, epi, allow_split=True)
-            elif self.x3:
-                ops.conv3x3_wino_x3(dy, None, self.net._wfrag_x3(conv, True), cin, out, epi, allow_split=True)
-            else:
-                ops.conv3x3_wino(dy, None, self.net._wfrag(conv, True), cin, out, epi, allow_split=True)     # Winograd F(2x2, 3x3)
+            self.wino_dgrad(dy, self.net._wfrag(conv, True, self.a_wino), cin, out, epi)        # Winograd F(2x2, 3x3)
             return
         if route == R.LIMB:
             ops.conv3x3_split(dy, None, self.net._frag(conv, True), cin, out, epi)
@@ -600,7 +602,7 @@ class _ExecBase:
         net = self.net
         # the operand shift of this pass's fp16 data gradients: a host integer from the divisor the loss published (consumed here)
         shift = ops.take_grad_shift()
-        self.gshift = shift if self.f16r else 0
+        self.gshift = shift if "f16" in self.arith else 0
         g_out = grad_out_nchw.contiguous()
         self.head_grad.g = g_out if net.is_classifier else ops.nchw_to_nhwc(g_out)
         # every pass: gn_backward and the resblock column sums allocate from the arena whether or not the reductions are

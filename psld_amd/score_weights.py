@@ -23,27 +23,26 @@ def _packed_entry(w: Tensor, dgrad: bool) -> Entry:
     return Entry(w, build=build, graph=not dgrad)
 
 
-def _frag_entry(w: Tensor, dgrad: bool, wino: bool) -> Entry:
-    pack, row = (ops.conv3x3_wino_frag, ops.conv3x3_wino_frag_entry) if wino else \
-        (ops.conv3x3_frag, ops.conv3x3_frag_entry)
-    return Entry(w, build=lambda prev: pack(w.detach(), dgrad, prev), family="wino" if wino else "limb",
+def _frag_entry(w: Tensor, dgrad: bool, wino: bool, arith: str = "x6") -> Entry:
+    """Fragments of a 3x3 weight for the direct limb kernels (three limbs only) or in Winograd form (any arithmetic)."""
+    row = ops.conv3x3_wino_frag_entry if wino else ops.conv3x3_frag_entry
+
+    def build(prev):
+        if not wino:
+            return ops.conv3x3_frag(w.detach(), dgrad, prev)
+        if arith == "x3":
+            return (ops.conv3x3_wino_dgrad_frag_x3 if dgrad else ops.conv3x3_wino_frag_x3)(w.detach(), prev)
+        if arith == "f16":
+            return (ops.conv3x3_wino_dgrad_frag_f16 if dgrad else ops.conv3x3_wino_frag_f16)(w.detach(), prev)
+        return ops.conv3x3_wino_frag(w.detach(), dgrad, prev)
+    return Entry(w, build=build, family=("wino" if wino else "limb") + ops.ARITH_SUFFIX[arith],
                  rows=lambda out: [(row(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
 
 
-def _wfrag_x3_entry(w: Tensor, dgrad: bool = False) -> Entry:
-    """Two-limb Winograd fragments: the 'wino' entries' siblings for math mode 'bf16x3' (forward orientation) and record math
-    'bf16x3' (both orientations)."""
-    pack = ops.conv3x3_wino_dgrad_frag_x3 if dgrad else ops.conv3x3_wino_frag_x3
-    return Entry(w, build=lambda prev: pack(w.detach(), prev), family="wino_x3",
-                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
-
-
-def _wfrag_f16_entry(w: Tensor, dgrad: bool = False) -> Entry:
-    """One-plane fp16 Winograd fragments: the 'wino' entries' siblings for eval math 'f16' (forward orientation) and record
-    f16 (both orientations)."""
-    pack = ops.conv3x3_wino_dgrad_frag_f16 if dgrad else ops.conv3x3_wino_frag_f16
-    return Entry(w, build=lambda prev: pack(w.detach(), prev), family="wino_f16",
-                 rows=lambda out: [(ops.conv3x3_wino_frag_entry(w, dgrad, out), w.shape[0] * w.shape[1] // 8)], graph=not dgrad)
+def _pfrag_packers(arith: str):
+    """(packer of one pointwise fragment set, its batched form) in ``arith``."""
+    return {"x6": (ops.gemm_frag, ops.pack_frag_batch), "x3": (ops.gemm_frag_x3, ops.pack_frag_batch_x3),
+            "f16": (ops.gemm_frag_f16, ops.pack_frag_batch_f16)}[arith]
 
 
 def pfrag_tail(n: int, k: int, n_total: int = 0, chunks_total: int = 0) -> bool:
@@ -67,14 +66,13 @@ def _pfrag_tail_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, int
     return Entry(p, build=build, family="limb_tail", rows=rows, graph=tag in ("fwd", "qkv_f"))
 
 
-def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor], chunk0: int,
+def _pfrag_entry(p: Tensor, tag: str, arith: str, n: int, k: int, sn: int, sk: int, into: Optional[Tensor], chunk0: int,
                  chunks_total: int, n0: int = 0, n_total: int = 0) -> Entry:
+    """``tag``: the cache tag without the arithmetic's suffix; 'x3' / 'f16' (whole-tile sets only) have batch families of their own."""
     if pfrag_tail(n, k, n_total, chunks_total):
+        assert arith == "x6", arith
         return _pfrag_tail_entry(p, tag, n, k, sn, sk, into, chunk0, chunks_total, n0, n_total)
-    x3 = tag.endswith("_x3")        # two-limb fragments (math mode 'bf16x3'): their own packers and batch family
-    f16 = tag.endswith("_f16")      # one fp16 plane (eval math 'f16', record f16): likewise
-    pack, pack_batch = (ops.gemm_frag_x3, ops.pack_frag_batch_x3) if x3 else \
-        (ops.gemm_frag_f16, ops.pack_frag_batch_f16) if f16 else (ops.gemm_frag, ops.pack_frag_batch)
+    pack, pack_batch = _pfrag_packers(arith)
 
     def rows(out):
         return [([p.data_ptr(), out.data_ptr(), n, k | (chunk0 << 20) | (chunks_total << 40), 1, sn, sk], n * k // 8)]
@@ -86,8 +84,7 @@ def _pfrag_entry(p: Tensor, tag: str, n: int, k: int, sn: int, sk: int, into: Op
         (row, items), = rows(into)
         pack_batch(torch.tensor(row + [0], dtype=torch.int64, device=p.device), 1, items)
         return into
-    return Entry(p, build=build, family="limb_x3" if x3 else "limb_f16" if f16 else "limb", rows=rows,
-                 graph=tag in ("fwd", "qkv_f", "fwd_x3", "qkv_f_x3", "fwd_f16", "qkv_f_f16"))
+    return Entry(p, build=build, family="limb" + ops.ARITH_SUFFIX[arith], rows=rows, graph=tag in ("fwd", "qkv_f"))
 
 
 def _built_entry(owner: Tensor, build) -> Entry:
@@ -155,19 +152,18 @@ class PointwiseWeight(NamedTuple):
         oi = self.kind == "oi"
         return self.w, int(oi != dgrad), self.k if oi else self.n
 
-    def frag(self, dgrad: bool = False, x3: bool = False, tail: bool = False, f16: bool = False) -> Tensor:
-        """Three-limb (``x3``: two-limb, ``f16``: one fp16 plane - both whole-tile sets only) fragments of B[n][k], or of B[k][n]
-        for the data gradient."""
+    def frag(self, dgrad: bool = False, arith: str = "x6", tail: bool = False) -> Tensor:
+        """Fragments of B[n][k], or of B[k][n] for the data gradient, in ``arith`` ('x3' / 'f16': whole-tile sets only, so not with
+        ``tail``)."""
         net, w, kind = self.net, self.w, self.kind
         n, k = (self.k, self.n) if dgrad else (self.n, self.k)
-        assert not (f16 and (x3 or tail))
-        sfx = "_x3" if x3 else "_f16" if f16 else ""
+        assert not (tail and arith != "x6")
         if kind == "qkv":
-            return net._qkv_frags_x3(w, dgrad, f16) if x3 or f16 else self.qkv[int(dgrad)]
+            return net._qkv_frags_x3(w, dgrad, arith == "f16") if arith != "x6" else self.qkv[int(dgrad)]
         if kind == "ohwi":
-            pack = ops.gemm_frag_x3 if x3 else ops.gemm_frag_f16 if f16 else ops.gemm_frag_tail if tail else ops.gemm_frag
+            pack = ops.gemm_frag_tail if tail else _pfrag_packers(arith)[0]
             sn, sk = (1, n) if dgrad else (k, 1)
-            return net._wcache.get(w.weight, ("s2dgrad" if dgrad else "s2fwd") + sfx, _built_entry,
+            return net._wcache.get(w.weight, ("s2dgrad" if dgrad else "s2fwd") + ops.ARITH_SUFFIX[arith], _built_entry,
                                    lambda prev: pack(net._packed(w), n, k, sn, sk, prev))
         _, rows, ld = self.tile(dgrad)          # rows: B's rows are the stored matrix's rows
-        return net._pfrag(w, ("dgrad" if dgrad else "fwd") + sfx, n, k, *((ld, 1) if rows else (1, ld)))
+        return net._pfrag(w, "dgrad" if dgrad else "fwd", n, k, *((ld, 1) if rows else (1, ld)), arith=arith)

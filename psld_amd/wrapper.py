@@ -138,12 +138,11 @@ class SDEWrapper(_Base):
         net, optim, sde = self.score_fn, self.optimizers(), self.sde
         if not hasattr(self, "_graph_steps"):
             self._graph_steps = {}
-        # a capture replays its own launches: which ones a recording pass issues depends on the math mode (limb kernels or the
-        # fp32 tile engine), on the record math (three or two limbs) and on record f16 with its gradient shift (fp16 launches;
-        # the shift is a launch argument.  The automatic one follows from the batch shape and this wrapper's loss, so the
-        # setting itself - None or the forced value - is the key)
-        key = (tuple(batch.shape), batch.device.index, bool(net.training), ops.record_f16(), ops.grad_shift_setting(),
-               ops.math_mode(), ops.record_math())
+        # a capture replays its own launches: which ones a recording pass issues depends on its arithmetic (fp32 tile engine;
+        # three limbs, two, fp16) and, for the fp16 data gradients, on the gradient shift - a launch argument.  The automatic one
+        # follows from the batch shape and this wrapper's loss, so the setting itself - None or the forced value - is the key.
+        # (ops.pass_arith is the only reader of the math settings: two math modes with the same ladder replay the same capture)
+        key = (tuple(batch.shape), batch.device.index, bool(net.training), ops.pass_arith(True), ops.grad_shift_setting())
         ent = self._graph_steps.get(key)
         if ent is None:
             ent = self._graph_steps[key] = {"seen": 0}

@@ -9,6 +9,10 @@ the number of rows, the count per entry point and a SHA-256 of the rows of one e
 point, every integer and float argument, every epilogue field, and for pointers into the flat parameter / gradient buffer
 their element offset - which weight a launch reads, which gradient it writes.
 
+The cases that set record math, eval math, record f16 and a loss divisor were added the same way from commit 2d67725, before
+the executor's ``x3`` / ``f16`` / ``f16r`` booleans became ``ops.pass_arith``'s ladder; that run reproduced the digests of the
+eight older cases.
+
 A pull request that changes a launch on purpose regenerates the file and reviews ``--dump CASE`` against the parent's."""
 import collections
 import json
@@ -64,6 +68,18 @@ _WANTED = {
     "psld_conv3x3_wino_x3_f32": ("psld_conv3x3_wino_x3_f32", None),
     "psld_bgemm_split_f32": ("psld_bgemm_split_f32", None),
     "psld_attn_fwd_split_f32": ("psld_attn_fwd_split_f32", None),
+    # record math 'bf16x3', eval math 'f16', record f16 (the *_f16s rows carry the operand shift)
+    "psld_conv3x3_wino_f16_f32": ("psld_conv3x3_wino_f16_f32", None),
+    "psld_conv3x3_wino_f16s_f32": ("psld_conv3x3_wino_f16s_f32", None),
+    "psld_conv3x3_wino_gn_x3_f32": ("psld_conv3x3_wino_gn_x3_f32", None),
+    "psld_conv3x3_wino_gn_f16_f32": ("psld_conv3x3_wino_gn_f16_f32", None),
+    "psld_gemm_split_f16_f32": ("psld_gemm_split_f16_f32", None),
+    "psld_gemm_split_f16s_f32": ("psld_gemm_split_f16s_f32", None),
+    "psld_conv3x3_wgrad_wino_x3_f32": ("psld_conv3x3_wgrad_wino_x3_f32", None),
+    "psld_pack_conv3x3_wino_dgrad_x3": ("psld_pack_conv3x3_wino_dgrad_x3", None),
+    "psld_pack_conv3x3_wino_dgrad_f16": ("psld_pack_conv3x3_wino_dgrad_f16", None),
+    "psld_pack_frag_batch_x3": ("psld_pack_frag_batch_x3", None),
+    "psld_pack_frag_batch_f16": ("psld_pack_frag_batch_f16", None),
 }
 
 
@@ -80,6 +96,10 @@ def test_cases_cover_the_dispatch(monkeypatch):
     assert {s[0]["nf"] for s in specs} >= {32, 128, 160}
     assert {s[3] for s in specs} == {"residual", "none"}
     assert any(s[4] > 0 for s in specs) and {s[5] for s in specs} >= {0, 2}
+    assert {(s.record_math, s.eval_math, s.record_f16) for s in specs} >= {
+        ("bf16x6", "limb", False), ("bf16x3", "limb", False), ("bf16x6", "f16", False), ("bf16x3", "limb", True),
+        ("bf16x3", "f16", True)}
+    assert {s.divisor for s in specs if s.record_f16} >= {196608, 1000}        # operand shifts 18 and 10
     missing = [what for what, (names, cond) in _WANTED.items()
                if not any(cond is None or cond(r) for n in names.split() for r in by_name[n])]
     assert not missing, missing

@@ -568,7 +568,7 @@ def test_graph_captured_training_step_under_record_f16():
         runs.append((losses, net.flatten_parameters().clone(), ema.flatten_parameters().clone()))
         if graphs:
             keys = list(wr._graph_steps)
-            assert len(keys) == 2 and {k[4] for k in keys} == {None, 6} and all(k[3] is True for k in keys), keys
+            assert len(keys) == 2 and {k[4] for k in keys} == {None, 6} and all(k[3] == ("f16", "x3", "x6") for k in keys), keys
             assert all("graph" in e for e in wr._graph_steps.values())
     (la, pa, ea), (lb, pb, eb) = runs
     print("eager  losses", la)

@@ -277,7 +277,7 @@ def test_attention_block_backward_at_the_width_the_two_limb_set_takes(monkeypatc
     for record in ("bf16x6", "bf16x3"):
         with record_math(record):
             h, sd = _attention_harness(c)
-            assert h.ex.x3 == (record == "bf16x3")
+            assert ("x3" in h.ex.arith) == (record == "bf16x3")
             log = []
             for name in ("gemm_split", "gemm_split_x3"):
                 def rec(*a, _fn=getattr(o, name), _name=name, **k):
@@ -521,7 +521,7 @@ def test_tail_width_resblock_against_the_oracle_under_record_math():
         g = torch.Generator().manual_seed(5)
         x, temb = torch.randn(b, cin, hw, hw, generator=g), torch.randn(b, 128, generator=g)
         h = Harness(mod, sd)
-        assert h.ex.x3
+        assert "x3" in h.ex.arith
         h.set_temb(temb)
         xin = h.S._Node(x.permute(0, 2, 3, 1).contiguous().to(DEV))
         with h.ops.stream_scope():
@@ -647,7 +647,7 @@ def test_graph_captured_training_step_under_record_math():
         runs.append((losses, net.flatten_parameters().clone(), ema.flatten_parameters().clone()))
         if graphs:
             keys = list(wr._graph_steps)
-            assert len(keys) == 2 and {k[-1] for k in keys} == {"bf16x3", "bf16x6"}, keys
+            assert len(keys) == 2 and {k[3] for k in keys} == {("x3", "x6"), ("x6",)}, keys       # ops.pass_arith(True) of each
             assert all("graph" in e for e in wr._graph_steps.values())
     (la, pa, ea), (lb, pb, eb) = runs
     print("eager  losses", la)

@@ -28,17 +28,31 @@ if ROOT not in sys.path:
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "launch_trace.json")
 
-# name -> (C.tiny arguments, batch, math mode, progressive_input, dropout, set_winograd mode)
+class Case(collections.namedtuple("Case", "tiny batch mode pin dropout wino record_math eval_math record_f16 divisor",
+                                  defaults=("bf16x6", "limb", False, None))):
+    """C.tiny arguments, batch, math mode, progressive_input, dropout, set_winograd mode; then record math, eval math, record
+    f16 and the loss divisor published (``ops.set_loss_divisor``) right before the recorded backward (None: none)."""
+
+
+_B16 = (dict(nf=128, image_size=64), 16)
 CASES = {
-    "nf160_bf16x6": (dict(nf=160), 2, "bf16x6", "residual", 0.0, None),
-    "nf128_bf16x6": (dict(nf=128), 2, "bf16x6", "residual", 0.0, None),
-    "nf32_f32": (dict(nf=32), 2, "f32", "residual", 0.0, None),
-    "nf160_bf16x3": (dict(nf=160), 2, "bf16x3", "residual", 0.0, None),
-    "nf128_none_dropout_wino0": (dict(nf=128), 2, "bf16x6", "none", 0.1, 0),
-    "nf128_wino2": (dict(nf=128, ch_mult=(1, 1)), 2, "bf16x6", "residual", 0.0, 2),
+    "nf160_bf16x6": Case(dict(nf=160), 2, "bf16x6", "residual", 0.0, None),
+    "nf128_bf16x6": Case(dict(nf=128), 2, "bf16x6", "residual", 0.0, None),
+    "nf32_f32": Case(dict(nf=32), 2, "f32", "residual", 0.0, None),
+    "nf160_bf16x3": Case(dict(nf=160), 2, "bf16x3", "residual", 0.0, None),
+    "nf128_none_dropout_wino0": Case(dict(nf=128), 2, "bf16x6", "none", 0.1, 0),
+    "nf128_wino2": Case(dict(nf=128, ch_mult=(1, 1)), 2, "bf16x6", "residual", 0.0, 2),
     # full grids: the eight-wave two-limb GEMM (>= 128 tiles of 128 x 256), unsplit and GroupNorm-fused Winograd launches
-    "nf128_64px_b16_bf16x3": (dict(nf=128, image_size=64), 16, "bf16x3", "residual", 0.0, None),
-    "nf128_64px_b16_bf16x6": (dict(nf=128, image_size=64), 16, "bf16x6", "residual", 0.0, None),
+    "nf128_64px_b16_bf16x3": Case(*_B16, "bf16x3", "residual", 0.0, None),
+    "nf128_64px_b16_bf16x6": Case(*_B16, "bf16x6", "residual", 0.0, None),
+    # record math / eval math / record f16: two-limb weight and data gradients; every fp16 launch and packer, the data gradients
+    # with the shift of the published divisor; fp16 falling back straight to three limbs; a three-limb eval forward next to an
+    # fp16 recording pass; the tail routes, three-limb under every setting
+    "nf128_64px_b16_rec_x3": Case(*_B16, "bf16x3", "residual", 0.0, None, "bf16x3"),
+    "nf128_64px_b16_f16_rec_f16": Case(*_B16, "bf16x3", "residual", 0.0, None, "bf16x3", "f16", True, 196608),
+    "nf128_64px_b16_bf16x6_eval_f16": Case(*_B16, "bf16x6", "residual", 0.0, None, "bf16x6", "f16"),
+    "nf128_64px_b16_bf16x6_rec_f16": Case(*_B16, "bf16x6", "residual", 0.0, None, "bf16x3", "limb", True, 1000),
+    "nf160_f16_rec_f16": Case(dict(nf=160), 2, "bf16x3", "residual", 0.0, None, "bf16x3", "f16", True, 1000),
 }
 
 
@@ -99,22 +113,26 @@ class _Recorder:
 
 def run_case(name, patch=setattr):
     """The rows of case ``name``: (eval forward, recorded forward + backward).  ``patch(object, attribute, value)`` sets
-    ``net.overlap_wgrad`` (the caller has applied ``patches()``); the math mode and the Winograd switch are restored."""
+    ``net.overlap_wgrad`` (the caller has applied ``patches()``); the four math settings, the published loss divisor and the
+    Winograd switch are restored."""
     import torch
     import psld_amd
     from psld_amd import _lib, config as cfgs, ops
     from psld_amd.registry import get_module
     from psld_amd.score_exec import _Exec
-    tiny, batch, mode, pin, dropout, wino = CASES[name]
+    tiny, batch, mode, pin, dropout, wino, record_math, eval_math, record_f16, divisor = CASES[name]
     psld_amd.import_modules_into_registry()
     cfg = cfgs.tiny(**tiny)
     sf = cfg.model.score_fn
     sf.progressive_input, sf.dropout = pin, dropout
     rec = _Recorder(_lib.load_real())
-    mode0 = ops.math_mode()
+    saved = ops.math_mode(), ops.record_math(), ops.eval_math(), ops.record_f16(), ops.loss_divisor()
     _lib.set_proxy(rec)
     try:
         ops.set_math_mode(mode)
+        ops.set_record_math(record_math)
+        ops.set_eval_math(eval_math)
+        ops.set_record_f16(record_f16)
         ops.set_winograd(wino)
         torch.manual_seed(0)
         net = get_module("score_fn", "ncsnpp")(cfg)
@@ -131,11 +149,16 @@ def run_case(name, patch=setattr):
             ex = _Exec(net, record=True)
             y = ex.run(x, t)
             net._begin_backward()
+            ops.set_loss_divisor(divisor)
             ex.backward(torch.zeros_like(y))
             net._end_backward()
     finally:
         ops.set_winograd(None)
-        ops.set_math_mode(mode0)
+        ops.set_math_mode(saved[0])
+        ops.set_record_math(saved[1])
+        ops.set_eval_math(saved[2])
+        ops.set_record_f16(saved[3])
+        ops.set_loss_divisor(saved[4])
         _lib.set_proxy(None)
     return rec.rows[:n_eval], rec.rows[n_eval:]
 
