@@ -783,6 +783,40 @@ int psld_lincomb_f64(double* out, const double* base, const double* const* v, co
 int psld_scaled_norm_sq_f64(const double* const* v, const double* coef, int nv, const double* p,
                             const double* q, double atol, double rtol, long long n, double* out,
                             void* workspace /* >= psld_reduce_workspace_bytes(n) */, hipStream_t stream);
+/* Probability-flow likelihood: the device kernels around ONE vector-Jacobian product of the network per
+ * evaluation of the augmented ODE's right-hand side.  One time per call, its scalars from the host as in the samplers:
+ * ``k`` is the psld_em_coeffs_t of the (forward) time t (dt and probability_flow are ignored); ``vp_std`` > 0 selects the
+ * VP-SDE instead, with k->beta = beta(t) and vp_std = sigma_t (every other field of k is then ignored); vp_std = 0: PSLD.
+ * State layout [B, 2c, hw] (PSLD: [x | m]) or [B, c, hw] (VP), NCHW, as everywhere in this section.  batch <= 65535.
+ *
+ * psld_rademacher_f32: out[i] = +-1 from the dropout hash of (seed, offset + i) - a function of those two numbers alone, so
+ *   any split of a range into launches, and any launch geometry, writes the same values.
+ * psld_pf_cotangent_f32: w = A^T z (f32) for the probe z (f32, the state's shape), A the linear map eps -> -1/2 g(t)^2 s(eps),
+ *   s = -L_t^{-T} eps as psld_reverse_sde_f64 forms it:
+ *     score_mode 0: w_x = 1/2 beta gamma c11 z_x + 1/2 beta M nu c21 z_m,  w_m = 1/2 beta gamma c12 z_x + 1/2 beta M nu c22 z_m
+ *     score_mode 1: w = 1/2 beta M nu c22 z_m  [B, c, hw];   score_mode 2: w = 1/2 beta gamma c11 z_x  [B, c, hw]
+ *     VP:           w = 1/2 beta / sigma_t z
+ *   (products in f64, rounded to f32 once).  w has the shape of the network's output.
+ * psld_pf_div_rhs_f64: with n = batch * 2c * hw (VP: batch * c * hw): out[0 : n] = F(u, t) = f - 1/2 g^2 s(eps_pred), the
+ *   FORWARD-time probability-flow drift (= -f_bar of psld_reverse_sde_f64 / psld_vp_reverse_f64 with probability_flow, in
+ *   their arithmetic); out[n + b] = div_lin + sum_i z_i vjp_i over sample b, div_lin = -1/2 beta (gamma + nu) c hw (VP:
+ *   -1/2 beta c hw) the divergence of the linear drift, vjp = J_eps^T w (f32, the state's shape).  The sum is taken in f64
+ *   in an order fixed by (c, hw) alone: bitwise repeatable, and a sample's value does not depend on the batch around it.
+ *   out holds n + batch doubles: the right-hand side of the ODE on the augmented flat state [u, log-density increment].
+ * psld_gauss_logp_f64: out[b] = log N(x_b; 0, var_x I) + log N(m_b; 0, var_m I) for u = [B, c_x + c_m, hw] f64 ([x | m];
+ *   c_m = 0: x alone, the VP prior); f64, same fixed order.
+ * workspace (the two reductions): >= psld_pf_workspace_bytes(batch) bytes. */
+#define PSLD_PF_MAX_SLICES 32
+long long psld_pf_workspace_bytes(int batch);
+int psld_rademacher_f32(float* out, long long n, unsigned long long seed, unsigned long long offset,
+                        hipStream_t stream);
+int psld_pf_cotangent_f32(const float* z, const psld_em_coeffs_t* k, double vp_std, int batch, int c, int hw,
+                          float* w, hipStream_t stream);
+int psld_pf_div_rhs_f64(const double* u, const float* eps_pred, const float* vjp, const float* z,
+                        const psld_em_coeffs_t* k, double vp_std, int batch, int c, int hw, double* out,
+                        void* workspace, hipStream_t stream);
+int psld_gauss_logp_f64(const double* u, double var_x, double var_m, int batch, int c_x, int c_m, int hw,
+                        double* out, void* workspace, hipStream_t stream);
 /* VP-SDE baseline (main/models/sde/vpsde.py:9-99): perturbation kernel and the reverse
  * drift / Euler-Maruyama update (mode 0: f_bar = -f + g^2*score; mode 1: x <- x + f_bar*dt + g*sqrt(dt)*z). */
 /* ScoreLoss beyond the eps-MSE (main/losses.py:38-39, 55-63).  mode 1: L1 criterion, loss f32 = mean|sum |eps - eps_pred|;

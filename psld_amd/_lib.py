@@ -228,6 +228,11 @@ SIGNATURES = {
     "psld_vp_reverse_f64": (I, [P, P, P, D, D, D, I, I, LL, P, P, P]),
     "psld_mask_combine_f64": (I, [P, P, P, I, I, I, P, P]),
     "psld_guide_f64": (I, [P, P, D, D, I, I, I, P, P]),
+    "psld_pf_workspace_bytes": (LL, [I]),
+    "psld_rademacher_f32": (I, [P, LL, C.c_ulonglong, C.c_ulonglong, P]),
+    "psld_pf_cotangent_f32": (I, [P, C.POINTER(EmCoeffs), D, I, I, I, P, P]),
+    "psld_pf_div_rhs_f64": (I, [P, P, P, P, C.POINTER(EmCoeffs), D, I, I, I, P, P, P]),
+    "psld_gauss_logp_f64": (I, [P, D, D, I, I, I, I, P, P, P]),
     "psld_softmax_xent_f32": (I, [P, P, I, I, F, F, P, P, P, P]),
     "psld_f64_to_f32": (I, [P, P, LL, P]),
     "psld_f32_to_f64": (I, [P, P, LL, P]),

@@ -8,6 +8,8 @@
                                                                            (main/train_clf.py:24-110)
     python -m psld_amd.cli cc_sample --config c10_sota --clf-config clf_c10 [dataset.clf.evaluation.label_to_sample=9 ...]
                                                                            (main/eval/class_cond_sample.py:29-138)
+    python -m psld_amd.cli bpd --config c10_sota --data x.npy --ckpt last.ckpt [--n-probes N --n-momentum N --rtol R --atol A]
+                                                                           (no counterpart: psld_amd/likelihood.py)
 
 For the two classifier-guidance commands ``dataset.clf.<key>=value`` / ``clf.<key>=value`` go to the ``clf`` node.
 
@@ -485,10 +487,46 @@ def inpaint(args, overrides):
         dist.destroy_process_group()
 
 
+def bpd_summary(bpd_values, nfes) -> dict:
+    """The one JSON line of the ``bpd`` command: mean bits/dim over the images, its standard error, mean NFE per batch."""
+    v = np.asarray(bpd_values, dtype=np.float64)
+    se = float(v.std(ddof=1) / np.sqrt(v.size)) if v.size > 1 else 0.0
+    return {"bpd": float(v.mean()), "bpd_stderr": se, "n_images": int(v.size), "mean_nfe": float(np.mean(nfes))}
+
+
+def bpd(args, overrides):
+    """Bits/dim of the images of ``--data`` under the EMA network in eval mode (psld_amd.likelihood.PFLikelihood.bpd), in
+    batches of ``evaluation.batch_size``; one JSON line on stdout.  Single process (no sharding)."""
+    import json
+
+    from psld_amd import config as C, ops
+    from psld_amd.likelihood import PFLikelihood
+    dev = torch.device("cuda", 0)
+    cfg = parse_overrides(getattr(C, args.config)(), overrides)
+    score_fn, ema, sde = build(cfg, dev)
+    path = args.ckpt or cfg.evaluation.chkpt_path
+    if path:
+        load_checkpoint(path, score_fn, ema)
+        ema.to(dev)
+    ema.eval()
+    lik = PFLikelihood(cfg, sde, ema, rtol=args.rtol, atol=args.atol, probe=args.probe)
+    data = _dataset(cfg, args, dev, 0)
+    n = data.shape[0] if not args.max_images else min(args.max_images, data.shape[0])
+    bs = max(1, min(cfg.evaluation.batch_size, n))
+    values, nfes = [], []
+    for start in range(0, n, bs):
+        x0 = ops.uint8_to_images(data[start:start + bs][:n - start].contiguous(), norm=cfg.data.norm)
+        out = lik.bpd(x0, n_momentum=args.n_momentum, dequantize=args.dequantize, n_probes=args.n_probes,
+                      seed=args.seed + start, levels=127.5 if cfg.data.norm else 255.0)
+        values += out["bpd"].cpu().tolist()
+        nfes.append(out["nfe"])
+    print(json.dumps(bpd_summary(values, nfes)), flush=True)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="psld_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("train", "sample", "inpaint", "train_clf", "cc_sample"):
+    for name in ("train", "sample", "inpaint", "train_clf", "cc_sample", "bpd"):
         p = sub.add_parser(name)
         p.add_argument("--config", default="c10_sota", choices=["c10_sota", "celeba64_sota", "afhqv2_128", "afhqv2_128_inpaint",
                                                          "yaml_default", "tiny"])
@@ -505,6 +543,21 @@ def build_parser() -> argparse.ArgumentParser:
                                 "PSLD_MATH); bf16x3 = two-limb reduced-precision inference; f16 = bf16x3 with the Winograd and "
                                 "wide pointwise forwards on ONE fp16 product (ops.set_eval_math): ~1e-3 rel-L2 from fp32, the "
                                 "precision of the reference's default TF32 convolutions, outside the 1e-4 parity contract")
+        if name == "bpd":
+            p.add_argument("--ckpt", default=None, help="checkpoint (Lightning layout); default evaluation.chkpt_path")
+            p.add_argument("--n-probes", type=int, default=1, help="independent divergence probes averaged per image")
+            p.add_argument("--n-momentum", type=int, default=1, help="PSLD: momentum draws of the Jensen bound per image")
+            p.add_argument("--rtol", type=float, default=1e-5)
+            p.add_argument("--atol", type=float, default=1e-5)
+            p.add_argument("--probe", default="rademacher", choices=["rademacher", "gaussian"])
+            p.add_argument("--dequantize", action="store_true", help="add uniform noise of one uint8 level to the images")
+            p.add_argument("--seed", type=int, default=0)
+            p.add_argument("--max-images", type=int, default=0, help="evaluate the first N images only (0: all)")
+            p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32", "f16"],
+                           help="as for sample.  The likelihood's right-hand side is a RECORDING pass (forward + input "
+                                "gradient), and the reduced modes bf16x3 / f16 touch only non-recording forwards: among the "
+                                "limb modes this setting does not change the result (record math governs recording passes); "
+                                "f32 takes every pass, recording ones included, off the limb kernels")
         if name in ("train", "train_clf"):
             p.add_argument("--train-math", default=None, choices=["bf16x6", "bf16x3", "f16"],
                            help="arithmetic of the passes that record a backward pass (ops.set_record_math; default: the "
@@ -535,7 +588,7 @@ def main(argv=None):
         from psld_amd import ops
         ops.set_grad_shift(args.grad_shift)
     {"train": train, "sample": sample, "inpaint": inpaint, "train_clf": train_clf,
-     "cc_sample": cc_sample}[args.cmd](args, overrides)
+     "cc_sample": cc_sample, "bpd": bpd}[args.cmd](args, overrides)
 
 
 if __name__ == "__main__":

@@ -721,7 +721,10 @@ __global__ void time_embed_kernel(const float* __restrict__ t, const float* __re
     const int b = i / e, k = i % e;
     float p;
     if (use_log) {
-        const float lt = logf(t[b]);
+        // log t correctly rounded (through fp64): p = 2 pi W log t reaches hundreds of radians at small t, where ONE fp32 ulp of
+        // log t moves sin / cos by ~5e-5 - and the network output by 2.3e-5 rel-L2 at t = 1e-3.  The device logf is within its
+        // 1 ulp but often not the nearest float; torch's CPU log (the reference's arithmetic) is, for 99.9 % of t
+        const float lt = (float)log((double)t[b]);
         p = __fmul_rn(__fmul_rn(__fmul_rn(lt, W[k]), 2.0f), 3.14159265358979323846f);
     } else {
         p = __fmul_rn(t[b], W[k]);

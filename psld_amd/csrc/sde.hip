@@ -657,3 +657,275 @@ extern "C" int psld_vp_score_loss(const float* eps, const float* eps_pred, const
     PSLD_CHECK_LAUNCH("scaled_final_kernel");
     return PSLD_OK;
 }
+
+// ---- probability-flow likelihood: probe, cotangent, augmented right-hand side, prior density ---------
+// Streaming kernels around one vector-Jacobian product of the network per right-hand-side evaluation.  The two reductions
+// (the divergence estimate, the Gaussian log-density) run as one workgroup per (sample, slice): the number of slices and
+// every summation order follow from the SAMPLE's size alone, so a sample's value is bitwise the same in any batch.
+namespace {
+
+constexpr int PF_THREADS = 256;
+
+// slices of a sample of ``items`` thread-items: one vector pass of a workgroup each, at most PSLD_PF_MAX_SLICES
+inline int pf_slices(long long items) {
+    const long long s = (items + 1023) / 1024;
+    return (int)(s < 1 ? 1 : (s > PSLD_PF_MAX_SLICES ? PSLD_PF_MAX_SLICES : s));
+}
+inline bool pf_aligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
+
+// +-1 from the dropout hash (common.h) at p = 1/2: element i is a function of (seed, offset + i) alone
+template <int VEC>
+__global__ void rademacher_kernel(float* __restrict__ out, long long n, unsigned long long seed,
+                                  unsigned long long offset) {
+    typedef float fv __attribute__((ext_vector_type(VEC)));
+    const long long nv = n / VEC;
+    GRID_STRIDE(i, nv) {
+        fv v;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+            v[e] = psld_dropout_keep(seed, offset + (unsigned long long)(i * VEC + e), 0.5f) ? 1.f : -1.f;
+        reinterpret_cast<fv*>(out)[i] = v;
+    }
+    if (VEC > 1 && blockIdx.x == 0 && (long long)threadIdx.x < n - nv * VEC) {
+        const long long i = nv * VEC + threadIdx.x;
+        out[i] = psld_dropout_keep(seed, offset + (unsigned long long)i, 0.5f) ? 1.f : -1.f;
+    }
+}
+
+// w = A^T z with A: eps -> -1/2 g^2 s(eps), s = -L^{-T} eps (reverse_terms above); products in f64, rounded once
+template <int VEC>
+__global__ void pf_cotangent_kernel(const float* __restrict__ z, const psld_em_coeffs_t k, double vp_std, int c, int hw,
+                                    float* __restrict__ w) {
+    typedef float fv __attribute__((ext_vector_type(VEC)));
+    const long long per = (long long)c * hw / VEC;
+    const long long b = blockIdx.y;
+    const fv* zv = reinterpret_cast<const fv*>(z);
+    fv* wv = reinterpret_cast<fv*>(w);
+    const double hx = 0.5 * k.beta * k.gamma, hm = 0.5 * k.beta * k.m * k.nu;
+    const double axx = hx * (double)k.c11, axm = hm * (double)k.c21, amx = hx * (double)k.c12, amm = hm * (double)k.c22;
+    const double avp = vp_std > 0.0 ? 0.5 * k.beta / vp_std : 0.0;
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < per; r += (long long)gridDim.x * blockDim.x) {
+        if (vp_std > 0.0) {
+            const fv zx = zv[b * per + r];
+            fv o;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) o[e] = (float)(avp * (double)zx[e]);
+            wv[b * per + r] = o;
+        } else if (k.score_mode == 0) {
+            const fv zx = zv[b * 2 * per + r], zm = zv[b * 2 * per + per + r];
+            fv ox, om;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                ox[e] = (float)(axx * (double)zx[e] + axm * (double)zm[e]);
+                om[e] = (float)(amx * (double)zx[e] + amm * (double)zm[e]);
+            }
+            wv[b * 2 * per + r] = ox;
+            wv[b * 2 * per + per + r] = om;
+        } else {
+            const fv zz = zv[b * 2 * per + (k.score_mode == 1 ? per : 0) + r];
+            const double a = k.score_mode == 1 ? amm : axx;
+            fv o;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) o[e] = (float)(a * (double)zz[e]);
+            wv[b * per + r] = o;
+        }
+    }
+}
+
+__device__ __forceinline__ void pf_block_sum(double acc, double* __restrict__ dst) {
+    __shared__ double red[PF_THREADS / 64];
+    acc = wave_sum_d(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) dst[0] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// forward-time drift F = f - 1/2 g^2 s = -f_bar(probability flow) of the kernels above, and this slice's share of z . vjp
+template <int VEC>
+__global__ void pf_div_rhs_kernel(const double* __restrict__ u, const float* __restrict__ eps, const float* __restrict__ vjp,
+                                  const float* __restrict__ z, const psld_em_coeffs_t k, double vp_std, int c, int hw,
+                                  double* __restrict__ out, double* __restrict__ part) {
+    typedef float fv __attribute__((ext_vector_type(VEC)));
+    typedef double dv __attribute__((ext_vector_type(VEC)));
+    const long long per = (long long)c * hw / VEC;
+    const long long b = blockIdx.y;
+    const long long len = (per + gridDim.x - 1) / gridDim.x;
+    const long long lo = (long long)blockIdx.x * len;
+    const long long hi = lo + len < per ? lo + len : per;
+    const dv* uv = reinterpret_cast<const dv*>(u);
+    dv* fo = reinterpret_cast<dv*>(out);
+    const fv* ev = reinterpret_cast<const fv*>(eps);
+    const fv* jv = reinterpret_cast<const fv*>(vjp);
+    const fv* zv = reinterpret_cast<const fv*>(z);
+    double acc = 0.0;
+    if (vp_std > 0.0) {
+        const double g = sqrt(k.beta);
+        for (long long r = lo + threadIdx.x; r < hi; r += blockDim.x) {
+            const long long i = b * per + r;
+            const dv xv = uv[i];
+            const fv e4 = ev[i], j4 = jv[i], z4 = zv[i];
+            dv f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const double score = 0.5 * (-(double)e4[e] / vp_std);           // vp_reverse_kernel, probability flow
+                f[e] = -(-(-0.5 * k.beta * xv[e]) + (g * g) * score);
+                acc += (double)z4[e] * (double)j4[e];
+            }
+            fo[i] = f;
+        }
+    } else {
+        for (long long r = lo + threadIdx.x; r < hi; r += blockDim.x) {
+            const long long ox = b * 2 * per + r, om = ox + per;
+            const dv xv = uv[ox], mv = uv[om];
+            fv ex, em;
+            if (k.score_mode == 0) { ex = ev[ox]; em = ev[om]; }
+            else { ex = ev[b * per + r]; em = ex; }
+            const fv jx = jv[ox], jm = jv[om], zx = zv[ox], zm = zv[om];
+            dv fx, fm;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const RevOut o = reverse_terms(k, xv[e], mv[e], ex[e], em[e], true);
+                fx[e] = -o.fbx;
+                fm[e] = -o.fbm;
+                acc += (double)zx[e] * (double)jx[e];
+            }
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc += (double)zm[e] * (double)jm[e];
+            fo[ox] = fx;
+            fo[om] = fm;
+        }
+    }
+    pf_block_sum(acc, part + b * gridDim.x + blockIdx.x);
+}
+
+// one thread per sample: the slices' shares in slice order, on top of the analytic divergence of the linear drift
+__global__ void pf_div_final_kernel(const double* __restrict__ part, int slices, int batch, double div_lin,
+                                    double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    double acc = 0.0;
+    for (int s = 0; s < slices; ++s) acc += part[(long long)b * slices + s];
+    out[b] = div_lin + acc;
+}
+
+// sums of squares of the first nx and of the other per - nx values of a sample, per slice
+template <int VEC>
+__global__ void gauss_sq_kernel(const double* __restrict__ u, long long nx, long long per, double* __restrict__ part) {
+    typedef double dv __attribute__((ext_vector_type(VEC)));
+    const long long items = per / VEC;
+    const long long b = blockIdx.y;
+    const long long len = (items + gridDim.x - 1) / gridDim.x;
+    const long long lo = (long long)blockIdx.x * len;
+    const long long hi = lo + len < items ? lo + len : items;
+    const dv* uv = reinterpret_cast<const dv*>(u + b * per);
+    double sx = 0.0, sm = 0.0;
+    for (long long r = lo + threadIdx.x; r < hi; r += blockDim.x) {
+        const dv v = uv[r];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const double q = v[e] * v[e];
+            if (r * VEC + e < nx) sx += q; else sm += q;
+        }
+    }
+    double* dst = part + 2 * (b * gridDim.x + blockIdx.x);
+    pf_block_sum(sx, dst);
+    __syncthreads();
+    pf_block_sum(sm, dst + 1);
+}
+
+__global__ void gauss_final_kernel(const double* __restrict__ part, int slices, int batch, double var_x, double var_m,
+                                   long long nx, long long nm, double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    double sx = 0.0, sm = 0.0;
+    for (int s = 0; s < slices; ++s) {
+        sx += part[2 * ((long long)b * slices + s)];
+        sm += part[2 * ((long long)b * slices + s) + 1];
+    }
+    const double two_pi = 6.283185307179586476925286766559;
+    double lp = -0.5 * (sx / var_x) - 0.5 * ((double)nx * log(two_pi * var_x));
+    if (nm > 0) lp = lp + (-0.5 * (sm / var_m) - 0.5 * ((double)nm * log(two_pi * var_m)));
+    out[b] = lp;
+}
+
+}  // namespace
+
+extern "C" long long psld_pf_workspace_bytes(int batch) {
+    return 2LL * sizeof(double) * PSLD_PF_MAX_SLICES * (batch > 0 ? batch : 0);
+}
+
+extern "C" int psld_rademacher_f32(float* out, long long n, unsigned long long seed, unsigned long long offset,
+                                   hipStream_t stream) {
+    PSLD_CHECK_ARG(out && n > 0, "psld_rademacher_f32: bad args");
+    if (pf_aligned(out, 16))
+        hipLaunchKernelGGL(rademacher_kernel<4>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, stream, out, n, seed, offset);
+    else
+        hipLaunchKernelGGL(rademacher_kernel<1>, dim3(grid_for(n)), dim3(256), 0, stream, out, n, seed, offset);
+    PSLD_CHECK_LAUNCH("psld_rademacher_f32");
+    return PSLD_OK;
+}
+
+extern "C" int psld_pf_cotangent_f32(const float* z, const psld_em_coeffs_t* k, double vp_std, int batch, int c, int hw,
+                                     float* w, hipStream_t stream) {
+    PSLD_CHECK_ARG(z && k && w && batch > 0 && batch <= 65535 && c > 0 && hw > 0 && vp_std >= 0.0 &&
+                   (vp_std > 0.0 || (k->score_mode >= 0 && k->score_mode <= 2)), "psld_pf_cotangent_f32: bad args");
+    const long long per = (long long)c * hw;
+    if (hw % 4 == 0 && pf_aligned(z, 16) && pf_aligned(w, 16))
+        hipLaunchKernelGGL(pf_cotangent_kernel<4>, dim3(pf_slices(per / 4), batch), dim3(PF_THREADS), 0, stream, z, *k, vp_std,
+                           c, hw, w);
+    else
+        hipLaunchKernelGGL(pf_cotangent_kernel<1>, dim3(pf_slices(per), batch), dim3(PF_THREADS), 0, stream, z, *k, vp_std, c,
+                           hw, w);
+    PSLD_CHECK_LAUNCH("psld_pf_cotangent_f32");
+    return PSLD_OK;
+}
+
+extern "C" int psld_pf_div_rhs_f64(const double* u, const float* eps_pred, const float* vjp, const float* z,
+                                   const psld_em_coeffs_t* k, double vp_std, int batch, int c, int hw, double* out,
+                                   void* workspace, hipStream_t stream) {
+    PSLD_CHECK_ARG(u && eps_pred && vjp && z && k && out && workspace && batch > 0 && batch <= 65535 && c > 0 && hw > 0 &&
+                   vp_std >= 0.0 && (vp_std > 0.0 || (k->score_mode >= 0 && k->score_mode <= 2)),
+                   "psld_pf_div_rhs_f64: bad args");
+    psld_em_coeffs_t kk = *k;
+    kk.probability_flow = 1;
+    const long long per = (long long)c * hw;
+    const long long n = (vp_std > 0.0 ? 1 : 2) * per * batch;
+    const double div_lin = (vp_std > 0.0 ? -0.5 * kk.beta : -0.5 * kk.beta * (kk.gamma + kk.nu)) * (double)per;
+    double* part = reinterpret_cast<double*>(workspace);
+    int slices;
+    if (hw % 4 == 0 && pf_aligned(u, 32) && pf_aligned(out, 32) && pf_aligned(eps_pred, 16) && pf_aligned(vjp, 16) &&
+        pf_aligned(z, 16)) {
+        slices = pf_slices(per / 4);
+        hipLaunchKernelGGL(pf_div_rhs_kernel<4>, dim3(slices, batch), dim3(PF_THREADS), 0, stream, u, eps_pred, vjp, z, kk,
+                           vp_std, c, hw, out, part);
+    } else {
+        slices = pf_slices(per);
+        hipLaunchKernelGGL(pf_div_rhs_kernel<1>, dim3(slices, batch), dim3(PF_THREADS), 0, stream, u, eps_pred, vjp, z, kk,
+                           vp_std, c, hw, out, part);
+    }
+    PSLD_CHECK_LAUNCH("pf_div_rhs_kernel");
+    hipLaunchKernelGGL(pf_div_final_kernel, dim3(cdiv(batch, 64)), dim3(64), 0, stream, part, slices, batch, div_lin, out + n);
+    PSLD_CHECK_LAUNCH("pf_div_final_kernel");
+    return PSLD_OK;
+}
+
+extern "C" int psld_gauss_logp_f64(const double* u, double var_x, double var_m, int batch, int c_x, int c_m, int hw,
+                                   double* out, void* workspace, hipStream_t stream) {
+    PSLD_CHECK_ARG(u && out && workspace && batch > 0 && batch <= 65535 && c_x > 0 && c_m >= 0 && hw > 0 && var_x > 0.0 &&
+                   (c_m == 0 || var_m > 0.0), "psld_gauss_logp_f64: bad args");
+    const long long nx = (long long)c_x * hw, nm = (long long)c_m * hw, per = nx + nm;
+    double* part = reinterpret_cast<double*>(workspace);
+    int slices;
+    if (per % 2 == 0 && pf_aligned(u, 16)) {
+        slices = pf_slices(per / 2);
+        hipLaunchKernelGGL(gauss_sq_kernel<2>, dim3(slices, batch), dim3(PF_THREADS), 0, stream, u, nx, per, part);
+    } else {
+        slices = pf_slices(per);
+        hipLaunchKernelGGL(gauss_sq_kernel<1>, dim3(slices, batch), dim3(PF_THREADS), 0, stream, u, nx, per, part);
+    }
+    PSLD_CHECK_LAUNCH("gauss_sq_kernel");
+    hipLaunchKernelGGL(gauss_final_kernel, dim3(cdiv(batch, 64)), dim3(64), 0, stream, part, slices, batch, var_x, var_m, nx,
+                       nm, out);
+    PSLD_CHECK_LAUNCH("gauss_final_kernel");
+    return PSLD_OK;
+}

@@ -1664,6 +1664,60 @@ def guide(x: Tensor, grad: Tensor, coef_x: float, coef_m: float, x_f32: Optional
     return x
 
 
+def rademacher(out: Tensor, seed: int, offset: int = 0) -> Tensor:
+    """Fill the float32 tensor ``out`` with +-1 probes: flat element i from the hash of (seed, offset + i) alone."""
+    check(lib().psld_rademacher_f32(_chk(out).data_ptr(), out.numel(), int(seed) & (2 ** 64 - 1), int(offset), _stream()),
+          "psld_rademacher_f32")
+    return out
+
+
+def _pf_dims(u_shape, vp: bool):
+    b, ct, h, w = u_shape
+    return b, (ct if vp else ct // 2), h * w
+
+
+def pf_cotangent(z: Tensor, k: EmCoeffs, vp_std: float = 0.0) -> Tensor:
+    """The network cotangent w = A^T z of the probability-flow divergence estimate (psld_pf_cotangent_f32): ``z`` f32 of the
+    state's shape; ``w`` of the network output's shape (half the channels in the score_m / score_x modes).  ``vp_std`` > 0:
+    VP-SDE with k.beta, else PSLD with ``k`` = em_coeffs(t)."""
+    vp = vp_std > 0.0
+    b, c, hw = _pf_dims(z.shape, vp)
+    cw = c if (vp or k.score_mode != 0) else 2 * c
+    w = torch.empty((b, cw) + tuple(z.shape[2:]), device=z.device, dtype=torch.float32)
+    check(lib().psld_pf_cotangent_f32(_chk(z).data_ptr(), C.byref(k), float(vp_std), b, c, hw, w.data_ptr(), _stream()),
+          "psld_pf_cotangent_f32")
+    return w
+
+
+def pf_div_rhs(u: Tensor, eps_pred: Tensor, vjp: Tensor, z: Tensor, k: EmCoeffs, vp_std: float = 0.0,
+               out: Optional[Tensor] = None) -> Tensor:
+    """Right-hand side of the likelihood ODE on the augmented flat state: out[:u.numel()] = the forward-time probability-flow
+    drift F(u, t), out[u.numel():] = per-sample divergence estimate div_lin + z . vjp (psld_pf_div_rhs_f64)."""
+    vp = vp_std > 0.0
+    b, c, hw = _pf_dims(u.shape, vp)
+    assert vjp.shape == u.shape and z.shape == u.shape, (tuple(vjp.shape), tuple(z.shape), tuple(u.shape))
+    assert eps_pred.numel() == (u.numel() if (vp or k.score_mode == 0) else u.numel() // 2), tuple(eps_pred.shape)
+    if out is None:
+        out = torch.empty(u.numel() + b, device=u.device, dtype=torch.float64)
+    assert out.numel() == u.numel() + b and out.dtype == torch.float64
+    ws = workspace(lib().psld_pf_workspace_bytes(b), u.device)
+    check(lib().psld_pf_div_rhs_f64(_chk(u, torch.float64).data_ptr(), _chk(eps_pred).data_ptr(), _chk(vjp).data_ptr(),
+                                    _chk(z).data_ptr(), C.byref(k), float(vp_std), b, c, hw, out.data_ptr(), ws.data_ptr(),
+                                    _stream()), "psld_pf_div_rhs_f64")
+    return out
+
+
+def gauss_logp(u: Tensor, var_x: float, var_m: float, c_m: int) -> Tensor:
+    """Per-sample log N(x; 0, var_x I) + log N(m; 0, var_m I) of the f64 state u = [x | m] whose last ``c_m`` channels are
+    m (0: none) -> f64 [B] (psld_gauss_logp_f64)."""
+    b, ct, h, w = u.shape
+    out = torch.empty(b, device=u.device, dtype=torch.float64)
+    ws = workspace(lib().psld_pf_workspace_bytes(b), u.device)
+    check(lib().psld_gauss_logp_f64(_chk(u, torch.float64).data_ptr(), float(var_x), float(var_m), b, ct - c_m, c_m, h * w,
+                                    out.data_ptr(), ws.data_ptr(), _stream()), "psld_gauss_logp_f64")
+    return out
+
+
 def softmax_xent(logits: Tensor, labels: Tensor, loss_scale: float, grad_scale: float, want_grad: bool = True):
     """(loss 0-d f32, dlogits or None, correct 0-d f32): cross entropy of [rows][n] logits vs int64 labels."""
     rows, n = logits.shape

@@ -66,6 +66,8 @@ class _Exec(_ExecBase):
         dense_batched = self.dense_batched
 
         def bwd():
+            if self.input_grad_only:    # t gets no gradient: the whole chain from here ends in parameters
+                return
             self.join_side()            # every block wrote its slice of dtp_all / accumulated into st.g
             if dense_batched:
                 kd = wcat.shape[1]
@@ -327,6 +329,7 @@ class _Exec(_ExecBase):
         cut3 = (f3.numel() - (R.WINO_FRAG_PAD_BYTES if wino else 0)) * c1 // cin
         gam, bet = gn0.weight.detach(), gn0.bias.detach()
         dgam, dbet = self.g(gn0.weight), self.g(gn0.bias)
+        cut = (lambda t, lo, hi: t[lo:hi]) if dgam is not None else (lambda t, lo, hi: None)    # (input-gradient-only: none)
         for node, lo, hi, fr3, st, g, first, route in ((xa, 0, c1, f3[:cut3], sta, g1, first_a, routes[0]),
                                                       (xb, c1, cin, f3[cut3:], stb, g2, first_b, routes[1])):
             c = hi - lo
@@ -337,7 +340,7 @@ class _Exec(_ExecBase):
                 self.wino_dgrad(dh1, fr3, c, da0)
             else:
                 ops.conv3x3_split(dh1, None, fr3, c, da0)
-            self.gn_backward(da0, node.v, st, gam[lo:hi], bet[lo:hi], dgam[lo:hi], dbet[lo:hi], True, xg,
+            self.gn_backward(da0, node.v, st, gam[lo:hi], bet[lo:hi], cut(dgam, lo, hi), cut(dbet, lo, hi), True, xg,
                              accumulate_dx=True, groups=g, last_writer_of=node if first else None)
 
     # -- AttnBlockpp.forward (layerspp.py:75-91) -----------------------------------------------------
@@ -568,7 +571,7 @@ class _Exec(_ExecBase):
             # cannot fill the chip by themselves (32x32 images: B = 16 +9 %, B = 32 +5 %, B = 64 +1.3 %, B = 128 +0.3 % images/s - and per-kernel HIP
             # event timings would be inflated by the concurrent MFMA kernel: off there)
             use = net.overlap_wgrad if net.overlap_wgrad is not None else (b * hh * ww <= _OVERLAP_MAX_PIXELS)
-            self.side = net._side_stream() if use else None
+            self.side = net._side_stream() if use and not self.input_grad_only else None
         h0 = torch.empty((b, hh, ww, stem.weight.shape[0]), device=x.device, dtype=torch.float32)
         stem_small = x_nhwc.shape[-1] * 9 <= 64 and stem.weight.shape[0] % 4 == 0
         stem_cols = None

@@ -579,6 +579,29 @@ class NCSNpp(nn.Module):
         with torch.no_grad():
             return _Exec(self, record=False).run(x, t)
 
+    def vjp_input(self, x: Tensor, time_cond: Tensor, w: Tensor):
+        """``(y, dx)``: the network output at ``(x, time_cond)`` and the vector-Jacobian product ``w^T dy/dx`` (NCHW, fp32),
+        from ONE recorded forward in the module's current train / eval state (eval: no dropout) and one backward that runs
+        the data-gradient launches alone (``_Exec.input_grad_only``).  No autograd node is built and no parameter gradient
+        is touched: nothing is written into ``flat_grad()`` or any ``p.grad``, so an EMA copy that is only being evaluated
+        needs no gradient buffer.  ``dx`` is bit for bit the ``x.grad`` of ``forward(x.requires_grad_()).backward(w)``.
+        The pass runs in the record arithmetic in force (``ops.pass_arith(record=True)``), like any recording pass."""
+        if not x.is_cuda:
+            raise RuntimeError("psld_amd.NCSNpp runs on MI355X only: the HIP extension has no CPU fallback "
+                               "(use oracle/psld_oracle.py as the CPU checker)")
+        if x.dtype != torch.float32 or time_cond.dtype != torch.float32 or w.dtype != torch.float32:
+            raise RuntimeError("NCSNpp.vjp_input expects float32 x, time_cond and w")
+        ops.lib()
+        self.flatten_parameters()
+        with torch.no_grad():
+            ex = _Exec(self, record=True, input_grad_only=True)
+            ex.want_dx = True
+            y = ex.run(x.detach().contiguous(), time_cond.detach().contiguous())
+            if w.shape != y.shape:
+                raise ValueError(f"vjp_input: cotangent of shape {tuple(w.shape)} for an output of shape {tuple(y.shape)}")
+            ex.backward(w.detach())
+        return y, ex.dx_nchw
+
     # ---- HIP-graph replay of the inference forward (launch-bound regime: small sampling batches) ----------
     def enable_graphs(self, flag: bool = True):
         """Capture the eval-mode forward into a HIP graph per input shape and replay it: one graph launch

@@ -69,8 +69,14 @@ def _fir_kernel(k) -> np.ndarray:
 class _ExecBase:
     """One forward (and, if ``record``, the tape of its backward) over NHWC tensors: state and launch helpers."""
 
-    def __init__(self, net: "NCSNpp", record: bool):
+    def __init__(self, net: "NCSNpp", record: bool, input_grad_only: bool = False):
         self.net = net
+        # the backward of this pass is wanted for the gradient w.r.t. the network input alone (NCSNpp.vjp_input): every
+        # launch whose only products are parameter gradients is off - whatever on_side carries (weight and bias gradients,
+        # the slab flush), the deferred reductions and the time-embedding MLP's backward (t gets no gradient, so all of it
+        # ends in parameters) - and g() hands out no view of the flat gradient.  The data-gradient launches are those of the
+        # full backward, argument for argument
+        self.input_grad_only = bool(input_grad_only) and record
         self.tape = [] if record else None
         self.record = record
         sf = net.sf
@@ -139,8 +145,8 @@ class _ExecBase:
         if self.tape is not None:
             self.tape.append((fn, module))
 
-    def g(self, p: nn.Parameter) -> Tensor:
-        return self.net._grad_view(p)
+    def g(self, p: nn.Parameter) -> Optional[Tensor]:
+        return None if self.input_grad_only else self.net._grad_view(p)
 
     def on_side(self, fn, *tensors):
         """Run ``fn`` (kernel launches only) on the side stream, ordered after everything queued so far
@@ -148,6 +154,8 @@ class _ExecBase:
         The work is forked in groups of ``side_group`` calls: one event + one stream wait per group instead of per call
         (a cross-stream edge costs ~3.5 us inside a captured graph and ~10 us of host time outside; measured:
         profiles/r02/graph_fork_cost.txt).  Until its group is launched a call keeps its inputs alive by reference."""
+        if self.input_grad_only:        # parameter gradients only: nothing to run, nothing to fork
+            return
         if self.side is None:
             fn()
             return
@@ -190,6 +198,8 @@ class _ExecBase:
                     alpha: float = 1.0, src_off: int = 0):
         """dst1 (and dst2) [c] = alpha * sum over ``rows`` rows of ``src`` (row stride ld): now, or with every other such
         reduction of the pass in one launch (flush_params)."""
+        if self.input_grad_only:
+            return
         if not self.defer:
             ops.param_reduce2(src if src_off == 0 else src.view(-1)[src_off:], None, rows, ld, c, dst1, None, alpha)
             if dst2 is not None:
@@ -270,7 +280,7 @@ class _ExecBase:
 
     def finish_backward(self):
         """After the last entry of the backward tape: the parked reductions, then the side stream joins."""
-        if self.defer:
+        if self.defer and not self.input_grad_only:
             self.flush_deferred()
         self.join_side()
 
@@ -310,6 +320,8 @@ class _ExecBase:
         """Bias gradient(s) = alpha * column sums of a node's final gradient ``dout``: from the sums its last writer left
         (True: nothing launched now), else by a pass over ``dout`` (False; call it where that pass may run)."""
         gsum, node.gsum = node.gsum, None
+        if self.input_grad_only:
+            return True
         if gsum is not None:
             self.defer_param(gsum, gsum.shape[0], gsum.shape[1], gsum.shape[1], self.g(bias),
                              self.g(bias2) if bias2 is not None else None, alpha)

@@ -321,7 +321,14 @@ class PSLD:
         return torch.cat([p_x, p_m], dim=1)
 
     def prior_logp(self, z):
-        pass
+        """Per-sample log-density, float64 ``[B]``, of the state ``z = [x | m]`` ``[B, 2C, H, W]`` under the distribution
+        ``prior_sampling`` draws from: ``log N(x; 0, I) + log N(m; 0, M I)`` (``M = self.m``).  (``pass`` in the reference,
+        psld.py:372-373; CLD's prior.)  One reduction kernel in float64 with a fixed summation order
+        (``psld_gauss_logp_f64``): bitwise repeatable, a sample's value independent of the batch."""
+        if not z.is_cuda:
+            raise RuntimeError("psld_amd.PSLD needs device tensors (no CPU fallback)")
+        assert z.dim() == 4 and z.shape[1] % 2 == 0, tuple(z.shape)
+        return ops.gauss_logp(z.detach().to(torch.float64).contiguous(), 1.0, float(self.m), z.shape[1] // 2)
 
     def likelihood_weighting(self, t):
         beta_t = self.beta_t(t)

@@ -91,6 +91,10 @@ class VPSDE:
         return torch.randn(*shape, device=device)
 
     def prior_logp(self, z):
+        """Per-sample standard-normal log-density ``log N(z; 0, I)`` (vpsde.py:91-95).  Device tensors: float64 ``[B]`` from
+        one fixed-order reduction kernel (``psld_gauss_logp_f64``); host tensors: the reference's expression."""
+        if z.is_cuda and z.dim() == 4:
+            return ops.gauss_logp(z.detach().to(torch.float64).contiguous(), 1.0, 1.0, 0)
         n = np.prod(z.shape[1:])
         return -n / 2.0 * np.log(2 * np.pi) - torch.sum(z ** 2, dim=(1, 2, 3)) / 2.0
 
