@@ -189,6 +189,8 @@ int psld_conv3x3_split_f32(const float* x1, int c1, const float* x2, int c2, int
  * the direct kernel's rounding error against fp64.  Weights come pre-transformed and pre-split in MFMA operand order
  * (psld_pack_conv3x3_wino, once per optimizer step; psld_conv3x3_wino_frag_bytes = 16/9 of the direct fragments).
  * Shapes: c1, c2 multiples of 32, cout a multiple of 128, h even, w in {8,16,32,64}, h*w dividing or divisible by 128.
+ * 4x4 maps (h == w == 4) run as seven whole images per workgroup (252 of the 256 halo pixels of its raw image): every entry
+ * point except the GroupNorm-fused ones, no gn_part.
  * Row strides: ldy and epi->ldres below 2^20 elements (every psld_conv3x3_wino_* launch: the epilogue addresses the up to
  * 416 pixels of a workgroup's region by 32-bit byte offsets from the first; larger strides are refused). */
 long long psld_conv3x3_wino_frag_bytes(int cout, int cin);
@@ -365,7 +367,7 @@ int psld_conv3x3_wgrad_xlimb_f32(const float* dy, int lddy, int cout, const void
  * with one round of one-workgroup-per-CU tiles).
  * Shapes: cout % 128 == 0 (a workgroup owns 256 output channels of one position, 128 when cout is not a multiple of 256),
  * cin % 128 == 0, cin2 % 128 == 0 (second source of a channel concatenation; 0 / null for none),
- * h == w in {8,16,32,64}, batch*h*w % 128 == 0; dy rows of lddy floats. */
+ * h == w in {8,16,32,64}, batch*h*w % 128 == 0 (4x4 maps too: a K tile is eight images, batch % 8 == 0); dy rows of lddy floats. */
 int psld_conv3x3_wgrad_wino_supported(int cout, int cin, int cin2, int batch, int h, int w);
 int psld_conv3x3_wgrad_wino_nsplit(int cout, int cin_total, int batch, int h, int w);
 long long psld_conv3x3_wgrad_wino_ws_bytes(int cout, int cin_total, int nsplit);

@@ -529,7 +529,7 @@ def build_parser() -> argparse.ArgumentParser:
     for name in ("train", "sample", "inpaint", "train_clf", "cc_sample", "bpd"):
         p = sub.add_parser(name)
         p.add_argument("--config", default="c10_sota", choices=["c10_sota", "celeba64_sota", "afhqv2_128", "afhqv2_128_inpaint",
-                                                         "yaml_default", "tiny"])
+                                                         "c10_ablation", "c10_vpsde", "yaml_default", "tiny"])
         p.add_argument("--data", default="synthetic", help="uint8 [N,H,W,3] .npy file or 'synthetic'")
         p.add_argument("--synthetic-size", type=int, default=2048)
         p.add_argument("--max-steps", type=int, default=0)
@@ -537,6 +537,10 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--mask", default="synthetic", help="inpaint: uint8 [N,H,W,3] .npy (1 = keep) or 'synthetic'")
         p.add_argument("--clf-config", default="clf_c10", choices=["clf_c10", "clf_afhqv2_128", "clf_default", "tiny_clf"])
         p.add_argument("--labels", default="synthetic", help="train_clf: int [N] .npy or 'synthetic'")
+        p.add_argument("--winograd-4x4", type=int, default=0, choices=[0, 1, 2],
+                       help="3x3 convolutions on 4x4 maps (the last level of c10_ablation, c10_vpsde, yaml_default, clf_c10) on the "
+                            "Winograd limb kernels (ops.set_winograd_4x4): 0 = the fp32 tile engine (default), 1 = from batch 8 up, "
+                            "where the launches measured faster than the tile engine's, 2 = every shape the kernels take")
         if name in ("sample", "cc_sample", "inpaint"):
             p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32", "f16"],
                            help="arithmetic of the network evaluations (ops.set_math_mode; default: the process's mode, "
@@ -584,6 +588,8 @@ def main(argv=None):
         from psld_amd import ops
         ops.set_record_math("bf16x3" if args.train_math == "f16" else args.train_math)
         ops.set_record_f16(args.train_math == "f16")
+    from psld_amd import ops as _ops
+    _ops.set_winograd_4x4(args.winograd_4x4)        # unconditionally: an in-process call without the flag means 0
     if getattr(args, "grad_shift", None) is not None:
         from psld_amd import ops
         ops.set_grad_shift(args.grad_shift)

@@ -13,7 +13,9 @@ scripts_psld/sota/uncond/cifar10/train_uncond_psld.sh:6-21 and ``celeba64_sota``
 those of scripts_psld/sota/uncond/celeba64/train_uncond_psld.sh:7-20; ``afhqv2_128`` is
 main/configs/dataset/afhqv2/afhqv2128_psld.yaml with the overrides of
 scripts_psld/ablations/uncond/afhqv2/train_uncond_psld.sh, and ``afhqv2_128_inpaint`` adds those of
-scripts_psld/sota/cond/afhqv2/sample_inpaint_psld.sh.
+scripts_psld/sota/cond/afhqv2/sample_inpaint_psld.sh; ``c10_ablation`` and ``c10_vpsde`` are cifar10_psld.yaml /
+cifar10_vpsde.yaml with the overrides of scripts_psld/ablations/uncond/cifar10/{train,sample}_uncond_{psld,vpsde}.sh (the
+four-level networks of the paper's ablation tables and its VP-SDE baseline).
 """
 from __future__ import annotations
 
@@ -132,6 +134,64 @@ def celeba64_sota() -> Config:
     c.model.sde.nu = 4.005
     c.model.sde.gamma = 0.005
     c.training.batch_size = 16
+    return c
+
+
+def c10_ablation() -> Config:
+    """The CIFAR-10 ablation network (four levels: 32, 16, 8 and 4x4 maps): cifar10_psld.yaml with the overrides of
+    scripts_psld/ablations/uncond/cifar10/train_uncond_psld.sh (nf 128, [1,2,2,2], 2 res blocks, nu 4.02 / gamma 0.02, batch
+    32, hsm); the evaluation node carries the values of sample_uncond_psld.sh (1000 uniform sscs_sde steps, batch 16)."""
+    c = yaml_default()
+    sf = c.model.score_fn
+    sf.in_ch, sf.out_ch = 6, 6
+    sf.nf = 128
+    sf.ch_mult = [1, 2, 2, 2]
+    sf.num_res_blocks = 2
+    sf.attn_resolutions = [16]
+    sf.dropout = 0.1
+    sde = c.model.sde
+    sde.beta_min, sde.beta_max = 8.0, 8.0
+    sde.nu, sde.gamma, sde.kappa, sde.decomp_mode = 4.02, 0.02, 0.04, "lower"
+    c.training.mode = "hsm"
+    c.training.batch_size = 32
+    ev = c.evaluation
+    ev.sampler.name = "sscs_sde"
+    ev.stride_type = "uniform"
+    ev.n_discrete_steps = 1000
+    ev.batch_size = 16
+    ev.sample_from = "target"
+    ev.n_samples = 10000
+    ev.workers = 1
+    ev.path_prefix = 1000
+    return c
+
+
+def c10_vpsde() -> Config:
+    """The VP-SDE baseline on CIFAR-10: cifar10_vpsde.yaml with the overrides of
+    scripts_psld/ablations/uncond/cifar10/train_uncond_vpsde.sh (3 channels in and out, nf 128, [1,2,2,2], 4 res blocks, beta
+    0.1 / 20, score_loss, batch 32); the evaluation node carries sample_uncond_vpsde.sh (1000 quadratic em_sde steps, batch
+    16).  NOTE: the reference's sampling scripts (sample_uncond_vpsde*.sh) rebuild the network with num_res_blocks = 2 -
+    a checkpoint of theirs needs ``model.score_fn.num_res_blocks = 2`` set on this preset."""
+    c = yaml_default()
+    sf = c.model.score_fn
+    sf.in_ch, sf.out_ch = 3, 3
+    sf.nf = 128
+    sf.ch_mult = [1, 2, 2, 2]
+    sf.num_res_blocks = 4
+    sf.attn_resolutions = [16]
+    sf.dropout = 0.1
+    c.model.sde = Config({"name": "vpsde", "beta_min": 0.1, "beta_max": 20, "n_timesteps": 1000, "is_augmented": False})
+    c.training.loss.name = "score_loss"
+    c.training.batch_size = 32
+    ev = c.evaluation
+    ev.sampler.name = "em_sde"
+    ev.stride_type = "quadratic"
+    ev.n_discrete_steps = 1000
+    ev.batch_size = 16
+    ev.sample_from = "target"
+    ev.n_samples = 10000
+    ev.workers = 1
+    ev.path_prefix = 1000
     return c
 
 

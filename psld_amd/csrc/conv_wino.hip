@@ -78,7 +78,7 @@ struct WinoArgs {
 constexpr int wino_mul16(int d) { return 65536 / d + 1; }
 __host__ __device__ constexpr int wino_div16(int x, int mul) { return (x * mul) >> 16; }
 // every (rps, cw) wino_geometry returns (64- and 128-wide maps run as the 32-wide case); nseg * seg_px <= 256
-constexpr int WINO_GEOS[6][2] = {{4, 8}, {8, 8}, {16, 8}, {4, 16}, {8, 16}, {4, 32}};
+constexpr int WINO_GEOS[7][2] = {{4, 4}, {4, 8}, {8, 8}, {16, 8}, {4, 16}, {8, 16}, {4, 32}};
 constexpr bool wino_div16_exact() {
     for (const auto& g : WINO_GEOS) {
         const int W2 = g[1] + 2, seg_px = (g[0] + 2) * W2;
@@ -261,7 +261,8 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
 
     // Region of this workgroup: nseg images (maps smaller than 128 pixels) or one rps x cw block of an image - cw = W, or 32
     // for 64- and 128-wide maps, whose full-width tile (2 rows x 64, 1 row x 128) would need a 264- / 390-pixel halo where
-    // the two raw images hold 256.
+    // the two raw images hold 256.  4x4 maps: SEVEN images (7 x 36 = 252 halo pixels; eight would need 288) - tiles 28 .. 31
+    // of the workgroup belong to no image: they transform halo pixel 0 onwards and store nothing.
     const int HW = a.H * a.W;
     const int W2 = a.cw + 2;
     const int lg_tx = a.lg_tiles_x, lg_tps = a.lg_tps;          // tiles per tile row and per image segment: powers of two
@@ -329,7 +330,7 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
     {
         const int seg = t_tile >> lg_tps, rem = t_tile & ((1 << lg_tps) - 1);
         const int ty = rem >> lg_tx, tx = rem & ((1 << lg_tx) - 1);
-        t_src = (seg * (a.rps + 2) + 2 * ty) * W2 + 2 * tx;
+        t_src = seg < a.nseg ? (seg * (a.rps + 2) + 2 * ty) * W2 + 2 * tx : 0;     // (a tile of no image: 4x4 maps)
     }
     const int t_dst = t_tile * ROWB + (((t_q >> 1) ^ lds_swz(t_tile)) << 4) + (t_q & 1) * 8;
     // raw-image offsets of d[vr + k][c]: a wave's two transforms read d rows vr .. vr + 2 only.  Formed once, in front of the
@@ -596,7 +597,7 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
             const int tile = tb * 16 + r16;
             const int seg = tile >> lg_tps, rem = tile & ((1 << lg_tps) - 1);
             const int ty = rem >> lg_tx, tx = rem & ((1 << lg_tx) - 1);
-            epi_ok[tb] = img0 + seg < a.B;                  // whole images only: a tile is in range or not
+            epi_ok[tb] = seg < a.nseg && img0 + seg < a.B;  // whole images only: a tile is in range or not (seg = nseg: 4x4 maps)
             epi_rel[tb] = epi_ok[tb] ? seg * HW + 2 * ty * a.W + 2 * tx : 0;
             // the row bias as one row per image: the tile's image (the region's first for a tile beyond the batch)
             epi_tbv[tb] = a.rb_img ? *reinterpret_cast<const f32x4v*>(
@@ -693,13 +694,19 @@ __global__ void __launch_bounds__(WINO_THREADS) wino_conv8s_kernel(const WinoArg
 #include "conv_wino_abl.inc"
 #endif
 
+// pixel tiles (workgroups per channel tile and chunk range) of a launch: 128-pixel regions of the images, or for maps below 128
+// pixels groups of nseg whole images - 128 pixels too except on 4x4 maps, whose groups are seven images = 112 pixels
+inline int wino_tiles_m(int batch, int h, int w, int nseg) {
+    return h * w >= 128 ? (int)cdiv((long long)batch * h * w, 128) : (int)cdiv(batch, nseg);
+}
+
 template <int ABL = 0, bool GNF = false, bool ERAW = false, int LA = 2, bool TAIL = false, int NL = 3, bool SH = false>
 int launch_wino8s(const WinoArgs& a, hipStream_t stream, const char* name) {
     constexpr size_t LDS = (size_t)VBYTES / 3 * NL + 2 * (size_t)4 * 64 * 128;
     static_assert(LDS <= 163840, "LDS budget");
     if (int st = psld_lds_once<&wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL, SH>>(LDS, name)) return st;
     // the kernel finds its (chunk range, channel tile, pixel tile) from tiles_m and lg_ksplit, not from gridDim
-    PSLD_CHECK_ARG(a.tiles_m == cdiv(a.M, 128) && (1 << a.lg_ksplit) == (a.ksplit > 1 ? a.ksplit : 1),
+    PSLD_CHECK_ARG(a.tiles_m == wino_tiles_m(a.B, a.H, a.W, a.nseg) && (1 << a.lg_ksplit) == (a.ksplit > 1 ? a.ksplit : 1),
                    "%s: launch geometry not filled in (tiles_m %d, ksplit %d)", name, a.tiles_m, a.ksplit);
     dim3 grid((unsigned)(a.tiles_m * cdiv(a.N, 128) * (a.ksplit > 1 ? a.ksplit : 1)));
     hipLaunchKernelGGL((wino_conv8s_kernel<ABL, GNF, ERAW, LA, TAIL, NL, SH>), grid, dim3(WINO_THREADS), LDS, stream, a);
@@ -723,6 +730,10 @@ bool wino_geometry(int h, int w, int* nseg, int* rps, int* halo_px) {
     if (w == 128) {     // 128-wide maps: 4 x 32 pixel blocks only (the 64-wide rule below, four blocks per row band)
         *nseg = 1; *rps = 4; *halo_px = 6 * 34;
         return h % 4 == 0;
+    }
+    if (w == 4) {       // 4x4 maps: seven images of 6 x 6 halo pixels per workgroup (252 of the raw image's 256), 28 of its 32 tiles
+        *nseg = 7; *rps = 4; *halo_px = 7 * 36;
+        return h == 4;
     }
     if (w != 8 && w != 16 && w != 32 && w != 64) return false;
     if (h % 2) return false;
@@ -871,7 +882,9 @@ extern "C" int psld_conv3x3_wino_f32(const float* x1, int c1, const float* x2, i
 // K splits a launch of this shape takes when it is given a workspace (1: none) and the bytes that workspace needs
 extern "C" int psld_conv3x3_wino_ksplit(int c1, int c2, int batch, int h, int w, int cout) {
     if (!psld_conv3x3_wino_supported(c1, c2, batch, h, w, cout)) return 1;
-    const int tiles = cdiv((long long)batch * h * w, 128) * cdiv(cout, 128), chunks = (c1 + c2) / 32;
+    int nseg, rps, halo;
+    wino_geometry(h, w, &nseg, &rps, &halo);
+    const int tiles = wino_tiles_m(batch, h, w, nseg) * cdiv(cout, 128), chunks = (c1 + c2) / 32;
     const int cus = wino_cu_count();
     int ks = 1;
     // one workgroup per CU: a grid below half a round leaves CUs idle - split the channel chunks so that it fills one round
@@ -1028,7 +1041,7 @@ int wino_conv(const float* x1, int c1, const float* x2, int c2, int batch, int h
         halo_px = 6 * 34;
     }
     // the kernel's divisors (WinoArgs): every one a power of two or on the proven multiply-shift list
-    a.tiles_m = cdiv(a.M, 128);
+    a.tiles_m = wino_tiles_m(batch, h, w, a.nseg);
     a.lg_tiles_x = wino_lg2(a.cw >> 1);
     a.lg_tps = wino_lg2((a.rps >> 1) * (a.cw >> 1));
     a.lg_xblocks = wino_lg2(w / a.cw);

@@ -494,7 +494,9 @@ static bool ww_width_ok(int c) { return c >= 128 && c % 32 == 0; }
 
 extern "C" int psld_conv3x3_wgrad_wino_supported(int cout, int cin, int cin2, int batch, int h, int w) {
     if (batch <= 0 || cin2 < 0 || !ww_width_ok(cout) || !ww_width_ok(cin) || (cin2 && (cin % WW_CI || !ww_width_ok(cin2)))) return 0;
-    if (h != w || !(w == 8 || w == 16 || w == 32 || w == 64 || w == 128)) return 0;
+    if (h != w || !(w == 4 || w == 8 || w == 16 || w == 32 || w == 64 || w == 128)) return 0;
+    // whole K tiles of 32 Winograd tiles: on 4x4 maps (four tiles an image, a K tile = 16 tile rows of two = eight images)
+    // batches that are multiples of 8
     return ((long long)batch * h * w / 4) % 32 == 0;
 }
 

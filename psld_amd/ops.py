@@ -493,6 +493,27 @@ def conv3x3_wino_f16s(x1: Tensor, x2: Optional[Tensor], ufrag: Tensor, cout: int
 
 
 _WINO_MODE = None     # 0: never, 1: where it pays (default), 2: wherever the kernel takes the shape (tests)
+# 4x4 maps (conv_wino.hip: seven images per workgroup; wgrad_wino.hip: eight images per K tile) are an OPT-IN of their own,
+# set_winograd_4x4(): 0 (default) keeps them on the fp32 tile engine under every PSLD_WINOGRAD / PSLD_WGRAD_WINOGRAD mode, as
+# before the kernels took them; 1: Winograd form from the smallest batch at which the launch measured not slower than the tile
+# engine's (forward / data gradient, weight gradient; tools/bench_c10abl.py, profiles/r14/c10_ablation.md); 2: every supported
+# shape.  PSLD_WINOGRAD=0 / PSLD_WGRAD_WINOGRAD=0 switch the respective direction off whatever this says.
+_WINO_4X4_MODE = 0
+WINO_4X4_MIN_BATCH = 8
+WGRAD_WINO_4X4_MIN_BATCH = 8
+
+
+def set_winograd_4x4(mode: Optional[int]):
+    """4x4 maps on the Winograd kernels for this process: 0 / None never (default), 1 where measured not slower than the tile
+    engine (batch >= 8), 2 wherever the kernels take the shape; see conv3x3_wino_wanted / conv3x3_wgrad_wino_wanted."""
+    global _WINO_4X4_MODE
+    _WINO_4X4_MODE = int(mode or 0)
+    conv3x3_wino_wanted.cache_clear()
+    conv3x3_wgrad_wino_wanted.cache_clear()
+
+
+def winograd_4x4() -> int:
+    return _WINO_4X4_MODE
 
 
 def set_winograd(mode: Optional[int]):
@@ -518,6 +539,10 @@ def conv3x3_wino_wanted(c1: int, c2: int, b: int, h: int, w: int, cout: int, spl
     mode = _WINO_MODE if _WINO_MODE is not None else int(os.environ.get("PSLD_WINOGRAD", "1"))
     if mode == 0 or not conv3x3_wino_supported(c1, c2, b, h, w, cout):
         return False
+    if h == 4 and w == 4:
+        # 4x4 maps: no direct limb kernel takes them, the alternative is the fp32 tile engine, and "one full round" never
+        # happens at the networks' batches - their own opt-in (set_winograd_4x4), whatever ``mode`` says beyond "not 0"
+        return _WINO_4X4_MODE == 2 or (_WINO_4X4_MODE == 1 and b >= WINO_4X4_MIN_BATCH)
     if mode == 2:
         return True
     tiles = (b * h * w // 128) * -(-cout // 128)          # a channel tail (cout % 128, csrc/conv_wino.hip) counts as a tile
@@ -892,6 +917,8 @@ def conv3x3_wgrad_wino_wanted(cout: int, cin: int, cin2: int, b: int, h: int, w:
     mode = _WGRAD_WINO_MODE if _WGRAD_WINO_MODE is not None else int(os.environ.get("PSLD_WGRAD_WINOGRAD", "1"))
     if mode == 0 or not conv3x3_wgrad_wino_supported(cout, cin, cin2, b, h, w):
         return False
+    if h == 4 and w == 4:   # 4x4 maps (the tile engine is the alternative): their own opt-in, set_winograd_4x4
+        return _WINO_4X4_MODE == 2 or (_WINO_4X4_MODE == 1 and b >= WGRAD_WINO_4X4_MIN_BATCH)
     if mode == 2:
         return True
     if not (conv3x3_wgrad_split_supported(cout, cin, b, h, w) and (cin2 == 0 or conv3x3_wgrad_split_supported(cout, cin2, b, h, w))):

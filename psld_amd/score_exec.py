@@ -525,7 +525,7 @@ class _Exec(_ExecBase):
             return False
         b, h, w, c1 = a.v.shape
         return R.cat_ok(self.split, self.record, c1, bnode.v.shape[-1], b, h, w, mod.out_ch, mod.up, mod.down,
-                        mod.has_shortcut)
+                        mod.has_shortcut, self.wino_wanted)
 
     def concat(self, a: _Node, bnode: _Node, consumer=None):
         """torch.cat([h, hs.pop()], dim=1) (ncsnpp.py:374) in NHWC; not materialised when ``consumer`` reads two sources."""

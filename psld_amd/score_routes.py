@@ -237,16 +237,24 @@ def block_plan(split: bool, limb_planes: bool, record: bool, dropout: bool, c1: 
 
 
 def cat_ok(split: bool, record: bool, c1: int, c2: int, b: int, h: int, w: int, cout: int, up: bool, down: bool,
-           has_shortcut: bool) -> bool:
+           has_shortcut: bool, wino=wino_wanted) -> bool:
     """Can a residual block read the concatenation of a c1- and a c2-channel source without it being materialised?  Needs
     the two-source direct limb forward kernels and, when recording, per-source direct limb data gradients (whatever form
-    ``block_plan`` then runs them in) and a two-source weight gradient."""
+    ``block_plan`` then runs them in) and a two-source weight gradient.  On maps below the direct kernels' geometries (4x4)
+    the Winograd kernels stand in for them where ``wino`` wants every one of those launches: ``block_plan`` then runs the
+    forward, both data gradients and the two-source weight gradient in Winograd form."""
     if not split or up or down or not has_shortcut:
         return False
     m = b * h * w
     cpg = (c1 + c2) // ops.gn_groups(c1 + c2)
     if c1 % 128 or c2 % 128 or c1 % cpg or c2 % cpg or (c1 // 4) > 256 or (c2 // 4) > 256:
         return False
+    if h == 4 and w == 4:
+        ok = wino(c1, c2, b, h, w, cout) and ops.gemm_split_supported(c1, c2, m, cout)
+        if record:
+            ok = ok and all(wino(cout, 0, b, h, w, c) and ops.gemm_split_supported(cout, 0, m, c) for c in (c1, c2)) and \
+                wgrad_route(split, cout, c1, c2, b, h, w, False) == WINO and ops.gemm_tn_split_supported(cout, c1, m)
+        return ok
     ok = limb_takes(split, c1, c2, b, h, w, cout) and ops.gemm_split_supported(c1, c2, m, cout)
     if record:
         ok = ok and all(limb_takes(split, cout, 0, b, h, w, c) and ops.gemm_split_supported(cout, 0, m, c) and

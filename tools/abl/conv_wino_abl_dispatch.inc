@@ -17,6 +17,9 @@
         // instead of handing the consumer statistics in the wrong layout
         PSLD_CHECK_ARG(!(e.gn_part && e.gn_fine == 4) || !(qk || persist || w4 != 2),
                        "%s: the ablation variants (PSLD_WINO_Q / PSLD_WINO_PERSIST / PSLD_WINO_W4) do not write 4-channel GroupNorm sums", name);
+        // the variants of conv_wino_abl.inc count 128-pixel tiles (cdiv(M, 128)); 4x4 maps run seven images = 112 pixels per workgroup
+        PSLD_CHECK_ARG(!(h == 4 && w == 4) || !(qk || persist || w4 != 2),
+                       "%s: the ablation variants (PSLD_WINO_Q / PSLD_WINO_PERSIST / PSLD_WINO_W4) do not take 4x4 maps", name);
         if (qk) {
             if (abl == 1) return launch_wino8q<1>(a, stream, name);
             if (abl == 2) return launch_wino8q<2>(a, stream, name);
