@@ -848,6 +848,20 @@ int psld_softmax_xent_f32(const float* logits, const long long* labels, int rows
  * mask [B,C,HW] f32 in {0,1} applied to both halves; optionally refreshes the f32 copy the network reads. */
 int psld_mask_combine_f64(double* x, const double* u, const float* mask, int batch, int c, int hw,
                           float* x_f32_out, hipStream_t stream);
+/* Class conditioning (model.score_fn.label_classes = K > 0; no counterpart in the reference, whose ncsnpp.py:288 leaves it as
+ * a TODO).  table [n_rows = K + 1][d] f32 is NCSNpp.label_emb, row null_row = K the "no label" row; labels int64 [batch] in
+ * [0, n_rows) (anything else is a contract violation the CALLER excludes: the add kernel skips such a sample, the gradient
+ * kernel counts it for no row); drop (may be NULL) uint8 [batch]: non-zero -> the sample reads null_row instead of its label.
+ * add:  temb[i][:] += table[lab_i][:] in place on the [batch][d] time embedding - one fp32 add per element.
+ * grad: dtable[r][:] = sum_{i : lab_i = r} dtemb[i][:] for EVERY row r (rows nobody selects are written as zeros), summed in
+ *       sample order without atomics (bitwise reproducible); accumulate != 0: dtable[r][:] += that sum. */
+int psld_label_embed_add_f32(float* temb, const float* table, const long long* labels, const unsigned char* drop,
+                             int batch, int d, int n_rows, int null_row, hipStream_t stream);
+int psld_label_embed_grad_f32(const float* dtemb, const long long* labels, const unsigned char* drop, int batch, int d,
+                              int n_rows, int null_row, float* dtable, int accumulate, hipStream_t stream);
+/* Classifier-free guidance: eps2 [2n] f32 holds the conditional network output in [0, n) and the unconditional one in
+ * [n, 2n); out[i] = u + scale * (c - u) (one subtraction, one fused multiply-add). */
+int psld_cfg_combine_f32(const float* eps2, float scale, float* out, long long n, hipStream_t stream);
 int psld_f64_to_f32(const double* x, float* y, long long n, hipStream_t stream);
 int psld_f32_to_f64(const float* x, double* y, long long n, hipStream_t stream);
 

@@ -234,6 +234,9 @@ SIGNATURES = {
     "psld_pf_div_rhs_f64": (I, [P, P, P, P, C.POINTER(EmCoeffs), D, I, I, I, P, P, P]),
     "psld_gauss_logp_f64": (I, [P, D, D, I, I, I, I, P, P, P]),
     "psld_softmax_xent_f32": (I, [P, P, I, I, F, F, P, P, P, P]),
+    "psld_label_embed_add_f32": (I, [P, P, P, P, I, I, I, I, P]),
+    "psld_label_embed_grad_f32": (I, [P, P, P, I, I, I, I, P, I, P]),
+    "psld_cfg_combine_f32": (I, [P, F, P, LL, P]),
     "psld_f64_to_f32": (I, [P, P, LL, P]),
     "psld_f32_to_f64": (I, [P, P, LL, P]),
     "psld_grad_norm_f32": (I, [P, LL, P, P, P]),

@@ -8,6 +8,9 @@
                                                                            (main/train_clf.py:24-110)
     python -m psld_amd.cli cc_sample --config c10_sota --clf-config clf_c10 [dataset.clf.evaluation.label_to_sample=9 ...]
                                                                            (main/eval/class_cond_sample.py:29-138)
+    python -m psld_amd.cli train  --config c10_sota model.score_fn.label_classes=10 --labels y.npy --data x.npy
+    python -m psld_amd.cli sample --config c10_sota model.score_fn.label_classes=10 --label 3 --cfg-scale 2.0
+                                                                           (no counterpart: classifier-free guidance, psld_amd/guidance.py)
     python -m psld_amd.cli bpd --config c10_sota --data x.npy --ckpt last.ckpt [--n-probes N --n-momentum N --rtol R --atol A]
                                                                            (no counterpart: psld_amd/likelihood.py)
 
@@ -122,8 +125,13 @@ def load_checkpoint(path, score_fn, ema, optim=None, sched=None):
     sd = ck["state_dict"] if "state_dict" in ck else ck
     s1 = {k[len("score_fn."):]: v for k, v in sd.items() if k.startswith("score_fn.")}
     s2 = {k[len("ema_score_fn."):]: v for k, v in sd.items() if k.startswith("ema_score_fn.")}
-    score_fn.load_state_dict(s1, strict=True)
-    ema.load_state_dict(s2 if s2 else s1, strict=True)
+    s2 = s2 if s2 else s1
+    for net, state in ((score_fn, s1), (ema, s2)):
+        # an unconditional checkpoint loads into a label-conditioned network (that one direction only): the embedding
+        # table keeps its zero initialisation, i.e. the network computes what the checkpoint's did
+        if getattr(net, "label_emb", None) is not None and "label_emb" not in state:
+            state["label_emb"] = torch.zeros_like(net.label_emb, device="cpu")
+        net.load_state_dict(state, strict=True)
     step = ck.get("global_step", 0)
     if optim is not None:
         states = ck.get("optimizer_states") or []
@@ -184,6 +192,50 @@ def epoch_indices(n_items: int, batch_size: int, seed: int, epoch: int, rank: in
     return mine[:mine.numel() // batch_size * batch_size]
 
 
+def label_classes_of(cfg) -> int:
+    return int(cfg.model.score_fn.get("label_classes", 0) or 0)
+
+
+def _train_labels(cfg, args, n_items: int, device):
+    """int64 [N] class labels of the ``train`` command (``--labels file.npy | synthetic``): required by a network with
+    ``model.score_fn.label_classes``, refused by one without."""
+    k = label_classes_of(cfg)
+    if k == 0:
+        if args.labels is not None:
+            raise SystemExit("train: --labels needs model.score_fn.label_classes=K (the network takes no labels)")
+        return None
+    if args.labels is None:
+        raise SystemExit("train: model.score_fn.label_classes is set: --labels file.npy|synthetic is required")
+    if args.labels != "synthetic":
+        labels = torch.from_numpy(np.load(args.labels).astype(np.int64))
+        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= k):
+            raise SystemExit(f"train: --labels holds a label outside [0, {k})")
+    else:
+        labels = torch.randint(0, k, (n_items,), generator=torch.Generator().manual_seed(4321))   # one label set for all ranks
+    assert labels.shape == (n_items,), (tuple(labels.shape), n_items)
+    return labels.to(device)
+
+
+def apply_label_args(cfg, args):
+    """``--label N`` / ``--cfg-scale S`` of ``sample`` and ``inpaint``: spellings of ``evaluation.label_to_sample`` /
+    ``evaluation.cfg_scale`` (classifier-free guidance, psld_amd.guidance); both need a label-conditioned network."""
+    if getattr(args, "label", None) is not None:
+        cfg.evaluation.label_to_sample = args.label
+    if getattr(args, "cfg_scale", None) is not None:
+        cfg.evaluation.cfg_scale = args.cfg_scale
+    ev, k = cfg.evaluation, label_classes_of(cfg)
+    label = ev.get("label_to_sample", None)
+    if label is None:
+        if ev.get("cfg_scale", None) is not None:
+            raise SystemExit("--cfg-scale / evaluation.cfg_scale needs --label N")
+        return cfg
+    if k == 0:
+        raise SystemExit("--label / evaluation.label_to_sample needs model.score_fn.label_classes=K")
+    if not 0 <= int(label) < k:
+        raise SystemExit(f"--label {label} outside [0, {k})")
+    return cfg
+
+
 def train(args, overrides):
     from psld_amd import config as C, ops
     from psld_amd.ddp import BucketReducer, init_distributed
@@ -210,6 +262,7 @@ def train(args, overrides):
         step, epoch0 = load_checkpoint(cfg.training.restore_path, score_fn, ema, optim, sched)
         score_fn.to(dev), ema.to(dev)
     data = _dataset(cfg, args, dev, rank)
+    labels = _train_labels(cfg, args, data.shape[0], dev)
     bs = min(cfg.training.batch_size, data.shape[0])                      # train_sde.py:101-102
     gen = torch.Generator(device=dev).manual_seed(cfg.training.seed + rank)   # horizontal flips: per-rank stream
     ckdir = os.path.join(cfg.training.results_dir or "psld_results", "checkpoints")
@@ -221,7 +274,7 @@ def train(args, overrides):
             idx = perm[i:i + bs]
             flip = (torch.rand(bs, device=dev, generator=gen) < 0.5).to(torch.uint8) if cfg.data.hflip else None
             x0 = ops.uint8_to_images(data[idx].contiguous(), norm=cfg.data.norm, flip=flip)
-            loss = wrapper.training_step(x0, step)
+            loss = wrapper.training_step(x0 if labels is None else (x0, labels[idx].contiguous()), step)
             if ema_cb is not None:
                 ema_cb.on_train_batch_end(None, wrapper)
             step += 1
@@ -250,7 +303,7 @@ def sample(args, overrides):
     rank, local, world = init_distributed()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    cfg = parse_overrides(getattr(C, args.config)(), overrides)
+    cfg = apply_label_args(parse_overrides(getattr(C, args.config)(), overrides), args)
     ev = cfg.evaluation
     score_fn, ema, sde = build(cfg, dev)
     if ev.chkpt_path:
@@ -442,7 +495,7 @@ def inpaint(args, overrides):
     rank, local, world = init_distributed()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    cfg = parse_overrides(getattr(C, args.config)(), overrides)
+    cfg = apply_label_args(parse_overrides(getattr(C, args.config)(), overrides), args)
     ev = cfg.evaluation
     score_fn, ema, sde = build(cfg, dev)
     if ev.chkpt_path:
@@ -536,11 +589,20 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--log-every", type=int, default=10)
         p.add_argument("--mask", default="synthetic", help="inpaint: uint8 [N,H,W,3] .npy (1 = keep) or 'synthetic'")
         p.add_argument("--clf-config", default="clf_c10", choices=["clf_c10", "clf_afhqv2_128", "clf_default", "tiny_clf"])
-        p.add_argument("--labels", default="synthetic", help="train_clf: int [N] .npy or 'synthetic'")
+        p.add_argument("--labels", default=None if name == "train" else "synthetic",
+                       help="train_clf: int [N] .npy or 'synthetic'; train: the same, required with (and only with) "
+                            "model.score_fn.label_classes=K")
         p.add_argument("--winograd-4x4", type=int, default=0, choices=[0, 1, 2],
                        help="3x3 convolutions on 4x4 maps (the last level of c10_ablation, c10_vpsde, yaml_default, clf_c10) on the "
                             "Winograd limb kernels (ops.set_winograd_4x4): 0 = the fp32 tile engine (default), 1 = from batch 8 up, "
                             "where the launches measured faster than the tile engine's, 2 = every shape the kernels take")
+        if name in ("sample", "inpaint"):
+            p.add_argument("--label", type=int, default=None, metavar="N",
+                           help="class to sample from a label-conditioned network (model.score_fn.label_classes=K): "
+                                "evaluation.label_to_sample")
+            p.add_argument("--cfg-scale", type=float, default=None, metavar="S",
+                           help="classifier-free guidance scale (evaluation.cfg_scale, default 1.0 = plain conditional "
+                                "sampling; 0 = unconditional; other values run the doubled batch)")
         if name in ("sample", "cc_sample", "inpaint"):
             p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32", "f16"],
                            help="arithmetic of the network evaluations (ops.set_math_mode; default: the process's mode, "

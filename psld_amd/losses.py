@@ -14,6 +14,32 @@ from . import ops
 from .registry import get_module, register_module
 
 
+def label_dropout_p(config) -> float:
+    """The label-dropout probability of a training configuration: ``training.label_dropout`` (absent: 0.1) for a network
+    with ``model.score_fn.label_classes`` > 0, else 0 - the key is ignored for a network without labels."""
+    if int(config.model.score_fn.get("label_classes", 0) or 0) <= 0:
+        return 0.0
+    return float(config.training.get("label_dropout", 0.1))
+
+
+def label_drop_mask(batch: int, p: float, device=None, generator=None):
+    """Which samples of a batch train without their label (classifier-free guidance): ``u < p`` for ONE ``torch.rand(batch)``
+    draw, or None - and no draw at all - for p <= 0.  The callers make this draw after the loss's other draws (momentum,
+    eps), so a run without labels consumes the RNG stream exactly as it always did."""
+    if p <= 0:
+        return None
+    return torch.rand(batch, device=device, generator=generator) < p
+
+
+def _conditional(score_fn, y, p: float, batch: int, device, drop=None):
+    """``score_fn`` with the labels (and this step's dropout mask) bound; ``score_fn`` itself when there are none."""
+    if y is None:
+        return score_fn
+    if drop is None:
+        drop = label_drop_mask(batch, p, device)
+    return lambda z, t: score_fn(z, t, y=y, drop=drop)
+
+
 class _SqErr(torch.autograd.Function):
     """loss = mean|sum (target - pred)^2; the kernel also emits d loss / d pred."""
 
@@ -46,14 +72,18 @@ class PSLDScoreLoss(nn.Module):
         self.mode = config.training.mode
         self.decomp_mode = config.model.sde.decomp_mode
         self.reduce_strategy = "mean" if config.training.loss.reduce_mean else "sum"
+        self.label_dropout = label_dropout_p(config)
 
     def prefetch(self, t):
         """The perturbation coefficients ``forward`` will ask for (SDEWrapper computes and checks them early)."""
         self.sde.prefetch_coeffs(t, 0, self.sde.mm_0 if self.mode == "hsm" else 0.0)
 
-    def forward(self, x_0, t, score_fn, eps=None, m_draw=None):
+    def forward(self, x_0, t, score_fn, eps=None, m_draw=None, y=None, drop=None):
         """``eps`` / ``m_draw``: the two normal draws of losses.py:96,108 when the caller has made them already (tests;
-        the captured training step, which keeps every RNG call outside its hipGraph)."""
+        the captured training step, which keeps every RNG call outside its hipGraph).
+        ``y``: int64 [B] class labels for a network with ``label_classes``; each sample runs without its label with
+        probability ``training.label_dropout`` (``drop``: that mask when the caller has drawn it already) - the one extra
+        ``torch.rand(B)`` comes AFTER the momentum and eps draws."""
         sde = self.sde
         # losses.py:96-102: DSM samples the momentum, HSM marginalises it; the momentum is drawn in BOTH modes (HSM
         # discards it), so a seeded run consumes the device RNG stream exactly like the reference
@@ -67,6 +97,7 @@ class PSLDScoreLoss(nn.Module):
             eps = torch.randn(x_0.shape[0], 2 * x_0.shape[1], *x_0.shape[2:], device=x_0.device)
         assert eps.shape[1] == 2 * x_0.shape[1]
         eps = eps.contiguous()
+        score_fn = _conditional(score_fn, y, self.label_dropout, x_0.shape[0], x_0.device, drop)
         z_t = sde.perturb_f32(x_0, m_0, 0, mm_0, t, eps)                # losses.py:113-114
         t32 = ops.f64_to_f32(t.contiguous()) if t.dtype == torch.float64 else t.float()
         eps_pred = score_fn(z_t, t32)                                   # losses.py:115
@@ -111,12 +142,15 @@ class ScoreLoss(nn.Module):
         if self.weighting == "nll" and self.l_type != "l2":
             raise ValueError("l_type can only be `l2` when using nll weighting")       # losses.py:33-35
         self.reduce_strategy = "mean" if config.training.loss.reduce_mean else "sum"
+        self.label_dropout = label_dropout_p(config)
 
-    def forward(self, x_0, t, score_fn, eps=None):
+    def forward(self, x_0, t, score_fn, eps=None, y=None, drop=None):
+        """``y`` / ``drop``: as in PSLDScoreLoss.forward (the dropout draw follows the eps draw)."""
         if eps is None:
             eps = torch.randn_like(x_0)
         assert eps.shape == x_0.shape
         eps = eps.contiguous()
+        score_fn = _conditional(score_fn, y, self.label_dropout, x_0.shape[0], x_0.device, drop)
         x_t = self.sde.perturb_f32(x_0, t, eps)                          # losses.py:48-49
         t32 = ops.f64_to_f32(t.contiguous()) if t.dtype == torch.float64 else t.float()
         eps_pred = score_fn(x_t, t32)

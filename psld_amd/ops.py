@@ -1760,6 +1760,60 @@ def softmax_xent(logits: Tensor, labels: Tensor, loss_scale: float, grad_scale: 
     return loss, grad, correct
 
 
+def check_labels(labels: Tensor, rows: int):
+    """A label outside [0, rows) would index past the embedding table: guarded like softmax_xent's labels (a device-side
+    assert that fires when the stream reaches it, no host synchronisation)."""
+    torch._assert_async(((labels >= 0) & (labels < rows)).all(), f"label embedding: label outside [0, {rows})")
+
+
+def _label_args(table: Tensor, labels: Tensor, drop: Optional[Tensor], batch: int, verify: bool):
+    """Operands of the two label-embedding kernels.  ``verify`` False: the caller has run check_labels on these labels itself
+    (a stream capture, whose static label buffer is checked before every replay instead)."""
+    assert labels.shape == (batch,), (tuple(labels.shape), batch)
+    assert drop is None or drop.shape == (batch,), (tuple(drop.shape), batch)
+    if verify:
+        check_labels(labels, table.shape[0])
+    return _chk(labels, torch.int64).data_ptr(), (None if drop is None else _chk(drop, torch.uint8).data_ptr())
+
+
+def label_embed_add(temb: Tensor, table: Tensor, labels: Tensor, drop: Optional[Tensor] = None, verify: bool = True) -> Tensor:
+    """temb[i, :] += table[lab_i, :] in place; lab_i = the last row of ``table`` (the "no label" row) where ``drop[i]``, else
+    ``labels[i]``.  temb f32 [B, D], table f32 [K + 1, D], labels int64 [B] in [0, K], drop uint8 [B] or None."""
+    b, d = temb.shape
+    rows = table.shape[0]
+    assert table.shape == (rows, d), (tuple(table.shape), d)
+    lp, dp = _label_args(table, labels, drop, b, verify)
+    check(lib().psld_label_embed_add_f32(_chk(temb).data_ptr(), _chk(table).data_ptr(), lp, dp, b, d, rows, rows - 1,
+                                         _stream()), "psld_label_embed_add_f32")
+    return temb
+
+
+def label_embed_grad(dtemb: Tensor, labels: Tensor, drop: Optional[Tensor], dtable: Tensor, accumulate: bool = False,
+                     verify: bool = True) -> Tensor:
+    """dtable[r, :] (+)= sum of dtemb[i, :] over the samples with lab_i == r (lab_i as in label_embed_add), for every row of
+    ``dtable`` [K + 1, D]: rows without a sample are WRITTEN as zeros (left alone under ``accumulate``)."""
+    b, d = dtemb.shape
+    rows = dtable.shape[0]
+    assert dtable.shape == (rows, d), (tuple(dtable.shape), d)
+    lp, dp = _label_args(dtable, labels, drop, b, verify)
+    check(lib().psld_label_embed_grad_f32(_chk(dtemb).data_ptr(), lp, dp, b, d, rows, rows - 1, _chk(dtable).data_ptr(),
+                                          1 if accumulate else 0, _stream()), "psld_label_embed_grad_f32")
+    return dtable
+
+
+def cfg_combine(eps2: Tensor, scale: float, out: Optional[Tensor] = None) -> Tensor:
+    """Classifier-free guidance: ``eps2`` f32 [2B, ...] = the conditional outputs followed by the unconditional ones ->
+    out [B, ...] = u + scale * (c - u)."""
+    assert eps2.shape[0] % 2 == 0, tuple(eps2.shape)
+    shape = (eps2.shape[0] // 2,) + tuple(eps2.shape[1:])
+    if out is None:
+        out = torch.empty(shape, device=eps2.device, dtype=torch.float32)
+    assert tuple(out.shape) == shape
+    check(lib().psld_cfg_combine_f32(_chk(eps2).data_ptr(), float(scale), _chk(out).data_ptr(), out.numel(), _stream()),
+          "psld_cfg_combine_f32")
+    return out
+
+
 def mask_combine(x: Tensor, u: Tensor, mask: Tensor, x_f32: Optional[Tensor] = None):
     """x <- x*(1-mask) + u*mask in place on the f64 state [B,2C,H,W]; mask [B,C,H,W] f32 of {0,1}."""
     b, c2, h, w = x.shape

@@ -22,7 +22,8 @@ class _Exec(_ExecBase):
     """One forward (and, if ``record``, the tape of its backward) over NHWC tensors."""
 
     # -- time embedding (ncsnpp.py:289-313) ------------------------------------------------------
-    def time_embedding(self, t: Tensor):
+    def time_embedding(self, t: Tensor, lab: Optional[Tensor] = None, drop: Optional[Tensor] = None):
+        """``lab`` / ``drop`` (networks with label_classes, NCSNpp._labels): rows of ``label_emb`` and the dropout mask."""
         net = self.net
         mods = net.all_modules
         i = 0
@@ -38,6 +39,10 @@ class _Exec(_ExecBase):
         t1 = ops.linear(emb, l1.weight, l1.bias)
         s1 = ops.silu(t1)
         temb = ops.linear(s1, l2.weight, l2.bias)
+        if lab is not None:
+            # the one place the class label enters: temb += label_emb[lab] (row K where the sample runs without a label).
+            # Inside a stream capture the labels' range check is the capturer's (NCSNpp._graph_forward)
+            ops.label_embed_add(temb, net.label_emb.detach(), lab, drop, verify=not torch.cuda.is_current_stream_capturing())
         st = _Node(ops.silu(temb))
         self.temb_act = st
         b = t.shape[0]
@@ -100,6 +105,8 @@ class _Exec(_ExecBase):
             n2, k2 = l2.weight.shape
             ops.gemm_raw(1, 0, n2, k2, b, dtemb, n2, 0, s1, k2, 0, self.g(l2.weight), k2, 0)
             ops.colsum(dtemb, n2, 1, b, n2, self.g(l2.bias))
+            if lab is not None:         # every row of the table is written: rows without a sample get zeros
+                ops.label_embed_grad(dtemb, lab, drop, self.g(net.label_emb), verify=False)
             ds1 = torch.empty_like(s1)
             ops.gemm_raw(0, 0, b, k2, n2, dtemb, n2, 0, l2.weight, k2, 0, ds1, k2, 0)
             dt1 = ops.silu_bwd(t1, ds1)
@@ -553,14 +560,14 @@ class _Exec(_ExecBase):
         return cn
 
     # -- whole network (ncsnpp.py:287-438) --------------------------------------------------------------
-    def run(self, x: Tensor, t: Tensor) -> Tensor:
+    def run(self, x: Tensor, t: Tensor, lab: Optional[Tensor] = None, drop: Optional[Tensor] = None) -> Tensor:
         with ops.stream_scope():
-            return self._run(x, t)
+            return self._run(x, t, lab, drop)
 
-    def _run(self, x: Tensor, t: Tensor) -> Tensor:
+    def _run(self, x: Tensor, t: Tensor, lab: Optional[Tensor] = None, drop: Optional[Tensor] = None) -> Tensor:
         net = self.net
         mods = net.all_modules
-        mi = self.time_embedding(t)
+        mi = self.time_embedding(t, lab, drop)
         pin = net.progressive_input
         x_nhwc = ops.nchw_to_nhwc(x)
         stem = mods[mi]

@@ -65,11 +65,11 @@ class _Pending:
 
 class _NCSNppFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, t, anchor, net):
+    def forward(ctx, x, t, anchor, net, lab=None, drop=None):
         ex = _Exec(net, record=True)
         ex.watermark = net._watermark_hook
         ex.want_dx = bool(x.requires_grad)
-        y = ex.run(x, t)
+        y = ex.run(x, t, lab, drop)
         ctx.ex = ex
         ctx.net = net
         ctx.pending = _Pending(net)
@@ -85,7 +85,7 @@ class _NCSNppFn(torch.autograd.Function):
         ex.backward(gy)
         net._end_backward()
         ctx.pending.release()
-        return ex.dx_nchw, None, None, None
+        return ex.dx_nchw, None, None, None, None, None
 
 
 class _NCSNppParamFn(torch.autograd.Function):
@@ -95,10 +95,10 @@ class _NCSNppParamFn(torch.autograd.Function):
     ``_NCSNppFn`` assigns ``p.grad`` itself and never reaches those nodes."""
 
     @staticmethod
-    def forward(ctx, x, t, net, *params):
+    def forward(ctx, x, t, net, lab, drop, *params):
         ex = _Exec(net, record=True)
         ex.want_dx = bool(x.requires_grad)
-        y = ex.run(x, t)
+        y = ex.run(x, t, lab, drop)
         ctx.ex = ex
         ctx.net = net
         ctx.pending = _Pending(net)
@@ -116,7 +116,7 @@ class _NCSNppParamFn(torch.autograd.Function):
         grads = net._end_backward_visible()
         ctx.pending.release()
         assert len(grads) == ctx.n_params
-        return (ex.dx_nchw, None, None) + grads
+        return (ex.dx_nchw, None, None, None, None) + grads
 
 
 @register_module(category="score_fn", name="ncsnpp")
@@ -164,6 +164,18 @@ class NCSNpp(nn.Module):
         if self.noise_cond:
             modules.append(_linear(embed_dim, nf * 4))
             modules.append(_linear(nf * 4, nf * 4))
+        # class conditioning (no counterpart in the reference: ncsnpp.py:288 leaves it as a TODO): K classes -> one embedding
+        # table [K + 1, 4 nf] added to the time embedding, row K = "no label"; zero-initialised, so the network starts as its
+        # unconditional twin.  A DIRECT parameter: it precedes all_modules in parameters(), i.e. sits at the front of the flat
+        # buffers, where the gradients produced last in the backward pass (the time MLP's) belong (ddp.BucketReducer)
+        self.label_classes = int(sf.get("label_classes", 0) or 0)
+        self.label_emb = None
+        if self.label_classes:
+            if self.is_classifier:
+                raise ValueError("label_classes is a key of model.score_fn: the classifier's number of logits is clf_fn.n_cls")
+            if self.label_classes < 0 or not self.noise_cond:
+                raise ValueError("model.score_fn.label_classes needs a positive class count and noise_cond=True")
+            self.label_emb = nn.Parameter(torch.zeros(self.label_classes + 1, nf * 4))
         temb_dim = nf * 4 if self.noise_cond else None
         rb = lambda **kw: ResnetBlockBigGANpp(temb_dim=temb_dim, dropout=dropout, init_scale=init_scale, **kw)
 
@@ -553,7 +565,29 @@ class NCSNpp(nn.Module):
         self._reducer = reducer
 
     # ---- forward -----------------------------------------------------------------------------------------
-    def forward(self, x: Tensor, time_cond: Tensor) -> Tensor:
+    def _labels(self, x: Tensor, y: Optional[Tensor], drop: Optional[Tensor] = None):
+        """``(lab, drop)`` as the executor takes them: int64 [B] rows of ``label_emb`` (``y`` None: the "no label" row K for
+        every sample) and the optional uint8 [B] mask of the samples that read row K whatever their label; (None, None) for a
+        network without labels, which refuses ``y``."""
+        k = self.label_classes
+        if k == 0:
+            if y is not None or drop is not None:
+                raise ValueError("NCSNpp: y / drop given to a network built without model.score_fn.label_classes")
+            return None, None
+        b = x.shape[0]
+        if y is None:
+            return torch.full((b,), k, device=x.device, dtype=torch.int64), None
+        if not torch.is_tensor(y) or y.dtype != torch.int64 or tuple(y.shape) != (b,) or y.device != x.device:
+            raise ValueError(f"NCSNpp: y must be an int64 tensor of shape ({b},) on {x.device}")
+        if drop is not None:
+            if tuple(drop.shape) != (b,) or drop.device != x.device:
+                raise ValueError(f"NCSNpp: drop must be a mask of shape ({b},) on {x.device}")
+            drop = drop.to(torch.uint8).contiguous()
+        return y.contiguous(), drop
+
+    def forward(self, x: Tensor, time_cond: Tensor, y: Optional[Tensor] = None, drop: Optional[Tensor] = None) -> Tensor:
+        """``y`` (networks with ``label_classes`` = K > 0): int64 [B] class labels in [0, K] on the device, K and ``y=None``
+        meaning "no label"; ``drop``: optional mask [B], true where a sample is to run without its label (label dropout)."""
         if not x.is_cuda:
             raise RuntimeError("psld_amd.NCSNpp runs on MI355X only: the HIP extension has no CPU fallback "
                                "(use oracle/psld_oracle.py as the CPU checker)")
@@ -562,6 +596,7 @@ class NCSNpp(nn.Module):
         ops.lib()
         x = x.contiguous()
         t = time_cond.contiguous()
+        lab, drop = self._labels(x, y, drop)
         self.flatten_parameters()
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._params())
         if need_grad or (torch.is_grad_enabled() and x.requires_grad):
@@ -572,14 +607,14 @@ class NCSNpp(nn.Module):
                 if self._reducer is not None:
                     raise RuntimeError("psld_amd.NCSNpp: autograd_params (gradients through AccumulateGrad, for torch DDP) "
                                        "and a BucketReducer are two gradient exchanges: detach one of them")
-                return _NCSNppParamFn.apply(x, t, self, *self._trainable())
-            return _NCSNppFn.apply(x, t, self._anchor, self)
+                return _NCSNppParamFn.apply(x, t, self, lab, drop, *self._trainable())
+            return _NCSNppFn.apply(x, t, self._anchor, self, lab, drop)
         if self.use_graphs and not self.training:
-            return self._graph_forward(x, t)
+            return self._graph_forward(x, t, lab, drop)
         with torch.no_grad():
-            return _Exec(self, record=False).run(x, t)
+            return _Exec(self, record=False).run(x, t, lab, drop)
 
-    def vjp_input(self, x: Tensor, time_cond: Tensor, w: Tensor):
+    def vjp_input(self, x: Tensor, time_cond: Tensor, w: Tensor, y: Optional[Tensor] = None):
         """``(y, dx)``: the network output at ``(x, time_cond)`` and the vector-Jacobian product ``w^T dy/dx`` (NCHW, fp32),
         from ONE recorded forward in the module's current train / eval state (eval: no dropout) and one backward that runs
         the data-gradient launches alone (``_Exec.input_grad_only``).  No autograd node is built and no parameter gradient
@@ -592,15 +627,16 @@ class NCSNpp(nn.Module):
         if x.dtype != torch.float32 or time_cond.dtype != torch.float32 or w.dtype != torch.float32:
             raise RuntimeError("NCSNpp.vjp_input expects float32 x, time_cond and w")
         ops.lib()
+        lab, drop = self._labels(x, y)
         self.flatten_parameters()
         with torch.no_grad():
             ex = _Exec(self, record=True, input_grad_only=True)
             ex.want_dx = True
-            y = ex.run(x.detach().contiguous(), time_cond.detach().contiguous())
-            if w.shape != y.shape:
-                raise ValueError(f"vjp_input: cotangent of shape {tuple(w.shape)} for an output of shape {tuple(y.shape)}")
+            out = ex.run(x.detach().contiguous(), time_cond.detach().contiguous(), lab, drop)
+            if w.shape != out.shape:
+                raise ValueError(f"vjp_input: cotangent of shape {tuple(w.shape)} for an output of shape {tuple(out.shape)}")
             ex.backward(w.detach())
-        return y, ex.dx_nchw
+        return out, ex.dx_nchw
 
     # ---- HIP-graph replay of the inference forward (launch-bound regime: small sampling batches) ----------
     def enable_graphs(self, flag: bool = True):
@@ -612,30 +648,40 @@ class NCSNpp(nn.Module):
         if not flag:
             self._graphs = {}
 
-    def _graph_forward(self, x: Tensor, t: Tensor) -> Tensor:
+    def _graph_forward(self, x: Tensor, t: Tensor, lab: Optional[Tensor] = None, drop: Optional[Tensor] = None) -> Tensor:
+        if drop is not None:            # label dropout belongs to training passes: not worth a capture of its own
+            with torch.no_grad():
+                return _Exec(self, record=False).run(x, t, lab, drop)
         key = (tuple(x.shape), x.device.index, ops.pass_arith(False))     # a capture replays the launches of its arithmetic
         ent = self._graphs.get(key)
+        if lab is not None:
+            # the labels are a static input like x and t, refreshed before every replay; their range is checked here, outside
+            # the capture (the label kernels' own check is an assert on the stream)
+            ops.check_labels(lab, self.label_classes + 1)
         if ent is None:
             sx, st = x.clone(), t.clone()
+            sl = lab.clone() if lab is not None else None
             cur = torch.cuda.current_stream()
             warm = torch.cuda.Stream(device=x.device)
             warm.wait_stream(cur)
             with torch.cuda.stream(warm), torch.no_grad():
                 for _ in range(2):   # packs weights, sizes workspaces, one-time kernel attributes
-                    _Exec(self, record=False).run(sx, st)
+                    _Exec(self, record=False).run(sx, st, sl)
             cur.wait_stream(warm)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph), torch.no_grad():
-                sy = _Exec(self, record=False).run(sx, st)
-            ent = self._graphs[key] = [graph, sx, st, sy, None]
+                sy = _Exec(self, record=False).run(sx, st, sl)
+            ent = self._graphs[key] = [graph, sx, st, sy, None, sl]
             self.pin_scratch()       # the graph holds raw pointers into arenas / job tables: no eviction, no freeing from now on
-        graph, sx, st, sy, stamp = ent
+        graph, sx, st, sy, stamp, sl = ent
         now = (self._wcache.epoch, self._flat._version)
         if stamp != now:
             self._wcache.refresh(forward_only=True)              # refresh, in the same storage, what the graph reads
             ent[4] = now
         sx.copy_(x)
         st.copy_(t)
+        if sl is not None:
+            sl.copy_(lab)
         graph.replay()
         return sy.clone()
 

@@ -73,7 +73,7 @@ class SDEWrapper(_Base):
         if sampler_cls is not None:
             self.sampler = sampler_cls(
                 self.config, self.sde,
-                self.ema_score_fn if config.evaluation.sample_from == "target" else self.score_fn,
+                self._guided(self.ema_score_fn if config.evaluation.sample_from == "target" else self.score_fn),
                 corrector_fn=corrector_fn)
         self.eval_eps = self.config.evaluation.eval_eps
         self.denoise = self.config.evaluation.denoise
@@ -87,13 +87,24 @@ class SDEWrapper(_Base):
     def forward(self):
         pass
 
+    def _guided(self, net):
+        """The network the sampler calls: ``net`` itself, or - for a label-conditioned network with
+        ``evaluation.label_to_sample`` set - its classifier-free-guidance front (``evaluation.cfg_scale``, default 1)."""
+        ev = self.config.evaluation
+        label = ev.get("label_to_sample", None)
+        if label is None or int(getattr(net, "label_classes", 0) or 0) <= 0:
+            return net
+        from .guidance import CFGScoreFn
+        return CFGScoreFn(net, int(label), float(ev.get("cfg_scale", 1.0)))
+
     # ---- hipGraph-captured training step (launch-bound regime: small per-GPU batches) ---------------------------------
     def enable_graphs(self, flag: bool = True, warmup_steps: int = 2):
         """Capture the whole training step - perturb, forward, loss, backward tape, norm + clip + Adam - into a HIP
         graph per batch shape and replay it: one graph launch instead of ~2700 kernel launches issued from Python (the
         reference's per-GPU batch of 16, scripts_psld/.../train_uncond_psld.sh:25-30; measured in profiles/: worth a few
         percent on its own there - the eager step with the weight-gradient side stream is the faster mode at B = 16, the
-        graph pays below B ~ 8 where the host is the bound).
+        graph pays below B ~ 8 where the host is the bound).  The labels of a labelled batch ``(x_0, y)`` and the step's
+        label-dropout mask are two more static inputs, refreshed before each replay (the mask drawn after eps, as in the loss).
         Everything the reference draws per step (t, the discarded momentum draw, eps) and the dropout seed is drawn
         OUTSIDE the graph into static device buffers, in the reference's order, so a seeded run consumes the RNG stream
         exactly like the eager step; the step-dependent Adam scalars and the LR-schedule value travel through a 2-float
@@ -129,6 +140,10 @@ class SDEWrapper(_Base):
 
     def _graph_ok(self, batch) -> bool:
         optim = self.optimizers()
+        if isinstance(batch, (tuple, list)):        # (x_0, y): both on the device
+            if len(batch) != 2 or not torch.is_tensor(batch[1]) or not batch[1].is_cuda:
+                return False
+            batch = batch[0]
         return (getattr(self, "_graphs_on", False) and torch.is_tensor(batch) and batch.is_cuda
                 and isinstance(optim, FusedAdam) and getattr(self.score_fn, "_reducer", None) is None
                 and not self.score_fn._params_visible() and optim.ema_module is None
@@ -136,6 +151,8 @@ class SDEWrapper(_Base):
 
     def _graphed_step(self, batch):
         net, optim, sde = self.score_fn, self.optimizers(), self.sde
+        batch, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
+        p_drop = float(getattr(self.criterion, "label_dropout", 0.0)) if y is not None else 0.0
         if not hasattr(self, "_graph_steps"):
             self._graph_steps = {}
         # a capture replays its own launches: which ones a recording pass issues depends on its arithmetic (fp32 tile engine;
@@ -143,6 +160,8 @@ class SDEWrapper(_Base):
         # follows from the batch shape and this wrapper's loss, so the setting itself - None or the forced value - is the key.
         # (ops.pass_arith is the only reader of the math settings: two math modes with the same ladder replay the same capture)
         key = (tuple(batch.shape), batch.device.index, bool(net.training), ops.pass_arith(True), ops.grad_shift_setting())
+        if y is not None:           # a labelled step is another program (and another one again with a dropout mask)
+            key += ("labels", p_drop > 0)
         ent = self._graph_steps.get(key)
         if ent is None:
             ent = self._graph_steps[key] = {"seen": 0}
@@ -158,11 +177,19 @@ class SDEWrapper(_Base):
             ent["eps"] = torch.empty((b, 2 * c, h, w), device=dev, dtype=torch.float32)
             ent["seed"] = torch.zeros(1, device=dev, dtype=torch.int64)
             ent["hyper"] = torch.zeros(2, device=dev, dtype=torch.float32)
-        # the step's random draws, in the eager step's order (wrapper.py:72, losses.py:96,108, then the dropout seed)
+            ent["y"] = torch.empty_like(y) if y is not None else None
+            ent["drop"] = torch.zeros(b, device=dev, dtype=torch.uint8) if p_drop > 0 else None
+        # the step's random draws, in the eager step's order (wrapper.py:72, losses.py:96,108, the label-dropout mask, then
+        # the dropout seed)
         t_new, _ = self._draw_times(b, dev)       # includes the NaN check the captured step cannot make
         ent["t_"].copy_(t_new)
         torch.randn(batch.shape, device=dev, out=ent["m_draw"])
         torch.randn(ent["eps"].shape, device=dev, out=ent["eps"])
+        if y is not None:
+            ent["y"].copy_(y)
+            ops.check_labels(ent["y"], net.label_classes + 1)      # the capture's own label kernels do not (no assert in a graph)
+            if p_drop > 0:
+                ent["drop"].copy_(torch.rand(b, device=dev) < p_drop)
         if net.training and float(net.sf.dropout) > 0:
             ent["seed"].random_(0, 2 ** 62)
         ent["x0"].copy_(batch)
@@ -182,7 +209,8 @@ class SDEWrapper(_Base):
             try:
                 with torch.cuda.graph(graph):
                     t = ent["t_"] * (sde.T - self.train_eps) + self.train_eps
-                    loss = self.criterion(ent["x0"], t, net, eps=ent["eps"], m_draw=ent["m_draw"])
+                    labels = {} if y is None else dict(y=ent["y"], drop=ent["drop"])
+                    loss = self.criterion(ent["x0"], t, net, eps=ent["eps"], m_draw=ent["m_draw"], **labels)
                     net.mark_grads_stale()
                     loss.backward()
                     with torch.no_grad():
@@ -209,13 +237,14 @@ class SDEWrapper(_Base):
                 return loss
         optim = self.optimizers()
         lr_sched = self.lr_schedulers()
-        x_0 = batch
+        # (x_0, y): the reference's data.return_target convention - class labels for a network with label_classes
+        x_0, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
         if x_0.is_cuda:
             _, t = self._draw_times(x_0.shape[0], x_0.device)                   # wrapper.py:72-73
         else:
             t_ = torch.rand(x_0.shape[0], device=x_0.device, dtype=torch.float64)
             t = t_ * (self.sde.T - self.train_eps) + self.train_eps
-        loss = self.criterion(x_0, t, self.score_fn)
+        loss = self.criterion(x_0, t, self.score_fn) if y is None else self.criterion(x_0, t, self.score_fn, y=y)
         optim.zero_grad()
         self.manual_backward(loss)
         gc = self.config.training.optimizer.grad_clip
