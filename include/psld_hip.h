@@ -828,6 +828,29 @@ int psld_gauss_logp_f64(const double* u, double var_x, double var_m, int batch, 
 int psld_vp_score_loss(const float* eps, const float* eps_pred, const double* t, double beta0, double beta1,
                        int batch, long long per, int mode, int reduce_mean, void* loss, float* grad,
                        float grad_scale, void* workspace, hipStream_t stream);
+/* Likelihood-weighted PSLD score loss (the composition of main/losses.py:55-63 with psld.py:230-260 and
+ * :375-377, which the reference leaves as a TODO at losses.py:74).  coeffs: the table psld_perturb_coeffs_f64 wrote for this
+ * very t [batch] (entries [8..10] = the covariance); the inverse-transpose coefficients of get_inv_coeff are formed from it
+ * in f64 and cast to f32, the two scores and their difference e are f32 as in get_score, and
+ *   loss (f64) = sum_b sample_weight_b * sum (beta(t_b) gamma e_x^2 + beta(t_b) M nu e_m^2)   [/ N for reduce_mean]
+ * with N = batch*2c*hw in EVERY score mode (the element count of get_score's output, zero half included).
+ * score_mode 0: eps, eps_pred, grad [B,2c,hw]; 1 (score_m, lower) / 2 (score_x, upper): eps_pred and grad [B,c,hw], the
+ * target is the m / x half of eps [B,2c,hw].  sample_weight [batch] f64 or NULL (= 1).  grad (optional): d loss / d eps_pred
+ * formed in f64, rounded to f32 once, times grad_scale.  The summation order is fixed by (batch, c, hw): bitwise repeatable.
+ * workspace >= psld_reduce_workspace_bytes(batch*2*c*hw); batch <= 4096. */
+int psld_nll_score_loss(const float* eps, const float* eps_pred, const double* t, const double* coeffs,
+                        const double* sample_weight, const psld_sde_params_t* p, int score_mode, int batch, int c,
+                        int hw, int reduce_mean, double* loss, float* grad, float grad_scale, void* workspace,
+                        hipStream_t stream);
+/* Importance-sampled training times: the inverse CDF at u [batch] (f64, in [0, 1)) of the piecewise
+ * log-uniform density with masses mass [bins] (cum [bins + 1] their running sum, cum[0] = 0, cum[bins] = 1) on the bins
+ * between exp(log_edges [bins + 1]):  k = the largest bin with cum[k] <= u,  r = (u - cum[k]) / mass[k],
+ * t = clamp(exp(log_edges[k] + r * d_k), t_lo, t_hi), d_k = log_edges[k+1] - log_edges[k];
+ * weight = 1 / (q(t) span) = t d_k / (mass[k] span), so that E_q[weight f(t)] = E_{U[t_lo, t_hi]}[f(t)] for span =
+ * t_hi - t_lo.  Deterministic in u. */
+int psld_sample_times_f64(const double* u, int batch, const double* cum, const double* log_edges, const double* mass,
+                          int bins, double span, double t_lo, double t_hi, double* t, double* weight,
+                          hipStream_t stream);
 int psld_vp_perturb_f32(const float* x0, const float* eps, const double* t, double beta0, double beta1,
                         int batch, long long per_image, float* z_f32, double* u_f64, hipStream_t stream);
 int psld_vp_reverse_f64(double* x, const float* eps_pred, const double* z, double beta, double std, double dt,

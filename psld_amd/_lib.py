@@ -217,6 +217,8 @@ SIGNATURES = {
     "psld_em_step_f64": (I, [P, P, P, C.POINTER(EmCoeffs), I, I, I, P, P]),
     "psld_reverse_sde_f64": (I, [P, P, C.POINTER(EmCoeffs), I, I, I, P, P, P]),
     "psld_vp_score_loss": (I, [P, P, P, D, D, I, LL, I, I, P, P, F, P, P]),
+    "psld_nll_score_loss": (I, [P, P, P, P, P, C.POINTER(SdeParams), I, I, I, I, I, P, P, F, P, P]),
+    "psld_sample_times_f64": (I, [P, I, P, P, P, I, D, D, D, P, P, P]),
     "psld_reverse_sde_rows_f64": (I, [P, P, P, C.POINTER(SdeParams), D, D, I, I, I, I, I, P, P, P, P]),
     "psld_sscs_analytic_f64": (I, [P, P, C.POINTER(SscsCoeffs), I, I, I, P, P]),
     "psld_sscs_score_step_f64": (I, [P, P, C.POINTER(EmCoeffs), I, I, I, P]),

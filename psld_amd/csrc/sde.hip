@@ -658,6 +658,161 @@ extern "C" int psld_vp_score_loss(const float* eps, const float* eps_pred, const
     return PSLD_OK;
 }
 
+// ---- likelihood-weighted PSLD score loss and its time sampler ---------------------------------------
+// loss = sum_b sw_b sum_i g_x^2 e_x^2 + g_m^2 e_m^2 with e = score(eps_pred) - score(eps), score = -L_t^{-T} eps formed in
+// f32 with the f32-cast coefficients exactly as get_score does (psld.py:230-260), g^2 of psld.py:375-377 and every product
+// with it in f64.  One workgroup column per sample (blockIdx.y): the per-sample scalars are uniform over a workgroup, and
+// the partial sums - one per workgroup, added up by scaled_final_kernel in index order - make the loss bitwise repeatable.
+namespace {
+
+struct NllCoeffs {
+    float c11, c12, c21, c22;   // get_inv_coeff cast to f32 (psld.py:253-258)
+    double gx2, gm2;            // beta(t) gamma, beta(t) M nu
+};
+
+__device__ NllCoeffs nll_coeffs(const psld_sde_params_t& p, const double* __restrict__ k, double tt) {
+    const double xx = k[8], xm = k[9], mm = k[10];
+    const double det = xx * mm - xm * xm;
+    double c11, c12, c21, c22;
+    if (p.decomp_lower) {  // psld.py:194-198
+        c11 = sqrt(1.0 / xx);
+        c12 = -xm / (sqrt(xx) * sqrt(det));
+        c21 = 0.0;
+        c22 = sqrt(xx / det);
+    } else {  // psld.py:209-212
+        c22 = sqrt(1.0 / mm);
+        c21 = -xm / (sqrt(mm) * sqrt(det));
+        c11 = sqrt(mm / det);
+        c12 = 0.0;
+    }
+    const double beta = p.beta_0 + tt * (p.beta_1 - p.beta_0);
+    NllCoeffs o;
+    o.c11 = (float)c11; o.c12 = (float)c12; o.c21 = (float)c21; o.c22 = (float)c22;
+    o.gx2 = beta * p.gamma;
+    o.gm2 = beta * (1.0 / p.m_inv) * p.nu;
+    return o;
+}
+
+// mode 0: one thread per VEC consecutive pixels of one channel plane of the x half and the same pixels of the m half
+// (eps, eps_pred, grad [B,2C,HW]); modes 1 / 2: eps_pred and grad are [B,C,HW], the target is the m / x half of eps.
+template <int VEC>
+__global__ void nll_score_loss_kernel(const float* __restrict__ e, const float* __restrict__ ep,
+                                      const double* __restrict__ t, const double* __restrict__ coeffs,
+                                      const double* __restrict__ sw, const psld_sde_params_t p, int mode, long long plane,
+                                      double gdenom, double* __restrict__ part, float* __restrict__ grad, float gscale) {
+    typedef float fv __attribute__((ext_vector_type(VEC)));
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const NllCoeffs k = nll_coeffs(p, coeffs + (long long)b * COEFF_STRIDE, t[b]);
+    const double w = sw ? sw[b] : 1.0;
+    const double gs = 2.0 * w / gdenom;
+    const long long items = plane / VEC;
+    const long long e_base = (long long)b * 2 * items, p_base = (long long)b * (mode == 0 ? 2 : 1) * items;
+    double acc = 0.0;
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < items; r += (long long)gridDim.x * blockDim.x) {
+        if (mode == 0) {
+            const fv ex = reinterpret_cast<const fv*>(e)[e_base + r], em = reinterpret_cast<const fv*>(e)[e_base + items + r];
+            const fv px = reinterpret_cast<const fv*>(ep)[p_base + r], pm = reinterpret_cast<const fv*>(ep)[p_base + items + r];
+            fv gx, gm;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                const float dx = (-k.c11 * px[v] - k.c12 * pm[v]) - (-k.c11 * ex[v] - k.c12 * em[v]);
+                const float dm = (-k.c21 * px[v] - k.c22 * pm[v]) - (-k.c21 * ex[v] - k.c22 * em[v]);
+                const double ax = k.gx2 * (double)dx, am = k.gm2 * (double)dm;
+                acc += ax * (double)dx + am * (double)dm;
+                gx[v] = (float)(gs * (-(double)k.c11 * ax - (double)k.c21 * am)) * gscale;
+                gm[v] = (float)(gs * (-(double)k.c12 * ax - (double)k.c22 * am)) * gscale;
+            }
+            if (grad) {
+                reinterpret_cast<fv*>(grad)[p_base + r] = gx;
+                reinterpret_cast<fv*>(grad)[p_base + items + r] = gm;
+            }
+        } else {
+            const float c = mode == 1 ? k.c22 : k.c11;
+            const double g2 = mode == 1 ? k.gm2 : k.gx2;
+            const fv tv = reinterpret_cast<const fv*>(e)[e_base + (mode == 1 ? items : 0) + r];
+            const fv pv = reinterpret_cast<const fv*>(ep)[p_base + r];
+            fv gv;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                const float d = (-c * pv[v]) - (-c * tv[v]);
+                const double a = g2 * (double)d;
+                acc += a * (double)d;
+                gv[v] = (float)(gs * (-(double)c * a)) * gscale;
+            }
+            if (grad) reinterpret_cast<fv*>(grad)[p_base + r] = gv;
+        }
+    }
+    acc = wave_sum_d(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long long)b * gridDim.x + blockIdx.x] = w * (red[0] + red[1] + red[2] + red[3]);
+}
+
+// t = the inverse CDF at u of the piecewise log-uniform density with bin masses ``mass`` on the edges exp(log_edges);
+// weight = 1 / (q(t) span), q(t) = mass_k / (t (ln e_{k+1} - ln e_k))
+__global__ void sample_times_kernel(const double* __restrict__ u, int batch, const double* __restrict__ cum,
+                                    const double* __restrict__ log_edges, const double* __restrict__ mass, int bins,
+                                    double span, double t_lo, double t_hi, double* __restrict__ t,
+                                    double* __restrict__ weight) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch) return;
+    const double uu = u[i];
+    int lo = 0, hi = bins;   // the largest k < bins with cum[k] <= u (cum[0] = 0)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cum[mid] <= uu) lo = mid; else hi = mid;
+    }
+    const double pk = mass[lo], dl = log_edges[lo + 1] - log_edges[lo];
+    const double r = (uu - cum[lo]) / pk;
+    double tt = exp(log_edges[lo] + r * dl);
+    tt = tt < t_lo ? t_lo : (tt > t_hi ? t_hi : tt);
+    t[i] = tt;
+    weight[i] = tt * dl / (pk * span);
+}
+
+}  // namespace
+
+extern "C" int psld_nll_score_loss(const float* eps, const float* eps_pred, const double* t, const double* coeffs,
+                                   const double* sample_weight, const psld_sde_params_t* p, int score_mode, int batch,
+                                   int c, int hw, int reduce_mean, double* loss, float* grad, float grad_scale,
+                                   void* workspace, hipStream_t stream) {
+    PSLD_CHECK_ARG(eps && eps_pred && t && coeffs && p && loss && workspace && batch > 0 && batch <= 4096 && c > 0 &&
+                       hw > 0 && score_mode >= 0 && score_mode <= 2,
+                   "psld_nll_score_loss: bad args (1 <= batch <= 4096, score_mode 0..2)");
+    const long long plane = (long long)c * hw;
+    const double n = 2.0 * (double)plane * batch;   // the element count of get_score's output in EVERY mode
+    const double denom = reduce_mean ? n : 1.0;
+    const bool vec = hw % 4 == 0 && ((reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(eps_pred) |
+                                      reinterpret_cast<uintptr_t>(grad)) & 15) == 0;
+    const long long items = vec ? plane / 4 : plane;
+    long long bx = (items + 255) / 256;
+    const long long cap = 4096 / batch;   // batch * bx partial sums in a workspace of 4096
+    if (bx > cap) bx = cap;
+    double* part = reinterpret_cast<double*>(workspace);
+    if (vec)
+        hipLaunchKernelGGL(nll_score_loss_kernel<4>, dim3((unsigned)bx, batch), dim3(256), 0, stream, eps, eps_pred, t,
+                           coeffs, sample_weight, *p, score_mode, plane, denom, part, grad, grad_scale);
+    else
+        hipLaunchKernelGGL(nll_score_loss_kernel<1>, dim3((unsigned)bx, batch), dim3(256), 0, stream, eps, eps_pred, t,
+                           coeffs, sample_weight, *p, score_mode, plane, denom, part, grad, grad_scale);
+    PSLD_CHECK_LAUNCH("nll_score_loss_kernel");
+    hipLaunchKernelGGL(scaled_final_kernel, dim3(1), dim3(64), 0, stream, part, (int)(bx * batch), denom, loss, nullptr);
+    PSLD_CHECK_LAUNCH("scaled_final_kernel");
+    return PSLD_OK;
+}
+
+extern "C" int psld_sample_times_f64(const double* u, int batch, const double* cum, const double* log_edges,
+                                     const double* mass, int bins, double span, double t_lo, double t_hi, double* t,
+                                     double* weight, hipStream_t stream) {
+    PSLD_CHECK_ARG(u && cum && log_edges && mass && t && weight && batch > 0 && bins > 0 && span > 0 && t_lo <= t_hi,
+                   "psld_sample_times_f64: bad args");
+    hipLaunchKernelGGL(sample_times_kernel, dim3(cdiv(batch, 128)), dim3(128), 0, stream, u, batch, cum, log_edges, mass,
+                       bins, span, t_lo, t_hi, t, weight);
+    PSLD_CHECK_LAUNCH("psld_sample_times_f64");
+    return PSLD_OK;
+}
+
 // ---- probability-flow likelihood: probe, cotangent, augmented right-hand side, prior density ---------
 // Streaming kernels around one vector-Jacobian product of the network per right-hand-side evaluation.  The two reductions
 // (the divergence estimate, the Gaussian log-density) run as one workgroup per (sample, slice): the number of slices and

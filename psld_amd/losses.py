@@ -59,16 +59,58 @@ class _SqErr(torch.autograd.Function):
         return grad * g, None, None   # g is the 0-d upstream gradient (1.0 for loss.backward())
 
 
+def importance_sampling(config, sde) -> bool:
+    """``training.loss.importance_sampling`` (absent: false): draw the training times from the tabulated density of the
+    likelihood weight instead of uniformly.  Only with weighting 'nll' on a PSLD SDE: ValueError else."""
+    on = bool(config.training.loss.get("importance_sampling", False))
+    if on and not (config.training.loss.weighting == "nll" and getattr(sde, "type", "").startswith("psld")):
+        raise ValueError("training.loss.importance_sampling needs training.loss.weighting=nll and the PSLD SDE "
+                         f"(got weighting={config.training.loss.weighting!r}, sde={getattr(sde, 'type', type(sde).__name__)!r})")
+    return on
+
+
+def refuse_f16_nll():
+    """fp16 record math places its data gradients by a shift that assumes gradients of about 2/N; under the likelihood
+    weighting they are up to 1e5 times larger (w(t) ~ 1/t at t = train_eps)."""
+    if "f16" in ops.pass_arith(True):
+        raise ValueError("training.loss.weighting=nll cannot be combined with fp16 training math (--train-math f16 / "
+                         "PSLD_MATH=f16_train): its gradient shift assumes gradients of about 2/N; use bf16x3 or the default")
+
+
+class _NllScoreErr(torch.autograd.Function):
+    """loss (f64) = mean|sum of the g(t)^2-weighted score error, times the per-sample weights; the kernel also emits
+    d loss / d pred."""
+
+    @staticmethod
+    def forward(ctx, pred, eps, t, coeffs, t_weight, params, score_mode, reduce_mean):
+        loss, grad = ops.nll_score_loss(eps, pred.contiguous(), t, coeffs, t_weight, params, score_mode, reduce_mean,
+                                        want_grad=True)
+        ctx.save_for_backward(grad)
+        ctx.divisor = eps.numel() if reduce_mean else 1     # N = B*2C*H*W in every score mode
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        ops.set_loss_divisor(ctx.divisor)       # as _SqErr
+        return grad * g.to(grad.dtype), None, None, None, None, None, None, None
+
+
 @register_module(category="losses", name="psld_score_loss")
 class PSLDScoreLoss(nn.Module):
     def __init__(self, config, sde):
         super().__init__()
-        assert config.training.loss.weighting in ["fid"]
+        assert config.training.loss.weighting in ["fid", "nll"]
         assert config.training.mode in ["hsm", "dsm"]
         assert isinstance(sde, get_module("sde", "psld"))
         self.sde = sde
         self.l_type = config.training.loss.l_type
         self.weighting = config.training.loss.weighting
+        if self.weighting == "nll" and self.l_type != "l2":
+            raise ValueError("l_type can only be `l2` when using nll weighting")       # losses.py:88-90
+        self.importance_sampling = importance_sampling(config, sde)
+        if self.weighting == "nll":
+            refuse_f16_nll()
         self.mode = config.training.mode
         self.decomp_mode = config.model.sde.decomp_mode
         self.reduce_strategy = "mean" if config.training.loss.reduce_mean else "sum"
@@ -78,13 +120,18 @@ class PSLDScoreLoss(nn.Module):
         """The perturbation coefficients ``forward`` will ask for (SDEWrapper computes and checks them early)."""
         self.sde.prefetch_coeffs(t, 0, self.sde.mm_0 if self.mode == "hsm" else 0.0)
 
-    def forward(self, x_0, t, score_fn, eps=None, m_draw=None, y=None, drop=None):
+    def forward(self, x_0, t, score_fn, eps=None, m_draw=None, y=None, drop=None, t_weight=None):
         """``eps`` / ``m_draw``: the two normal draws of losses.py:96,108 when the caller has made them already (tests;
         the captured training step, which keeps every RNG call outside its hipGraph).
         ``y``: int64 [B] class labels for a network with ``label_classes``; each sample runs without its label with
         probability ``training.label_dropout`` (``drop``: that mask when the caller has drawn it already) - the one extra
-        ``torch.rand(B)`` comes AFTER the momentum and eps draws."""
+        ``torch.rand(B)`` comes AFTER the momentum and eps draws.
+        ``t_weight``: f64 [B] importance weights of the times (weighting 'nll' only): each sample's loss is multiplied by its
+        weight before the reduction."""
         sde = self.sde
+        if self.weighting == "nll":
+            return self._forward_nll(x_0, t, score_fn, eps, m_draw, y, drop, t_weight)
+        assert t_weight is None, "t_weight belongs to weighting 'nll'"
         # losses.py:96-102: DSM samples the momentum, HSM marginalises it; the momentum is drawn in BOTH modes (HSM
         # discards it), so a seeded run consumes the device RNG stream exactly like the reference
         if m_draw is None:
@@ -109,6 +156,32 @@ class PSLDScoreLoss(nn.Module):
             target = eps
         assert eps_pred.shape == target.shape
         return _SqErr.apply(eps_pred, target, self.reduce_strategy == "mean")
+
+    def _forward_nll(self, x_0, t, score_fn, eps, m_draw, y, drop, t_weight):
+        """The composition of losses.py:55-63 with PSLD's get_score and likelihood_weighting (the reference's TODO at
+        losses.py:74): same draws, same perturbation, then mean|sum of (score(eps_pred) - score(eps))^2 g(t)^2 in f64."""
+        sde = self.sde
+        refuse_f16_nll()
+        if m_draw is None:
+            m_draw = torch.randn_like(x_0)
+        if self.mode == "hsm":
+            m_0, mm_0 = None, sde.mm_0
+        else:
+            m_0, mm_0 = np.sqrt(sde.mm_0) * m_draw, 0.0
+        if eps is None:
+            eps = torch.randn(x_0.shape[0], 2 * x_0.shape[1], *x_0.shape[2:], device=x_0.device)
+        assert eps.shape[1] == 2 * x_0.shape[1]
+        eps = eps.contiguous()
+        score_fn = _conditional(score_fn, y, self.label_dropout, x_0.shape[0], x_0.device, drop)
+        tb = sde._coeff_table(t, 0, mm_0)       # ONE table: the perturbation and the score coefficients of the loss
+        z_t, _, _ = ops.perturb(x_0.contiguous(), None if m_0 is None else m_0.contiguous(), eps, tb, sde._params,
+                                want_f32=True)
+        t64 = t.to(torch.float64).contiguous()
+        eps_pred = score_fn(z_t, ops.f64_to_f32(t64))
+        if t_weight is not None:
+            t_weight = t_weight.to(torch.float64).contiguous()
+        return _NllScoreErr.apply(eps_pred, eps, t64, tb, t_weight, sde._params, sde._score_mode(),
+                                  self.reduce_strategy == "mean")
 
 
 class _VpScoreLoss(torch.autograd.Function):
@@ -141,6 +214,7 @@ class ScoreLoss(nn.Module):
         self.weighting = config.training.loss.weighting
         if self.weighting == "nll" and self.l_type != "l2":
             raise ValueError("l_type can only be `l2` when using nll weighting")       # losses.py:33-35
+        importance_sampling(config, sde)         # PSLD only: refuses the key here
         self.reduce_strategy = "mean" if config.training.loss.reduce_mean else "sum"
         self.label_dropout = label_dropout_p(config)
 

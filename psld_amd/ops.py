@@ -1579,6 +1579,39 @@ def vp_score_loss(eps: Tensor, eps_pred: Tensor, t: Optional[Tensor], beta0: flo
     return loss, grad
 
 
+def nll_score_loss(eps: Tensor, eps_pred: Tensor, t: Tensor, coeffs: Tensor, sample_weight: Optional[Tensor],
+                   params: SdeParams, score_mode: int, reduce_mean: bool, want_grad: bool):
+    """Likelihood-weighted PSLD score loss (f64 scalar) and d loss / d eps_pred; ``coeffs`` is the perturb_coeffs table of
+    ``t``, ``eps`` the full [B,2C,H,W] draw, ``eps_pred`` the network's output ([B,C,H,W] for score modes 1 / 2)."""
+    b, c2, h, w = eps.shape
+    c = c2 // 2
+    assert tuple(eps_pred.shape) == (b, c2 if score_mode == 0 else c, h, w), (tuple(eps.shape), tuple(eps_pred.shape))
+    assert tuple(coeffs.shape) == (b, COEFF_STRIDE) and t.numel() == b
+    assert sample_weight is None or sample_weight.numel() == b
+    loss = torch.empty((), device=eps.device, dtype=torch.float64)
+    grad = torch.empty_like(eps_pred) if want_grad else None
+    ws = workspace(lib().psld_reduce_workspace_bytes(eps.numel()), eps.device)
+    check(lib().psld_nll_score_loss(_chk(eps).data_ptr(), _chk(eps_pred).data_ptr(), _chk(t, torch.float64).data_ptr(),
+                                    _chk(coeffs, torch.float64).data_ptr(),
+                                    _chk(sample_weight, torch.float64).data_ptr() if sample_weight is not None else None,
+                                    C.byref(params), score_mode, b, c, h * w, 1 if reduce_mean else 0, loss.data_ptr(),
+                                    _p(grad), 1.0, ws.data_ptr(), _stream()), "psld_nll_score_loss")
+    return loss, grad
+
+
+def sample_times(u: Tensor, cum: Tensor, log_edges: Tensor, mass: Tensor, span: float, t_lo: float, t_hi: float):
+    """(t, weight) of the tabulated importance density at the uniform draws ``u`` (f64 [B]); see psld_sample_times_f64."""
+    b, bins = u.numel(), mass.numel()
+    assert cum.numel() == bins + 1 and log_edges.numel() == bins + 1
+    t = torch.empty(b, device=u.device, dtype=torch.float64)
+    weight = torch.empty(b, device=u.device, dtype=torch.float64)
+    check(lib().psld_sample_times_f64(_chk(u, torch.float64).data_ptr(), b, _chk(cum, torch.float64).data_ptr(),
+                                      _chk(log_edges, torch.float64).data_ptr(), _chk(mass, torch.float64).data_ptr(), bins,
+                                      float(span), float(t_lo), float(t_hi), t.data_ptr(), weight.data_ptr(), _stream()),
+          "psld_sample_times_f64")
+    return t, weight
+
+
 def em_step(x: Tensor, eps_pred: Tensor, z: Optional[Tensor], k: EmCoeffs, x_f32: Optional[Tensor]):
     b, c2, h, w = x.shape
     check(lib().psld_em_step_f64(_chk(x, torch.float64).data_ptr(), _chk(eps_pred).data_ptr(), _p(z), C.byref(k), b,

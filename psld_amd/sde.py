@@ -333,3 +333,34 @@ class PSLD:
     def likelihood_weighting(self, t):
         beta_t = self.beta_t(t)
         return beta_t * self.gamma, beta_t * self.m * self.nu
+
+    def nll_weight_host(self, t: float, mm_0: float) -> float:
+        """w(t) = g_x^2 (c11^2 + c12^2) + g_m^2 (c21^2 + c22^2): the factor the likelihood weighting puts on a unit eps
+        error at time ``t`` (rows of L_t^{-T} the score mode uses; python floats)."""
+        c11, c12, c21, c22 = self._inv_coeff_host(self._cov_host(0.0, float(mm_0), float(t)))
+        gx2, gm2 = self.likelihood_weighting(float(t))
+        mode = self._score_mode()
+        if mode == 1:
+            return gm2 * c22 ** 2
+        if mode == 2:
+            return gx2 * c11 ** 2
+        return gx2 * (c11 ** 2 + c12 ** 2) + gm2 * (c21 ** 2 + c22 ** 2)
+
+    def nll_time_table(self, train_eps: float, mm_0: float, bins: int = 256) -> dict:
+        """The tabulated time density of likelihood-weighted training: ``bins`` log-spaced bins on
+        ``[train_eps, T]`` with mass proportional to the trapezoid of ``w(t) t`` in ``ln t``, log-uniform inside a bin, so
+        q(t) = mass_k / (t ln(e_{k+1} / e_k)) exactly.  Returns float64 numpy arrays ``edges``, ``log_edges``
+        (bins + 1), ``mass`` (bins), ``cum`` (bins + 1; cum[0] = 0, cum[bins] = 1) and the floats ``span = T - train_eps``,
+        ``t_lo``, ``t_hi``."""
+        lo, hi = float(train_eps), float(self.T)
+        assert 0 < lo < hi and bins >= 1
+        edges = np.exp(np.linspace(math.log(lo), math.log(hi), bins + 1))
+        edges[0], edges[-1] = lo, hi
+        log_edges = np.log(edges)
+        f = np.array([self.nll_weight_host(e, mm_0) * e for e in edges], dtype=np.float64)
+        mass = 0.5 * (f[:-1] + f[1:]) * (log_edges[1:] - log_edges[:-1])
+        assert np.all(np.isfinite(mass)) and np.all(mass > 0), "the likelihood weight must be finite and positive on the grid"
+        mass = mass / mass.sum()
+        cum = np.concatenate([[0.0], np.cumsum(mass)])
+        cum[-1] = 1.0
+        return {"edges": edges, "log_edges": log_edges, "mass": mass, "cum": cum, "span": hi - lo, "t_lo": lo, "t_hi": hi}

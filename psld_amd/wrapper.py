@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .losses import importance_sampling
 from .optim import FusedAdam
 from .registry import register_module
 
@@ -69,6 +70,7 @@ class SDEWrapper(_Base):
         self.sde = sde
         self.criterion = criterion
         self.train_eps = self.config.training.train_eps
+        self.importance_sampling = importance_sampling(config, sde)     # ValueError unless weighting 'nll' on PSLD
         self.sampler = None
         if sampler_cls is not None:
             self.sampler = sampler_cls(
@@ -117,26 +119,53 @@ class SDEWrapper(_Base):
         if not flag:
             self._graph_steps = {}
 
+    def _time_table(self, dev):
+        """The importance density of the training times on the device (``PSLD.nll_time_table`` for this wrapper's
+        ``train_eps`` and training mode), built once per device."""
+        tab = getattr(self, "_nll_table", None)
+        if tab is None or tab["cum"].device != dev:
+            mm_0 = self.sde.mm_0 if self.config.training.mode == "hsm" else 0.0
+            host = self.sde.nll_time_table(self.train_eps, mm_0)
+            tab = {k: torch.tensor(host[k], dtype=torch.float64, device=dev) for k in ("cum", "log_edges", "mass")}
+            tab.update({k: host[k] for k in ("span", "t_lo", "t_hi")})
+            self._nll_table = tab
+        return tab
+
+    def _map_times(self, t_, tab):
+        """``t_ ~ U[0, 1)`` -> (t, weight): uniform on ``[train_eps, T]`` with no weight, or through the importance density."""
+        if tab is None:
+            return t_ * (self.sde.T - self.train_eps) + self.train_eps, None
+        return ops.sample_times(t_, tab["cum"], tab["log_edges"], tab["mass"], tab["span"], tab["t_lo"], tab["t_hi"])
+
     def _draw_times(self, b: int, dev):
         """``t_ ~ U[0, 1)`` and ``t`` (wrapper.py:72-73) plus the NaN check of the perturbation coefficients
         (psld.py:166-171, a host read) on a stream of their own that does NOT wait for the compute stream: none of it
         depends on the previous step, and on the compute stream the flag read would make the host wait for the whole
         queue of the previous step at every step boundary (4.4 ms of a 37 ms step at batch 16).  The random draw is
         the first of the step on the host, so the device RNG stream is consumed in the reference's order."""
+        return self._draw_weighted_times(b, dev)[:2]
+
+    def _draw_weighted_times(self, b: int, dev):
+        """``_draw_times`` with the importance weights of the times as a third value: None for uniform times; under
+        ``training.loss.importance_sampling`` the SAME single draw ``t_`` is mapped through the tabulated density (one
+        kernel, on the early stream too) and the coefficients of the mapped times are the ones prefetched and checked."""
+        tab = self._time_table(dev) if self.importance_sampling else None
         main = torch.cuda.current_stream(dev)
         early = getattr(self, "_early", None)
         if early is None or early.device != dev:
             early = self._early = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(early):
             t_ = torch.rand(b, device=dev, dtype=torch.float64)
-            t = t_ * (self.sde.T - self.train_eps) + self.train_eps
+            t, weight = self._map_times(t_, tab)
             prefetch = getattr(self.criterion, "prefetch", None)
             if prefetch is not None and getattr(self.sde, "check_nan", False):
                 prefetch(t)
         main.wait_stream(early)
         t_.record_stream(main)
         t.record_stream(main)
-        return t_, t
+        if weight is not None:
+            weight.record_stream(main)
+        return t_, t, weight
 
     def _graph_ok(self, batch) -> bool:
         optim = self.optimizers()
@@ -181,7 +210,7 @@ class SDEWrapper(_Base):
             ent["drop"] = torch.zeros(b, device=dev, dtype=torch.uint8) if p_drop > 0 else None
         # the step's random draws, in the eager step's order (wrapper.py:72, losses.py:96,108, the label-dropout mask, then
         # the dropout seed)
-        t_new, _ = self._draw_times(b, dev)       # includes the NaN check the captured step cannot make
+        t_new = self._draw_weighted_times(b, dev)[0]       # includes the NaN check the captured step cannot make
         ent["t_"].copy_(t_new)
         torch.randn(batch.shape, device=dev, out=ent["m_draw"])
         torch.randn(ent["eps"].shape, device=dev, out=ent["eps"])
@@ -208,13 +237,18 @@ class SDEWrapper(_Base):
             net._dropout_seed_dev = ent["seed"]
             try:
                 with torch.cuda.graph(graph):
-                    t = ent["t_"] * (sde.T - self.train_eps) + self.train_eps
+                    # the time table's buffers are static inputs; the t_ -> (t, weight) mapping is part of the capture
+                    t, weight = self._map_times(ent["t_"], self._time_table(dev) if self.importance_sampling else None)
                     labels = {} if y is None else dict(y=ent["y"], drop=ent["drop"])
+                    if weight is not None:
+                        labels["t_weight"] = weight
                     loss = self.criterion(ent["x0"], t, net, eps=ent["eps"], m_draw=ent["m_draw"], **labels)
                     net.mark_grads_stale()
                     loss.backward()
                     with torch.no_grad():
-                        optim._launch(hyper_dev=ent["hyper"], poison=loss.detach())
+                        poison = self._poison_for(loss)
+                        optim._launch(hyper_dev=ent["hyper"], poison=poison)
+                        loss = self._poisoned(loss, poison)
             finally:
                 sde.check_nan = check_nan
                 net._dropout_seed_dev = None
@@ -229,6 +263,18 @@ class SDEWrapper(_Base):
         self.lr_schedulers().step()
         return ent["loss"]
 
+    @staticmethod
+    def _poison_for(loss):
+        """The float32 device scalar the optimiser kernel turns NaN when it refuses the step: the loss itself, or - for the
+        float64 loss of the 'nll' weightings - a zero that ``_poisoned`` adds to it."""
+        if loss.dtype == torch.float32:
+            return loss.detach()
+        return torch.zeros((), device=loss.device, dtype=torch.float32)
+
+    @staticmethod
+    def _poisoned(loss, poison):
+        return loss if loss.dtype == torch.float32 else loss.detach() + poison
+
     def training_step(self, batch, batch_idx):
         if self._graph_ok(batch):
             loss = self._graphed_step(batch)
@@ -239,21 +285,28 @@ class SDEWrapper(_Base):
         lr_sched = self.lr_schedulers()
         # (x_0, y): the reference's data.return_target convention - class labels for a network with label_classes
         x_0, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
+        extra = {} if y is None else dict(y=y)
         if x_0.is_cuda:
-            _, t = self._draw_times(x_0.shape[0], x_0.device)                   # wrapper.py:72-73
+            _, t, weight = self._draw_weighted_times(x_0.shape[0], x_0.device)  # wrapper.py:72-73
+            if weight is not None:
+                extra["t_weight"] = weight
         else:
             t_ = torch.rand(x_0.shape[0], device=x_0.device, dtype=torch.float64)
             t = t_ * (self.sde.T - self.train_eps) + self.train_eps
-        loss = self.criterion(x_0, t, self.score_fn) if y is None else self.criterion(x_0, t, self.score_fn, y=y)
+        loss = self.criterion(x_0, t, self.score_fn, **extra)
         optim.zero_grad()
         self.manual_backward(loss)
         gc = self.config.training.optimizer.grad_clip
         fused = isinstance(getattr(optim, "optimizer", optim), FusedAdam)
         if gc != 0 and not fused:
             torch.nn.utils.clip_grad_norm_(self.score_fn.parameters(), gc)   # wrapper.py:82-85
-        if fused and loss.is_cuda and loss.dtype == torch.float32:
-            getattr(optim, "optimizer", optim).poison = loss.detach()   # a refused step (device error word) logs NaN
+        poison = None
+        if fused and loss.is_cuda:
+            poison = self._poison_for(loss)
+            getattr(optim, "optimizer", optim).poison = poison          # a refused step (device error word) logs NaN
         optim.step()                  # FusedAdam: norm + clip + Adam (+EMA) in two launches
+        if poison is not None:
+            loss = self._poisoned(loss, poison)
         lr_sched.step()
         self.log("loss", loss, prog_bar=True)
         return loss
