@@ -767,6 +767,24 @@ int psld_sscs_analytic_f64(double* x, const double* z, const psld_sscs_coeffs_t*
                            int batch, int c, int hw, float* x_f32_out, hipStream_t stream);
 int psld_sscs_score_step_f64(double* x, const float* eps_pred, const psld_em_coeffs_t* k,
                              int batch, int c, int hw, hipStream_t stream);
+/* Few-step exponential-integrator sampler (ei_ode; not in the reference): one multistep update
+ *   u <- Phi u + sum_{j < n_hist} C_j eps_j
+ * of the float64 state in place.  eps is a HOST array of n_hist (1..3) device pointers to float32 network outputs, newest
+ * first, each promoted to double; Phi and C_j are host-computed float64 coefficients (never cast to float32).
+ *   augmented = 1: state and eps are [B, 2c, hw] = [x | m]; phi and c[j] are row-major 2x2 matrices acting on the pair
+ *                  (x, m) of one pixel: x' = phi[0] x + phi[1] m + sum_j (c[j][0] ex_j + c[j][1] em_j), m' likewise
+ *                  with entries [2], [3];
+ *   augmented = 0: (VP-SDE) state and eps are [B, c, hw]; only phi[0] and c[j][0] are used.
+ * Optionally writes the float32 rounding of the new state for the next network call.  16-byte accesses when every
+ * pointer is 16-byte aligned (and, augmented, c * hw % 4 == 0), element-wise otherwise. */
+typedef struct psld_ei_coeffs {
+    double phi[4];
+    double c[3][4];
+    int n_hist;
+    int augmented;
+} psld_ei_coeffs_t;
+int psld_ei_step_f64(double* x, const float* const* eps, const psld_ei_coeffs_t* k,
+                     int batch, int c, int hw, float* x_f32_out, hipStream_t stream);
 /* Edges of the path.  Writer: position half of the f64 [B,c_total,H,W] state ->
  * uint8 [B,H,W,c] = trunc(clip((x*0.5+0.5)*255, 0, 255)) (callbacks.py:103-107, util.py:147-158).
  * Loader: uint8 [B,H,W,c] -> f32 [B,c,H,W] = img/127.5-1 (norm) or img/255, optional per-image

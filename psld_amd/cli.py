@@ -582,7 +582,7 @@ def build_parser() -> argparse.ArgumentParser:
     for name in ("train", "sample", "inpaint", "train_clf", "cc_sample", "bpd"):
         p = sub.add_parser(name)
         p.add_argument("--config", default="c10_sota", choices=["c10_sota", "celeba64_sota", "afhqv2_128", "afhqv2_128_inpaint",
-                                                         "c10_ablation", "c10_vpsde", "yaml_default", "tiny"])
+                                                         "c10_ablation", "c10_vpsde", "yaml_default", "tiny", "tiny_vpsde"])
         p.add_argument("--data", default="synthetic", help="uint8 [N,H,W,3] .npy file or 'synthetic'")
         p.add_argument("--synthetic-size", type=int, default=2048)
         p.add_argument("--max-steps", type=int, default=0)

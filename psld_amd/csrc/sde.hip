@@ -318,6 +318,113 @@ __global__ void sscs_score_kernel(double* __restrict__ x, const float* __restric
     }
 }
 
+// ---- exponential-integrator sampler (no counterpart in the reference) -----------
+// u' = Phi u + sum_j C_j eps_j: host-computed float64 2x2 matrices (augmented) or scalars (VP-SDE), up to three float32
+// eps buffers promoted to double.  VEC = 4: one thread per four consecutive elements of a segment - 16-byte accesses on
+// the float64 state (two per half), the float32 eps and the float32 copy; VEC = 1 is the element-wise form.  A segment
+// is one sample's x half (augmented; the m half lies `seg` elements behind it) or the whole flat state.
+struct EiArgs {
+    const float* e[3];
+};
+
+template <int VEC>
+__device__ __forceinline__ void ei_load(const double* p, double (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        const d2 a = reinterpret_cast<const d2*>(p)[0], b = reinterpret_cast<const d2*>(p)[1];
+        v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
+    } else {
+        v[0] = p[0];
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void ei_load(const float* p, float (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        const f4 a = reinterpret_cast<const f4*>(p)[0];
+        v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
+    } else {
+        v[0] = p[0];
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void ei_store(double* p, float* pf, const double (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        d2 a, b;
+        a[0] = v[0]; a[1] = v[1]; b[0] = v[2]; b[1] = v[3];
+        reinterpret_cast<d2*>(p)[0] = a;
+        reinterpret_cast<d2*>(p)[1] = b;
+        if (pf) {
+            f4 f;
+            f[0] = (float)v[0]; f[1] = (float)v[1]; f[2] = (float)v[2]; f[3] = (float)v[3];
+            reinterpret_cast<f4*>(pf)[0] = f;
+        }
+    } else {
+        p[0] = v[0];
+        if (pf) pf[0] = (float)v[0];
+    }
+}
+
+// VEC elements at element offset ox (and om = the momentum half, augmented only)
+template <int VEC, bool AUG>
+__device__ __forceinline__ void ei_update(double* __restrict__ x, const EiArgs& a, const psld_ei_coeffs_t& k,
+                                          long long ox, long long om, float* __restrict__ xf) {
+    double xv[VEC], mv[VEC], nx[VEC], nm[VEC];
+    ei_load<VEC>(x + ox, xv);
+    if constexpr (AUG) ei_load<VEC>(x + om, mv);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        if constexpr (AUG) {
+            nx[e] = k.phi[0] * xv[e] + k.phi[1] * mv[e];
+            nm[e] = k.phi[2] * xv[e] + k.phi[3] * mv[e];
+        } else {
+            nx[e] = k.phi[0] * xv[e];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        if (j < k.n_hist) {
+            float ex[VEC], em[VEC];
+            ei_load<VEC>(a.e[j] + ox, ex);
+            if constexpr (AUG) ei_load<VEC>(a.e[j] + om, em);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                if constexpr (AUG) {
+                    nx[e] = nx[e] + (k.c[j][0] * (double)ex[e] + k.c[j][1] * (double)em[e]);
+                    nm[e] = nm[e] + (k.c[j][2] * (double)ex[e] + k.c[j][3] * (double)em[e]);
+                } else {
+                    nx[e] = nx[e] + k.c[j][0] * (double)ex[e];
+                }
+            }
+        }
+    }
+    ei_store<VEC>(x + ox, xf ? xf + ox : nullptr, nx);
+    if constexpr (AUG) ei_store<VEC>(x + om, xf ? xf + om : nullptr, nm);
+}
+
+// nseg segments of `seg` elements; segment s starts at element s * stride.  The first seg / VEC * VEC elements of every
+// segment go VEC at a time, the rest (only where VEC = 4 and seg % 4 != 0: the flat VP-SDE state) one at a time.
+template <int VEC, bool AUG>
+__global__ void ei_step_kernel(double* __restrict__ x, const EiArgs a, const psld_ei_coeffs_t k, long long nseg,
+                               long long seg, long long stride, float* __restrict__ xf) {
+    const long long pv = seg / VEC, nvec = nseg * pv;
+    GRID_STRIDE(i, nvec) {
+        const long long s = i / pv, r = (i - s * pv) * VEC;
+        const long long ox = s * stride + r;
+        ei_update<VEC, AUG>(x, a, k, ox, ox + seg, xf);
+    }
+    if constexpr (VEC > 1) {
+        const long long tail = seg - pv * VEC, ntail = nseg * tail;
+        GRID_STRIDE(i, ntail) {
+            const long long s = i / tail, r = pv * VEC + (i - s * tail);
+            const long long ox = s * stride + r;
+            ei_update<1, AUG>(x, a, k, ox, ox + seg, xf);
+        }
+    }
+}
+
 // ---- adaptive RK45 building blocks (black-box probability-flow ODE sampler, samplers/ode.py) ---------
 struct RkArgs {
     const double* v[8];
@@ -512,6 +619,39 @@ extern "C" int psld_sscs_score_step_f64(double* x, const float* eps_pred, const 
     const long long n = (long long)batch * c * hw;
     hipLaunchKernelGGL(sscs_score_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_pred, *k, batch, c, hw);
     PSLD_CHECK_LAUNCH("psld_sscs_score_step_f64");
+    return PSLD_OK;
+}
+
+extern "C" int psld_ei_step_f64(double* x, const float* const* eps, const psld_ei_coeffs_t* k, int batch, int c, int hw,
+                                float* x_f32_out, hipStream_t stream) {
+    PSLD_CHECK_ARG(x && eps && k && batch > 0 && c > 0 && hw > 0, "psld_ei_step_f64: bad args");
+    PSLD_CHECK_ARG(k->n_hist >= 1 && k->n_hist <= 3 && (k->augmented == 0 || k->augmented == 1),
+                   "psld_ei_step_f64: n_hist %d not in 1..3 or augmented %d not 0 / 1", k->n_hist, k->augmented);
+    EiArgs a{};
+    bool aligned = ((uintptr_t)x | (uintptr_t)x_f32_out) % 16 == 0;
+    for (int j = 0; j < k->n_hist; ++j) {
+        PSLD_CHECK_ARG(eps[j], "psld_ei_step_f64: eps[%d] is NULL", j);
+        a.e[j] = eps[j];
+        aligned = aligned && (uintptr_t)eps[j] % 16 == 0;
+    }
+    const long long plane = (long long)c * hw;
+    if (k->augmented) {
+        if (aligned && plane % 4 == 0)
+            hipLaunchKernelGGL((ei_step_kernel<4, true>), dim3(grid_for(batch * plane / 4)), dim3(256), 0, stream, x, a,
+                               *k, (long long)batch, plane, 2 * plane, x_f32_out);
+        else
+            hipLaunchKernelGGL((ei_step_kernel<1, true>), dim3(grid_for(batch * plane)), dim3(256), 0, stream, x, a, *k,
+                               (long long)batch, plane, 2 * plane, x_f32_out);
+    } else {
+        const long long n = batch * plane;
+        if (aligned && n >= 4)
+            hipLaunchKernelGGL((ei_step_kernel<4, false>), dim3(grid_for(n / 4)), dim3(256), 0, stream, x, a, *k, 1LL, n,
+                               n, x_f32_out);
+        else
+            hipLaunchKernelGGL((ei_step_kernel<1, false>), dim3(grid_for(n)), dim3(256), 0, stream, x, a, *k, 1LL, n, n,
+                               x_f32_out);
+    }
+    PSLD_CHECK_LAUNCH("psld_ei_step_f64");
     return PSLD_OK;
 }
 

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Epilogue, EmCoeffs, SdeParams, SscsCoeffs, check
+from ._lib import EiCoeffs, Epilogue, EmCoeffs, SdeParams, SscsCoeffs, check
 
 Tensor = torch.Tensor
 INV_SQRT2 = float(1.0 / np.sqrt(2.0))
@@ -1651,6 +1651,25 @@ def sscs_score_step(x: Tensor, eps_pred: Tensor, k: EmCoeffs):
     b, c2, h, w = x.shape
     check(lib().psld_sscs_score_step_f64(_chk(x, torch.float64).data_ptr(), _chk(eps_pred).data_ptr(), C.byref(k), b,
                                          c2 // 2, h * w, _stream()), "psld_sscs_score_step_f64")
+
+
+def ei_step(x: Tensor, eps_hist: Sequence[Tensor], k: EiCoeffs, x_f32: Optional[Tensor] = None):
+    """One exponential-integrator update ``u <- Phi u + sum_j C_j eps_j`` in place on the float64 state (psld_ei_step_f64):
+    ``eps_hist`` holds ``k.n_hist`` float32 network outputs of the state's shape, newest first; ``k.augmented`` says whether
+    the state is ``[x | m]`` (2x2 matrices per pixel pair) or flat (scalars)."""
+    b, ct, h, w = x.shape
+    if len(eps_hist) != k.n_hist:
+        raise ValueError(f"ei_step: {len(eps_hist)} eps tensors for n_hist = {k.n_hist}")
+    if k.augmented and ct % 2:
+        raise ValueError(f"ei_step: an augmented state needs an even channel count, got {ct}")
+    for e in eps_hist:
+        if tuple(_chk(e).shape) != tuple(x.shape):
+            raise ValueError(f"ei_step: eps of shape {tuple(e.shape)} for a state of shape {tuple(x.shape)}")
+    if x_f32 is not None and tuple(_chk(x_f32).shape) != tuple(x.shape):
+        raise ValueError(f"ei_step: float32 copy of shape {tuple(x_f32.shape)} for a state of shape {tuple(x.shape)}")
+    check(lib().psld_ei_step_f64(_chk(x, torch.float64).data_ptr(), _ptr_array(eps_hist), C.byref(k), b,
+                                 ct // 2 if k.augmented else ct, h * w, _p(x_f32), _stream()), "psld_ei_step_f64")
+    return x
 
 
 def samples_to_uint8(samples: Tensor, is_augmented: bool = True, denorm: bool = True) -> Tensor:

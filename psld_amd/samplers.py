@@ -315,6 +315,76 @@ class SSCSSampler(Sampler):
         return x64
 
 
+@register_module(category="samplers", name="ei_ode")
+class ExponentialIntegratorSampler(Sampler):
+    """Few-step deterministic sampler of the probability-flow ODE (no counterpart in the reference): an
+    exponential integrator with a multistep (Adams-Bashforth) polynomial for the network's output, of order
+    ``evaluation.sampler.order`` (1-3, default 2).  The linear drift is integrated exactly and the network's eps is held
+    polynomial in the rotated frame ``R_t = L_t Q(theta_t)`` (PSLD, mode score_xm) or as it is (VP-SDE, where order 1 is
+    DDIM).  All coefficients come from the host plan (``psld_amd.ei.plan``, float64); per step: ONE network call at
+    ``float32(T - t)`` + ONE fused kernel (``ops.ei_step``) that reads up to ``order`` kept eps tensors.  ``denoise`` appends
+    the drift-only probability-flow Euler step of size ``eps`` that ``bb_ode`` ends with.  Deterministic: no noise is drawn."""
+
+    def __init__(self, config, sde, score_fn, corrector_fn=None):
+        super().__init__(config, sde, score_fn, corrector_fn=corrector_fn)
+        from . import ei
+        if corrector_fn is not None:
+            raise NotImplementedError("ei_ode keeps the network outputs of earlier steps: a corrector between the steps would "
+                                      "invalidate them")
+        node = config.evaluation.sampler
+        self.order = ei.check_order(node.get("order", 2) if hasattr(node, "get") else getattr(node, "order", 2))
+        self.nfe = 0
+
+    def predictor_update_fn(self, u, t, dt):
+        raise NotImplementedError("use sample(); a multistep update needs the eps history and the fused kernel updates the "
+                                  "state in place")
+
+    def _eps(self, x32, t_rev: float):
+        self.nfe += 1
+        t32 = torch.full((x32.shape[0],), float(np.float32(t_rev)), device=x32.device, dtype=torch.float32)
+        return self.score_fn(x32, t32).contiguous()
+
+    def sample(self, batch, ts, n_discrete_steps, denoise=True, eps=1e-3):
+        if not batch.is_cuda:
+            raise RuntimeError("psld_amd sampler needs device tensors (no CPU fallback)")
+        from . import ei
+        from .vpsde import VPSDE
+        sde = self.sde
+        self.nfe = 0
+        tl = ts.detach().to(torch.float64).cpu().tolist()
+        coeffs = ei.plan(sde, tl[:n_discrete_steps + 1], self.order)
+        x32 = batch.to(torch.float32).contiguous().clone()
+        x64 = ops.f32_to_f64(x32) if batch.dtype != torch.float64 else batch.contiguous().clone()
+        # the ring of kept eps tensors, newest first.  A score_fn that hands out a fresh tensor per call (the executor does)
+        # is kept by reference; one that writes every result into the same buffer (seen on the second call: the first
+        # result is kept as a copy until then, and its original stays referenced so that no fresh allocation can take its
+        # address) is copied from then on.
+        ring, first, reuses = [], None, None
+        with torch.no_grad():
+            for i in range(n_discrete_steps):
+                e = self._eps(x32, sde.T - tl[i])
+                if self.order > 1:
+                    if first is None:
+                        first, e = e, e.clone()
+                    elif reuses is None:
+                        reuses = e.data_ptr() == first.data_ptr()
+                    if reuses:
+                        e = e.clone()
+                ring.insert(0, e)
+                del ring[self.order:]
+                k = coeffs[i]
+                ops.ei_step(x64, ring[:k.n_hist], k.struct(), x32)
+            if denoise:                                                   # as bb_ode: x += f_bar(x, T - eps) * eps
+                t_rev = sde.T - (sde.T - eps)
+                e = self._eps(x32, t_rev)
+                if isinstance(sde, VPSDE):
+                    ops.vp_reverse(x64, e, None, float(sde.beta_t(t_rev)), sde._std(t_rev), float(eps), True, update=True,
+                                   x_f32=x32)
+                else:
+                    ops.em_step(x64, e, None, sde.em_coeffs(t_rev, float(eps), probability_flow=True), x32)
+        return x64
+
+
 # Dormand-Prince 5(4) tableau (scipy.integrate.RK45)
 _RK_C = (0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0)
 _RK_A = ((), (1 / 5,), (3 / 40, 9 / 40), (44 / 45, -56 / 15, 32 / 9),

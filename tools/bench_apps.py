@@ -1,5 +1,6 @@
 """Per-step timings of the SURVEY 8(f) samplers on the north-star networks (C10-SOTA score net, clf_c10 classifier):
-EM, SSCS, inpainting (ip_em_sde) and classifier guidance (cc_em_sde).  python tools/bench_apps.py [--batch 64]"""
+EM, SSCS, the few-step exponential integrator (ei_ode), inpainting (ip_em_sde) and classifier guidance (cc_em_sde).
+python tools/bench_apps.py [--batch 64]"""
 import argparse, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -41,6 +42,8 @@ em = get_module("samplers", "em_sde")(dcfg, sde, net)
 timed("em_sde", lambda k: em.sample(x, ts[: k + 1], k, denoise=False))
 ss = get_module("samplers", "sscs_sde")(dcfg, sde, net)
 timed("sscs_sde", lambda k: ss.sample(x, ts[: k + 1], k, denoise=False))
+ei = get_module("samplers", "ei_ode")(dcfg, sde, net)      # evaluation.sampler.order unset: order 2
+timed("ei_ode (order 2)", lambda k: ei.sample(x, ts[: k + 1], k, denoise=False))
 ip = get_module("samplers", "ip_em_sde")(dcfg, sde, net)
 x0 = torch.rand(B, 3, 32, 32, device=dev) * 2 - 1
 mask = (torch.rand(B, 3, 32, 32, device=dev) > 0.3).long()
