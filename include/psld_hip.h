@@ -785,6 +785,21 @@ typedef struct psld_ei_coeffs {
 } psld_ei_coeffs_t;
 int psld_ei_step_f64(double* x, const float* const* eps, const psld_ei_coeffs_t* k,
                      int batch, int c, int hw, float* x_f32_out, hipStream_t stream);
+/* The stochastic member of the family (ei_sde; order 1 only): one update
+ *   u <- Phi u + C eps + S z
+ * of the float64 state in place, with ONE float32 eps buffer (promoted to double) and float64 standard-normal noise z in
+ * the state's layout.  phi, c, s as psld_ei_coeffs_t's phi and c[0]; s is lower-triangular (s[1] is not read):
+ * x' = ... + s[0] zx, m' = ... + s[2] zx + s[3] zm; augmented = 0 uses entry [0] of each.  z == NULL drops the noise
+ * term: the result is then psld_ei_step_f64's at n_hist = 1 on the same phi and c, bit for bit.  Same optional float32
+ * copy, same 16-byte / element-wise forms (z counts among the pointers). */
+typedef struct psld_ei_sde_coeffs {
+    double phi[4];
+    double c[4];
+    double s[4];
+    int augmented;
+} psld_ei_sde_coeffs_t;
+int psld_ei_sde_step_f64(double* x, const float* eps, const double* z, const psld_ei_sde_coeffs_t* k,
+                         int batch, int c, int hw, float* x_f32_out, hipStream_t stream);
 /* Edges of the path.  Writer: position half of the f64 [B,c_total,H,W] state ->
  * uint8 [B,H,W,c] = trunc(clip((x*0.5+0.5)*255, 0, 255)) (callbacks.py:103-107, util.py:147-158).
  * Loader: uint8 [B,H,W,c] -> f32 [B,c,H,W] = img/127.5-1 (norm) or img/255, optional per-image

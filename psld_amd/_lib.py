@@ -67,6 +67,11 @@ class EiCoeffs(C.Structure):
     _fields_ = [("phi", C.c_double * 4), ("c", (C.c_double * 4) * 3), ("n_hist", C.c_int), ("augmented", C.c_int)]
 
 
+class EiSdeCoeffs(C.Structure):
+    """struct psld_ei_sde_coeffs."""
+    _fields_ = [("phi", C.c_double * 4), ("c", C.c_double * 4), ("s", C.c_double * 4), ("augmented", C.c_int)]
+
+
 I, F, D, LL, P = C.c_int, C.c_float, C.c_double, C.c_longlong, C.c_void_p
 EP = C.POINTER(Epilogue)
 IP = C.POINTER(C.c_int)
@@ -228,6 +233,7 @@ SIGNATURES = {
     "psld_sscs_analytic_f64": (I, [P, P, C.POINTER(SscsCoeffs), I, I, I, P, P]),
     "psld_sscs_score_step_f64": (I, [P, P, C.POINTER(EmCoeffs), I, I, I, P]),
     "psld_ei_step_f64": (I, [P, P, C.POINTER(EiCoeffs), I, I, I, P, P]),
+    "psld_ei_sde_step_f64": (I, [P, P, P, C.POINTER(EiSdeCoeffs), I, I, I, P, P]),
     "psld_samples_to_uint8": (I, [P, P, I, I, I, I, I, P]),
     "psld_uint8_to_images_f32": (I, [P, P, P, I, I, I, I, I, P]),
     "psld_lincomb_f64": (I, [P, P, P, P, I, LL, P, P]),

@@ -11,6 +11,11 @@
     python -m psld_amd.cli train  --config c10_sota model.score_fn.label_classes=10 --labels y.npy --data x.npy
     python -m psld_amd.cli sample --config c10_sota model.score_fn.label_classes=10 --label 3 --cfg-scale 2.0
                                                                            (no counterpart: classifier-free guidance, psld_amd/guidance.py)
+    python -m psld_amd.cli sample --config c10_sota evaluation.sampler.name=ei_sde evaluation.sampler.lam=0.5
+                                  evaluation.n_discrete_steps=20 evaluation.stride_type=quadratic
+                                                                           (no counterpart: the few-step samplers ei_ode
+                                                                           (evaluation.sampler.order) and ei_sde
+                                                                           (evaluation.sampler.lam), psld_amd/ei.py)
     python -m psld_amd.cli bpd --config c10_sota --data x.npy --ckpt last.ckpt [--n-probes N --n-momentum N --rtol R --atol A]
                                                                            (no counterpart: psld_amd/likelihood.py)
 

@@ -425,6 +425,63 @@ __global__ void ei_step_kernel(double* __restrict__ x, const EiArgs a, const psl
     }
 }
 
+// The stochastic member (ei_sde): u' = Phi u + C eps + S z with one eps buffer and float64 noise in the
+// state's layout, S lower-triangular.  Same segments, same accesses and, for the terms it shares with ei_update at
+// n_hist = 1, the same order of operations; the noise goes on last.
+template <int VEC, bool AUG>
+__device__ __forceinline__ void ei_sde_update(double* __restrict__ x, const float* __restrict__ eps,
+                                              const double* __restrict__ z, const psld_ei_sde_coeffs_t& k, long long ox,
+                                              long long om, float* __restrict__ xf) {
+    double xv[VEC], mv[VEC], zx[VEC], zm[VEC], nx[VEC], nm[VEC];
+    float ex[VEC], em[VEC];
+    ei_load<VEC>(x + ox, xv);
+    ei_load<VEC>(eps + ox, ex);
+    ei_load<VEC>(z + ox, zx);
+    if constexpr (AUG) {
+        ei_load<VEC>(x + om, mv);
+        ei_load<VEC>(eps + om, em);
+        ei_load<VEC>(z + om, zm);
+    }
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        if constexpr (AUG) {
+            nx[e] = k.phi[0] * xv[e] + k.phi[1] * mv[e];
+            nm[e] = k.phi[2] * xv[e] + k.phi[3] * mv[e];
+            nx[e] = nx[e] + (k.c[0] * (double)ex[e] + k.c[1] * (double)em[e]);
+            nm[e] = nm[e] + (k.c[2] * (double)ex[e] + k.c[3] * (double)em[e]);
+            nx[e] = nx[e] + k.s[0] * zx[e];
+            nm[e] = nm[e] + (k.s[2] * zx[e] + k.s[3] * zm[e]);
+        } else {
+            nx[e] = k.phi[0] * xv[e];
+            nx[e] = nx[e] + k.c[0] * (double)ex[e];
+            nx[e] = nx[e] + k.s[0] * zx[e];
+        }
+    }
+    ei_store<VEC>(x + ox, xf ? xf + ox : nullptr, nx);
+    if constexpr (AUG) ei_store<VEC>(x + om, xf ? xf + om : nullptr, nm);
+}
+
+// the segments of ei_step_kernel
+template <int VEC, bool AUG>
+__global__ void ei_sde_step_kernel(double* __restrict__ x, const float* __restrict__ eps, const double* __restrict__ z,
+                                   const psld_ei_sde_coeffs_t k, long long nseg, long long seg, long long stride,
+                                   float* __restrict__ xf) {
+    const long long pv = seg / VEC, nvec = nseg * pv;
+    GRID_STRIDE(i, nvec) {
+        const long long s = i / pv, r = (i - s * pv) * VEC;
+        const long long ox = s * stride + r;
+        ei_sde_update<VEC, AUG>(x, eps, z, k, ox, ox + seg, xf);
+    }
+    if constexpr (VEC > 1) {
+        const long long tail = seg - pv * VEC, ntail = nseg * tail;
+        GRID_STRIDE(i, ntail) {
+            const long long s = i / tail, r = pv * VEC + (i - s * tail);
+            const long long ox = s * stride + r;
+            ei_sde_update<1, AUG>(x, eps, z, k, ox, ox + seg, xf);
+        }
+    }
+}
+
 // ---- adaptive RK45 building blocks (black-box probability-flow ODE sampler, samplers/ode.py) ---------
 struct RkArgs {
     const double* v[8];
@@ -652,6 +709,40 @@ extern "C" int psld_ei_step_f64(double* x, const float* const* eps, const psld_e
                                x_f32_out);
     }
     PSLD_CHECK_LAUNCH("psld_ei_step_f64");
+    return PSLD_OK;
+}
+
+extern "C" int psld_ei_sde_step_f64(double* x, const float* eps, const double* z, const psld_ei_sde_coeffs_t* k, int batch,
+                                    int c, int hw, float* x_f32_out, hipStream_t stream) {
+    PSLD_CHECK_ARG(x && eps && k && batch > 0 && c > 0 && hw > 0, "psld_ei_sde_step_f64: bad args");
+    PSLD_CHECK_ARG(k->augmented == 0 || k->augmented == 1, "psld_ei_sde_step_f64: augmented %d not 0 / 1", k->augmented);
+    if (!z) {   // no noise term: the deterministic kernel itself, on the same Phi and C
+        psld_ei_coeffs_t d{};
+        for (int i = 0; i < 4; ++i) { d.phi[i] = k->phi[i]; d.c[0][i] = k->c[i]; }
+        d.n_hist = 1;
+        d.augmented = k->augmented;
+        const float* e[1] = {eps};
+        return psld_ei_step_f64(x, e, &d, batch, c, hw, x_f32_out, stream);
+    }
+    const bool aligned = ((uintptr_t)x | (uintptr_t)eps | (uintptr_t)z | (uintptr_t)x_f32_out) % 16 == 0;
+    const long long plane = (long long)c * hw;
+    if (k->augmented) {
+        if (aligned && plane % 4 == 0)
+            hipLaunchKernelGGL((ei_sde_step_kernel<4, true>), dim3(grid_for(batch * plane / 4)), dim3(256), 0, stream, x, eps,
+                               z, *k, (long long)batch, plane, 2 * plane, x_f32_out);
+        else
+            hipLaunchKernelGGL((ei_sde_step_kernel<1, true>), dim3(grid_for(batch * plane)), dim3(256), 0, stream, x, eps, z,
+                               *k, (long long)batch, plane, 2 * plane, x_f32_out);
+    } else {
+        const long long n = batch * plane;
+        if (aligned && n >= 4)
+            hipLaunchKernelGGL((ei_sde_step_kernel<4, false>), dim3(grid_for(n / 4)), dim3(256), 0, stream, x, eps, z, *k, 1LL,
+                               n, n, x_f32_out);
+        else
+            hipLaunchKernelGGL((ei_sde_step_kernel<1, false>), dim3(grid_for(n)), dim3(256), 0, stream, x, eps, z, *k, 1LL, n,
+                               n, x_f32_out);
+    }
+    PSLD_CHECK_LAUNCH("psld_ei_sde_step_f64");
     return PSLD_OK;
 }
 

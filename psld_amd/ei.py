@@ -1,4 +1,5 @@
-"""Host plan of the few-step exponential-integrator sampler ``ei_ode`` (not in the reference).
+"""Host plans of the few-step exponential-integrator samplers ``ei_ode`` and ``ei_sde`` (section 12; at
+the end of this file).  Neither is in the reference.
 
 ``plan(sde, ts, order)`` turns the sampler's time grid into one coefficient set per step, in NumPy float64:
 
@@ -24,7 +25,7 @@ import collections
 
 import numpy as np
 
-from ._lib import EiCoeffs as _EiStruct
+from ._lib import EiCoeffs as _EiStruct, EiSdeCoeffs as _EiSdeStruct
 
 NQ = 16                                       # Gauss-Legendre nodes per panel
 _CACHE: "collections.OrderedDict" = collections.OrderedDict()
@@ -256,6 +257,156 @@ def plan(sde, ts, order: int = 2):
     hit = _CACHE.get(key)
     if hit is None:
         hit = _CACHE[key] = build(sde, t, order)
+        while len(_CACHE) > _CACHE_MAX:
+            _CACHE.popitem(last=False)
+    else:
+        _CACHE.move_to_end(key)
+    return hit
+
+
+# ---- ei_sde: the stochastic lambda family at order 1 --------------------------------------------------
+SUB_LOG = 0.0025      # largest ln(t_a / t_b) of one RK4 sub-step: F^_lam grows like (1 + lam^2) / (2 t) towards t = eval_eps
+SUB_DB = 0.02         # ... and the largest increment of b_t, which bounds what the conjugation by Phi contributes
+
+
+class EiSdeCoeffs:
+    """Coefficients of one stochastic step ``u <- phi u + c eps + s z`` from ``t`` to ``t_next`` (forward times).  Augmented
+    (PSLD): ``phi``, ``c``, ``s`` [2, 2] acting on the pair (x, m) of one pixel, ``s`` lower-triangular; VP-SDE: floats.
+    ``psi`` is the transition matrix Psi^_lam(t_next, t) they were formed from."""
+    __slots__ = ("phi", "c", "s", "psi", "augmented", "t", "t_next", "lam", "_struct")
+
+    def __init__(self, phi, c, s, psi, augmented: bool, t: float, t_next: float, lam: float):
+        self.phi, self.c, self.s, self.psi, self.augmented = phi, c, s, psi, bool(augmented)
+        self.t, self.t_next, self.lam, self._struct = float(t), float(t_next), float(lam), None
+
+    def struct(self) -> _EiSdeStruct:
+        """The ``psld_ei_sde_coeffs_t`` of this step (float64 throughout; the VP-SDE scalars in entry 0)."""
+        if self._struct is None:
+            k = _EiSdeStruct()
+            k.augmented = 1 if self.augmented else 0
+            for name in ("phi", "c", "s"):
+                v = np.asarray(getattr(self, name), dtype=np.float64).reshape(-1)
+                for i in range(4):
+                    getattr(k, name)[i] = float(v[i]) if i < v.size else 0.0
+            self._struct = k
+        return self._struct
+
+
+def check_lam(lam) -> float:
+    if isinstance(lam, (bool, np.bool_)) or not isinstance(lam, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(lam) or lam < 0:
+        raise ValueError(f"ei_sde: evaluation.sampler.lam must be a finite number >= 0, got {lam!r}")
+    return float(lam)
+
+
+def _psi_hat(p: _Psld, t: np.ndarray, lam: float) -> np.ndarray:
+    """Psi^_lam(t_{n+1}, t_n) [N, 2, 2] of F^_lam = beta (F~ + (1 + lam^2) / 2 D~ Sigma^-1), all steps in lock-step.  With
+    Psi^(s, t_n) = Phi(s, t_n) V(s): V' = Phi(t_n, s) G(s) Phi(s, t_n) V, G = (1 + lam^2) / 2 beta D~ Sigma^-1, V(t_n) = I,
+    so the linear drift stays exact and only the 1 / t part is integrated: classical RK4 on sub-steps geometric in t.  The
+    one-step propagators of all sub-steps are formed at once; what remains sequential is their ordered product."""
+    t0, t1 = t[:-1], t[1:]
+    m = int(max(8, np.ceil(np.log(t0 / t1).max() * (1 + lam * lam) / 2 / SUB_LOG),
+                np.ceil(np.abs(p.b(t0) - p.b(t1)).max() / SUB_DB)))
+    frac = np.arange(m + 1)[:, None] / m
+    ends = t0[None, :] * (t1 / t0)[None, :] ** frac                           # [m + 1, N]
+    ends[0], ends[-1] = t0, t1
+    a, b = ends[:-1], ends[1:]
+    h = (b - a)[..., None, None]                                              # < 0
+    s = np.stack([a, (a + b) / 2, b])                                         # [3, m, N]: the RK4 abscissae
+    _, inv = p.factors(s)
+    g = ((1 + lam * lam) / 2 * p.beta(s))[..., None, None] * p.dt[:, None] * (inv @ np.swapaxes(inv, -1, -2))
+    db = p.b(s) - p.b(t0)[None, None, :]
+    hm = p.flow(-db) @ g @ p.flow(db)
+    eye = np.eye(2)
+    k1 = hm[0]
+    k2 = hm[1] @ (eye + h / 2 * k1)
+    k3 = hm[1] @ (eye + h / 2 * k2)
+    k4 = hm[2] @ (eye + h * k3)
+    prop = eye + h / 6 * (k1 + 2 * k2 + 2 * k3 + k4)                          # [m, N, 2, 2]
+    v = prop[0]
+    for i in range(1, m):
+        v = prop[i] @ v
+    return p.flow(p.b(t1) - p.b(t0)) @ v
+
+
+def _chol2(pm: np.ndarray) -> np.ndarray:
+    """Lower Cholesky factors of [N, 2, 2] symmetric matrices."""
+    s00 = np.sqrt(pm[:, 0, 0])
+    s10 = pm[:, 1, 0] / s00
+    s11 = np.sqrt(pm[:, 1, 1] - s10 ** 2)
+    out = np.zeros_like(pm)
+    out[:, 0, 0], out[:, 1, 0], out[:, 1, 1] = s00, s10, s11
+    if not np.all(np.isfinite(out)):
+        raise ValueError("ei_sde: the noise covariance of a step is not positive definite")
+    return out
+
+
+def _psld_plan_sde(sde, t: np.ndarray, lam: float):
+    if sde.mode != "score_xm":
+        raise ValueError(f"ei_sde needs the PSLD mode score_xm (nu != 0 and gamma != 0), got {sde.mode}: the network "
+                         "predicts only half of eps there and C = (Psi^ - Phi) L_t needs both halves")
+    p = _Psld(sde)
+    psi = _psi_hat(p, t, lam)
+    phi = p.flow(p.b(t[1:]) - p.b(t[:-1]))
+    fac, _ = p.factors(t)
+    xx, xm, mm = p.cov(t)
+    sig = np.stack([np.stack([xx, xm], -1), np.stack([xm, mm], -1)], -2)
+    pm = sig[1:] - psi @ sig[:-1] @ np.swapaxes(psi, -1, -2)
+    s = _chol2((pm + np.swapaxes(pm, -1, -2)) / 2)
+    c = (psi - phi) @ fac[:-1]
+    return [EiSdeCoeffs(phi[i], c[i], s[i], psi[i], True, t[i], t[i + 1], lam) for i in range(t.size - 1)]
+
+
+def _vp_plan_sde(sde, t: np.ndarray, lam: float):
+    b0, b1 = float(sde.beta_0), float(sde.beta_1)
+    lmc = lambda u: -0.25 * u ** 2 * (b1 - b0) - 0.5 * u * b0                  # ln alpha
+    la = lmc(t)
+    lsig = 0.5 * np.log(-np.expm1(2.0 * la))                                  # ln sigma
+    lr = (lsig[1:] - la[1:]) - (lsig[:-1] - la[:-1])                          # ln of the ratio of sigma / alpha: < 0
+    phi = np.exp(la[1:] - la[:-1])
+    psi = np.exp(lsig[1:] - lsig[:-1] + lam * lam * lr)
+    sig = np.exp(lsig)
+    c = (psi - phi) * sig[:-1]
+    s = sig[1:] * np.sqrt(-np.expm1(2.0 * lam * lam * lr))                    # s^2 = sigma_s^2 - psi^2 sigma_t^2
+    return [EiSdeCoeffs(float(phi[i]), float(c[i]), float(s[i]), float(psi[i]), False, t[i], t[i + 1], lam)
+            for i in range(t.size - 1)]
+
+
+def _from_order_one(sde, k: EiCoeffs) -> EiSdeCoeffs:
+    """lam = 0: Phi and C_0 of ``plan(sde, ts, 1)`` as they are, S = 0, Psi^ = Phi + C_0 L_t^-1."""
+    if k.augmented:
+        fac, _ = _Psld(sde).factors(np.float64(k.t))
+        return EiSdeCoeffs(k.phi, k.c[0], np.zeros((2, 2)), k.phi + k.c[0] @ np.linalg.inv(fac), True, k.t, k.t_next, 0.0)
+    la = -0.25 * k.t ** 2 * (float(sde.beta_1) - float(sde.beta_0)) - 0.5 * k.t * float(sde.beta_0)
+    return EiSdeCoeffs(k.phi, float(k.c[0]), 0.0, k.phi + float(k.c[0]) / np.sqrt(-np.expm1(2.0 * la)), False, k.t, k.t_next, 0.0)
+
+
+def plan_sde(sde, ts, lam: float = 1.0):
+    """One ``EiSdeCoeffs`` per step of the sampler grid ``ts`` (as for ``plan``) for the member ``lam`` of the stochastic
+    family: 0 is ``plan(sde, ts, 1)`` with no noise, 1 the reverse SDE."""
+    from .sde import PSLD
+    from .vpsde import VPSDE
+    lam = check_lam(lam)
+    tau = np.asarray(ts.detach().cpu().numpy() if hasattr(ts, "detach") else ts, dtype=np.float64).reshape(-1)
+    t = float(sde.T) - tau
+    if t.size < 2 or not np.all(np.diff(t) < 0) or not t[-1] > 0:
+        raise ValueError("ei_sde: the time grid must ascend strictly from 0 and end before T")
+    if isinstance(sde, PSLD):
+        key = ("psld_sde", sde.beta_0, sde.beta_1, sde.nu, sde.gamma, sde.kappa, sde.eps, sde.decomp_mode)
+        build = _psld_plan_sde
+    elif isinstance(sde, VPSDE):
+        key = ("vpsde_sde", sde.beta_0, sde.beta_1)
+        build = _vp_plan_sde
+    else:
+        raise TypeError(f"ei_sde: no plan for an SDE of type {type(sde).__name__}")
+    key = key + (tuple(tau.tolist()), lam)
+    hit = _CACHE.get(key)
+    if hit is None:
+        if lam == 0.0:                                                        # the probability flow: ei_ode's own order 1
+            hit = [_from_order_one(sde, k) for k in plan(sde, ts, 1)]
+        else:
+            hit = build(sde, t, lam)
+        _CACHE[key] = hit
         while len(_CACHE) > _CACHE_MAX:
             _CACHE.popitem(last=False)
     else:

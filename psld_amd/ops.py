@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EiCoeffs, Epilogue, EmCoeffs, SdeParams, SscsCoeffs, check
+from ._lib import EiCoeffs, EiSdeCoeffs, Epilogue, EmCoeffs, SdeParams, SscsCoeffs, check
 
 Tensor = torch.Tensor
 INV_SQRT2 = float(1.0 / np.sqrt(2.0))
@@ -1669,6 +1669,26 @@ def ei_step(x: Tensor, eps_hist: Sequence[Tensor], k: EiCoeffs, x_f32: Optional[
         raise ValueError(f"ei_step: float32 copy of shape {tuple(x_f32.shape)} for a state of shape {tuple(x.shape)}")
     check(lib().psld_ei_step_f64(_chk(x, torch.float64).data_ptr(), _ptr_array(eps_hist), C.byref(k), b,
                                  ct // 2 if k.augmented else ct, h * w, _p(x_f32), _stream()), "psld_ei_step_f64")
+    return x
+
+
+def ei_sde_step(x: Tensor, eps: Tensor, z: Optional[Tensor], k: EiSdeCoeffs, x_f32: Optional[Tensor] = None):
+    """One stochastic exponential-integrator update ``u <- Phi u + C eps + S z`` in place on the float64 state
+    (psld_ei_sde_step_f64): ``eps`` the float32 network output and ``z`` float64 standard-normal noise, both of the state's
+    shape; ``z = None`` drops the noise term (then ``ei_step`` with one eps tensor, bit for bit)."""
+    b, ct, h, w = x.shape
+    if k.augmented not in (0, 1):
+        raise ValueError(f"ei_sde_step: augmented must be 0 or 1, got {k.augmented}")
+    if k.augmented and ct % 2:
+        raise ValueError(f"ei_sde_step: an augmented state needs an even channel count, got {ct}")
+    if tuple(_chk(eps).shape) != tuple(x.shape):
+        raise ValueError(f"ei_sde_step: eps of shape {tuple(eps.shape)} for a state of shape {tuple(x.shape)}")
+    if z is not None and tuple(_chk(z, torch.float64).shape) != tuple(x.shape):
+        raise ValueError(f"ei_sde_step: noise of shape {tuple(z.shape)} for a state of shape {tuple(x.shape)}")
+    if x_f32 is not None and tuple(_chk(x_f32).shape) != tuple(x.shape):
+        raise ValueError(f"ei_sde_step: float32 copy of shape {tuple(x_f32.shape)} for a state of shape {tuple(x.shape)}")
+    check(lib().psld_ei_sde_step_f64(_chk(x, torch.float64).data_ptr(), eps.data_ptr(), _p(z), C.byref(k), b,
+                                     ct // 2 if k.augmented else ct, h * w, _p(x_f32), _stream()), "psld_ei_sde_step_f64")
     return x
 
 

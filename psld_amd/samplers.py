@@ -348,7 +348,6 @@ class ExponentialIntegratorSampler(Sampler):
         if not batch.is_cuda:
             raise RuntimeError("psld_amd sampler needs device tensors (no CPU fallback)")
         from . import ei
-        from .vpsde import VPSDE
         sde = self.sde
         self.nfe = 0
         tl = ts.detach().to(torch.float64).cpu().tolist()
@@ -374,14 +373,63 @@ class ExponentialIntegratorSampler(Sampler):
                 del ring[self.order:]
                 k = coeffs[i]
                 ops.ei_step(x64, ring[:k.n_hist], k.struct(), x32)
-            if denoise:                                                   # as bb_ode: x += f_bar(x, T - eps) * eps
-                t_rev = sde.T - (sde.T - eps)
-                e = self._eps(x32, t_rev)
-                if isinstance(sde, VPSDE):
-                    ops.vp_reverse(x64, e, None, float(sde.beta_t(t_rev)), sde._std(t_rev), float(eps), True, update=True,
-                                   x_f32=x32)
-                else:
-                    ops.em_step(x64, e, None, sde.em_coeffs(t_rev, float(eps), probability_flow=True), x32)
+            if denoise:
+                self._denoise(x64, x32, eps)
+        return x64
+
+    def _denoise(self, x64, x32, eps):
+        """As bb_ode: x += f_bar(x, T - eps) * eps, the drift-only probability-flow Euler step."""
+        from .vpsde import VPSDE
+        sde = self.sde
+        t_rev = sde.T - (sde.T - eps)
+        e = self._eps(x32, t_rev)
+        if isinstance(sde, VPSDE):
+            ops.vp_reverse(x64, e, None, float(sde.beta_t(t_rev)), sde._std(t_rev), float(eps), True, update=True, x_f32=x32)
+        else:
+            ops.em_step(x64, e, None, sde.em_coeffs(t_rev, float(eps), probability_flow=True), x32)
+
+
+@register_module(category="samplers", name="ei_sde")
+class StochasticExponentialIntegratorSampler(ExponentialIntegratorSampler):
+    """Few-step stochastic sampler (no counterpart in the reference): the member
+    ``evaluation.sampler.lam`` (>= 0, default 1.0) of the family of reverse processes that share the forward marginals -
+    0 is the probability flow (``ei_ode`` at order 1, bit for bit, no noise drawn), 1 the reverse SDE.  Order 1 only: the
+    linear drift and the noise are integrated exactly, so that a step of any size is exact in distribution on point-mass
+    data.  Coefficients from the host plan (``psld_amd.ei.plan_sde``, float64); per step: ONE network call at
+    ``float32(T - t)``, ONE ``torch.randn_like`` on the float64 state and ONE fused kernel (``ops.ei_sde_step``).
+    ``denoise`` appends ``ei_ode``'s drift-only probability-flow Euler step, which draws nothing."""
+
+    def __init__(self, config, sde, score_fn, corrector_fn=None):
+        Sampler.__init__(self, config, sde, score_fn, corrector_fn=corrector_fn)
+        from . import ei
+        if corrector_fn is not None:
+            raise ValueError("ei_sde: the plan's noise covariance completes each step to the marginal of its end time; a "
+                             "corrector between the steps is not supported")
+        node = config.evaluation.sampler
+        self.lam = ei.check_lam(node.get("lam", 1.0) if hasattr(node, "get") else getattr(node, "lam", 1.0))
+        self.order = 1
+        self.noise_fn = None  # test hook: callable(step, x) -> float64 noise replacing torch.randn_like
+        self.nfe = 0
+
+    def sample(self, batch, ts, n_discrete_steps, denoise=True, eps=1e-3):
+        if not batch.is_cuda:
+            raise RuntimeError("psld_amd sampler needs device tensors (no CPU fallback)")
+        from . import ei
+        sde = self.sde
+        self.nfe = 0
+        tl = ts.detach().to(torch.float64).cpu().tolist()
+        coeffs = ei.plan_sde(sde, tl[:n_discrete_steps + 1], self.lam)
+        x32 = batch.to(torch.float32).contiguous().clone()
+        x64 = ops.f32_to_f64(x32) if batch.dtype != torch.float64 else batch.contiguous().clone()
+        with torch.no_grad():
+            for i in range(n_discrete_steps):
+                e = self._eps(x32, sde.T - tl[i])
+                z = None
+                if self.lam > 0:
+                    z = (self.noise_fn(i, x64) if self.noise_fn is not None else torch.randn_like(x64)).contiguous()
+                ops.ei_sde_step(x64, e, z, coeffs[i].struct(), x32)
+            if denoise:
+                self._denoise(x64, x32, eps)
         return x64
 
 

@@ -1,5 +1,5 @@
 """Per-step timings of the SURVEY 8(f) samplers on the north-star networks (C10-SOTA score net, clf_c10 classifier):
-EM, SSCS, the few-step exponential integrator (ei_ode), inpainting (ip_em_sde) and classifier guidance (cc_em_sde).
+EM, SSCS, the few-step exponential integrators (ei_ode, ei_sde), inpainting (ip_em_sde) and classifier guidance (cc_em_sde).
 python tools/bench_apps.py [--batch 64]"""
 import argparse, os, sys, time
 import torch
@@ -44,6 +44,8 @@ ss = get_module("samplers", "sscs_sde")(dcfg, sde, net)
 timed("sscs_sde", lambda k: ss.sample(x, ts[: k + 1], k, denoise=False))
 ei = get_module("samplers", "ei_ode")(dcfg, sde, net)      # evaluation.sampler.order unset: order 2
 timed("ei_ode (order 2)", lambda k: ei.sample(x, ts[: k + 1], k, denoise=False))
+es = get_module("samplers", "ei_sde")(dcfg, sde, net)     # evaluation.sampler.lam unset: lam 1.0
+timed("ei_sde (lam 1)", lambda k: es.sample(x, ts[: k + 1], k, denoise=False))
 ip = get_module("samplers", "ip_em_sde")(dcfg, sde, net)
 x0 = torch.rand(B, 3, 32, 32, device=dev) * 2 - 1
 mask = (torch.rand(B, 3, 32, 32, device=dev) > 0.3).long()
