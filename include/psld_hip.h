@@ -800,6 +800,37 @@ typedef struct psld_ei_sde_coeffs {
 } psld_ei_sde_coeffs_t;
 int psld_ei_sde_step_f64(double* x, const float* eps, const double* z, const psld_ei_sde_coeffs_t* k,
                          int batch, int c, int hw, float* x_f32_out, hipStream_t stream);
+/* Measurement-guided (posterior) sampling for y = A x0 + noise (not in the reference; csrc/restore.hip):
+ * the two kernels around the one network evaluation with its input gradient that a guided call costs.  float32 tensors,
+ * float64 arithmetic in registers, one host-computed float64 coefficient set per call (one time for the whole batch):
+ *   q_u, q_e: the Tweedie estimate x0^ = q_u[0] u_x + q_u[1] u_m - q_e[0] e_x - q_e[1] e_m of the clean image,
+ *   l = (l11, l21, l22): the lower Cholesky factor of the perturbation covariance, kappa = scale / (sigma_y^2 + r_t^2);
+ *   augmented = 1: state, eps, cotangent, dx and out are [B, 2c, h, w] = [x | m];
+ *   augmented = 0: (VP-SDE) they are [B, c, h, w] and entry [0] of q_u, q_e, l (= sigma_t) is used.
+ * psld_restore_measure_f32 writes g = A^T (y - A x0^) ([B, c, h, w]) and the cotangent (q_e[0] g | q_e[1] g) in one pass:
+ *   op = PSLD_RESTORE_MASK: A x = mask . x, y and mask [B, c, h, w] (mask of {0, 1}; NULL for the other operators);
+ *   op = PSLD_RESTORE_GRAY: A x = (x_R + x_G + x_B) / sqrt(3), c == 3, y [B, 1, h, w];
+ *   op = PSLD_RESTORE_POOL: A x = (1 / k) sum over each k x k block, k = 2 or 4 dividing h and w, y [B, c, h/k, w/k]
+ *   (k is read by the pool operator only); every A has orthonormal rows.
+ * psld_restore_combine_f32 writes out_x = e_x - kappa (q_e[0] g - l11 dx_x - l21 dx_m), out_m = e_m - kappa (q_e[1] g -
+ * l22 dx_m) (augmented = 0: out = e - kappa (q_e[0] g - l[0] dx)), dx the vector-Jacobian product of the cotangent.
+ * 16-byte accesses when every pointer is 16-byte aligned and the shape allows (mask, combine: c * h * w % 4 == 0 augmented,
+ * any length flat; gray: h * w % 4 == 0; pool: w % 4 == 0), element-wise otherwise: any h, w and any alignment works. */
+#define PSLD_RESTORE_MASK 0
+#define PSLD_RESTORE_GRAY 1
+#define PSLD_RESTORE_POOL 2
+typedef struct psld_restore_coeffs {
+    double q_u[2];
+    double q_e[2];
+    double l[3];
+    double kappa;
+    int augmented;
+} psld_restore_coeffs_t;
+int psld_restore_measure_f32(const float* u, const float* eps, const float* y, const float* mask, int op, int k,
+                             const psld_restore_coeffs_t* q, int batch, int c, int h, int w, float* g, float* cot,
+                             hipStream_t stream);
+int psld_restore_combine_f32(const float* eps, const float* g, const float* dx, const psld_restore_coeffs_t* q,
+                             int batch, int c, int hw, float* out, hipStream_t stream);
 /* Edges of the path.  Writer: position half of the f64 [B,c_total,H,W] state ->
  * uint8 [B,H,W,c] = trunc(clip((x*0.5+0.5)*255, 0, 255)) (callbacks.py:103-107, util.py:147-158).
  * Loader: uint8 [B,H,W,c] -> f32 [B,c,H,W] = img/127.5-1 (norm) or img/255, optional per-image

@@ -72,6 +72,12 @@ class EiSdeCoeffs(C.Structure):
     _fields_ = [("phi", C.c_double * 4), ("c", C.c_double * 4), ("s", C.c_double * 4), ("augmented", C.c_int)]
 
 
+class RestoreCoeffs(C.Structure):
+    """struct psld_restore_coeffs."""
+    _fields_ = [("q_u", C.c_double * 2), ("q_e", C.c_double * 2), ("l", C.c_double * 3), ("kappa", C.c_double),
+                ("augmented", C.c_int)]
+
+
 I, F, D, LL, P = C.c_int, C.c_float, C.c_double, C.c_longlong, C.c_void_p
 EP = C.POINTER(Epilogue)
 IP = C.POINTER(C.c_int)
@@ -79,6 +85,8 @@ IP = C.POINTER(C.c_int)
 # enum psld_tile_form: kernel kind | operand flags, what the psld_*_plan queries return
 TILE_GENERIC, TILE_FAST128, TILE_FAST256, TILE_FAST64, TILE_FAST64_SPLITK = 0, 1, 2, 3, 4
 TILE_KIND_MASK, TILE_A_VEC, TILE_B_VEC = 15, 16, 32
+# operator codes of psld_restore_measure_f32
+RESTORE_MASK, RESTORE_GRAY, RESTORE_POOL = 0, 1, 2
 
 ABI_VERSION = 14   # PSLD_ABI_VERSION of include/psld_hip.h these signatures were written against
 
@@ -234,6 +242,8 @@ SIGNATURES = {
     "psld_sscs_score_step_f64": (I, [P, P, C.POINTER(EmCoeffs), I, I, I, P]),
     "psld_ei_step_f64": (I, [P, P, C.POINTER(EiCoeffs), I, I, I, P, P]),
     "psld_ei_sde_step_f64": (I, [P, P, P, C.POINTER(EiSdeCoeffs), I, I, I, P, P]),
+    "psld_restore_measure_f32": (I, [P, P, P, P, I, I, C.POINTER(RestoreCoeffs), I, I, I, I, P, P, P]),
+    "psld_restore_combine_f32": (I, [P, P, P, C.POINTER(RestoreCoeffs), I, I, I, P, P]),
     "psld_samples_to_uint8": (I, [P, P, I, I, I, I, I, P]),
     "psld_uint8_to_images_f32": (I, [P, P, P, I, I, I, I, I, P]),
     "psld_lincomb_f64": (I, [P, P, P, P, I, LL, P, P]),

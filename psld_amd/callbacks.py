@@ -14,7 +14,7 @@ from .optim import EMAWeightUpdate  # noqa: F401  (re-export under the reference
 
 class SimpleImageWriter:
     def __init__(self, output_dir, write_interval="batch", sample_prefix="", path_prefix="", save_mode="image",
-                 is_norm=True, is_augmented=True):
+                 is_norm=True, is_augmented=True, save_momentum=False):
         self.output_dir = output_dir
         self.interval = write_interval
         self.sample_prefix = sample_prefix
@@ -22,6 +22,9 @@ class SimpleImageWriter:
         self.save_mode = save_mode
         self.is_norm = is_norm
         self.is_augmented = is_augmented
+        # the reference's TODO (callbacks.py:66): also write the momentum half, float32 [B, C, H, W] under momentum/ (raw
+        # values: it is no image); ``evaluation.save_momentum`` of the commands
+        self.save_momentum = bool(save_momentum) and bool(is_augmented)
 
     def write_on_batch_end(self, trainer, pl_module, prediction, batch_indices, batch, batch_idx, dataloader_idx=0):
         rank = getattr(pl_module, "global_rank", 0)
@@ -30,6 +33,10 @@ class SimpleImageWriter:
         os.makedirs(img_dir, exist_ok=True)
         stem = os.path.join(img_dir, f"output_{self.sample_prefix }_{rank}_{batch_idx}")     # callbacks.py:120-122
         pred = prediction if prediction.dtype == torch.float64 else prediction.double()
+        if self.save_momentum:
+            os.makedirs(os.path.join(base, "momentum"), exist_ok=True)
+            np.save(os.path.join(base, "momentum", os.path.basename(stem) + ".npy"),
+                    pred[:, pred.shape[1] // 2:].to(torch.float32).cpu().numpy())
         if self.save_mode == "image":
             u8 = ops.samples_to_uint8(pred.contiguous(), self.is_augmented, self.is_norm).cpu().numpy()
             from PIL import Image

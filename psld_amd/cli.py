@@ -18,6 +18,10 @@
                                                                            (evaluation.sampler.lam), psld_amd/ei.py)
     python -m psld_amd.cli bpd --config c10_sota --data x.npy --ckpt last.ckpt [--n-probes N --n-momentum N --rtol R --atol A]
                                                                            (no counterpart: psld_amd/likelihood.py)
+    python -m psld_amd.cli restore --config c10_sota --data x.npy --task mask|gray|pool2|pool4 --sigma-y 0.05
+                                   [--mask m.npy --guidance-scale G evaluation.sampler.name=ei_sde ...]
+                                                                           (no counterpart: measurement-guided restoration
+                                                                           with the unconditional network, psld_amd/guidance.py)
 
 For the two classifier-guidance commands ``dataset.clf.<key>=value`` / ``clf.<key>=value`` go to the ``clf`` node.
 
@@ -310,6 +314,7 @@ def sample(args, overrides):
     dev = torch.device("cuda", local)
     cfg = apply_label_args(parse_overrides(getattr(C, args.config)(), overrides), args)
     ev = cfg.evaluation
+    momentum = _wants_momentum(cfg)
     score_fn, ema, sde = build(cfg, dev)
     if ev.chkpt_path:
         load_checkpoint(ev.chkpt_path, score_fn, ema)
@@ -343,6 +348,8 @@ def sample(args, overrides):
                 np.save(stem + ".npy", u8)
         else:
             np.save(stem + ".npy", u8)
+        if momentum:
+            _save_momentum(base, f"output_{ev.sample_prefix}_{rank}_{bi}", x)
         if rank == 0:
             done = start + b - lo
             print(f"rank 0: {done}/{hi - lo} samples, {done / (time.perf_counter() - t0):.2f} img/s", flush=True)
@@ -488,6 +495,109 @@ def _save_u8(stem, u8, save_mode):
     np.save(stem + ".npy", u8)
 
 
+def _wants_momentum(cfg) -> bool:
+    """``evaluation.save_momentum=true`` (off by default; the reference leaves it as a TODO, callbacks.py:66): ``sample`` and
+    ``restore`` also write the momentum half of the final state.  Checked before anything is sampled."""
+    if not cfg.evaluation.get("save_momentum", False):
+        return False
+    if not cfg.model.sde.is_augmented:
+        raise SystemExit("evaluation.save_momentum needs an augmented SDE (the VP-SDE state has no momentum half)")
+    return True
+
+
+def _save_momentum(base, name, x):
+    """The momentum half as float32 ``[B, C, H, W]`` in ``<base>/momentum/<name>.npy`` - raw values, it is no image."""
+    os.makedirs(os.path.join(base, "momentum"), exist_ok=True)
+    np.save(os.path.join(base, "momentum", name + ".npy"), x[:, x.shape[1] // 2:].to(torch.float32).cpu().numpy())
+
+
+def _masks(cfg, args, n, dev):
+    """bool [n, H, W, 3] on the device: ``--mask file.npy`` (uint8 / bool [N, H, W, 3], 1 = keep) or a centred square hole."""
+    size = cfg.data.image_size
+    if args.mask and args.mask != "synthetic":
+        marr = np.load(args.mask, mmap_mode="r")
+        assert marr.shape[1:] == (size, size, 3), marr.shape
+        return torch.from_numpy(np.ascontiguousarray(marr[:n])).to(dev).ne(0)
+    masks = torch.ones((n, size, size, 3), dtype=torch.bool, device=dev)
+    masks[:, size // 4: 3 * size // 4, size // 4: 3 * size // 4] = False
+    return masks
+
+
+def restore(args, overrides):
+    """Measurement-guided restoration (no counterpart in the reference): the images of ``--data`` are
+    degraded here - ``y = A x0 + N(0, sigma_y^2)`` with ``A`` the operator of ``--task`` (``mask``: the pixels where
+    ``--mask`` is 1; ``gray``; ``pool2`` / ``pool4``: block averages) and the noise from a generator seeded with
+    ``evaluation.seed`` + rank - and restored from ``prior_sampling`` by the sampler ``evaluation.sampler.name`` running the
+    unconditional network under ``PosteriorScoreFn``.  Writes images/ (the restorations), corrupt/ (the measurement shown at
+    image scale, ``A^T y``) and batch/ (the originals) like ``inpaint``; ``evaluation.restore.prior_var=V`` sets the pixel
+    prior's variance."""
+    from psld_amd import config as C, ops
+    from psld_amd.ddp import init_distributed, shard_range
+    from psld_amd.guidance import apply_adjoint, apply_operator
+    from psld_amd.registry import get_module
+    import torch.distributed as dist
+    rank, local, world = init_distributed()
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    cfg = getattr(C, args.config)()
+    cfg.evaluation.restore = {"task": args.task, "sigma_y": args.sigma_y, "scale": args.guidance_scale, "prior_var": 1.0}
+    cfg = parse_overrides(cfg, overrides)
+    ev = cfg.evaluation
+    momentum = _wants_momentum(cfg)
+    if ev.sampler.name in ("ip_em_sde", "cc_em_sde"):
+        raise SystemExit(f"restore: evaluation.sampler.name={ev.sampler.name} takes its own conditioning; use an "
+                         "unconditional sampler (em_sde, sscs_sde, bb_ode, ei_ode, ei_sde)")
+    if ev.restore.sigma_y < 0:
+        raise SystemExit("restore: --sigma-y must be >= 0")
+    score_fn, ema, sde = build(cfg, dev)
+    if ev.chkpt_path:
+        load_checkpoint(ev.chkpt_path, score_fn, ema)
+        score_fn.to(dev), ema.to(dev)
+    score_fn.eval(), ema.eval()
+    wrapper = get_module("pl_modules", cfg.model.pl_module)(cfg, sde, score_fn, ema_score_fn=ema,
+                                                            sampler_cls=get_module("samplers", ev.sampler.name))
+    wrapper.global_rank = rank
+    wrapper.on_predict_start()
+    guided = wrapper.sampler.score_fn
+    data = _dataset(cfg, args, dev, 0)
+    size, ch = cfg.data.image_size, cfg.data.num_channels
+    n = min(ev.n_samples, data.shape[0])
+    masks = _masks(cfg, args, n, dev) if args.task == "mask" else None
+    gen = torch.Generator(device=dev).manual_seed(int(ev.seed) + rank)
+    lo, hi = shard_range(n, rank, world)
+    base = os.path.join(ev.save_path or "psld_restore", str(ev.path_prefix)) if ev.path_prefix else (ev.save_path or "psld_restore")
+    dirs = {k: os.path.join(base, k) for k in ("images", "corrupt", "batch")}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    for bi, start in enumerate(range(lo, hi, ev.batch_size)):
+        stop = min(start + ev.batch_size, hi)
+        x0 = ops.uint8_to_images(data[start:stop].contiguous(), norm=cfg.data.norm)
+        mask = masks[start:stop].permute(0, 3, 1, 2).contiguous().to(torch.float32) if masks is not None else None
+        y = apply_operator(x0, args.task, mask)
+        y = y + float(ev.restore.sigma_y) * torch.randn(y.shape, device=dev, generator=gen)
+        if mask is not None:
+            y = y * mask                                                   # nothing is measured where the mask is 0
+        guided.set_measurement(y, mask)
+        x = wrapper.predict_step(sde.prior_sampling((stop - start, ch, size, size), device=dev), bi)
+        if x.dtype != torch.float64:
+            x = x.double()
+        name = f"output_{ev.sample_prefix}_{rank}_{bi}"
+        u8 = ops.samples_to_uint8(x.contiguous(), is_augmented=cfg.model.sde.is_augmented, denorm=cfg.data.norm)
+        _save_u8(os.path.join(dirs["images"], name), u8.cpu().numpy(), ev.save_mode)
+        to01 = lambda t: (t * 0.5 + 0.5) if cfg.data.norm else t
+        to_u8 = lambda t: (t.clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+        shown = to01(apply_adjoint(y, args.task, mask))
+        _save_u8(os.path.join(dirs["corrupt"], name), to_u8(shown * mask if mask is not None else shown), ev.save_mode)
+        _save_u8(os.path.join(dirs["batch"], name), to_u8(to01(x0)), ev.save_mode)
+        if momentum:
+            _save_momentum(base, name, x)
+        if rank == 0:
+            print(f"rank 0: restored {stop - lo}/{hi - lo} ({args.task})", flush=True)
+    if world > 1:
+        dist.barrier(device_ids=[local])
+        dist.destroy_process_group()
+
+
 def inpaint(args, overrides):
     """main/eval/inpaint.py: images of ``--data`` with the pixels where ``--mask`` is 0 re-synthesised by the
     ``ip_em_sde`` sampler.  Masks: uint8/bool [N,H,W,3] (1 = keep; the reference derives them from MNIST digits,
@@ -512,15 +622,8 @@ def inpaint(args, overrides):
     wrapper.global_rank = rank
     wrapper.on_predict_start()
     data = _dataset(cfg, args, dev, 0)
-    size = cfg.data.image_size
     n = min(ev.n_samples, data.shape[0])                                  # datasets/inpaint.py:43-44
-    if args.mask and args.mask != "synthetic":
-        marr = np.load(args.mask, mmap_mode="r")
-        assert marr.shape[1:] == (size, size, 3), marr.shape
-        masks = torch.from_numpy(np.ascontiguousarray(marr[:n])).to(dev).ne(0)
-    else:
-        masks = torch.ones((n, size, size, 3), dtype=torch.bool, device=dev)
-        masks[:, size // 4: 3 * size // 4, size // 4: 3 * size // 4] = False
+    masks = _masks(cfg, args, n, dev)
     lo, hi = shard_range(n, rank, world)
     base = os.path.join(ev.save_path or "psld_inpaint", str(ev.path_prefix)) if ev.path_prefix else (ev.save_path or "psld_inpaint")
     dirs = {k: os.path.join(base, k) for k in ("images", "corrupt", "batch")}
@@ -584,7 +687,7 @@ def bpd(args, overrides):
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="psld_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("train", "sample", "inpaint", "train_clf", "cc_sample", "bpd"):
+    for name in ("train", "sample", "inpaint", "train_clf", "cc_sample", "bpd", "restore"):
         p = sub.add_parser(name)
         p.add_argument("--config", default="c10_sota", choices=["c10_sota", "celeba64_sota", "afhqv2_128", "afhqv2_128_inpaint",
                                                          "c10_ablation", "c10_vpsde", "yaml_default", "tiny", "tiny_vpsde"])
@@ -608,6 +711,20 @@ def build_parser() -> argparse.ArgumentParser:
             p.add_argument("--cfg-scale", type=float, default=None, metavar="S",
                            help="classifier-free guidance scale (evaluation.cfg_scale, default 1.0 = plain conditional "
                                 "sampling; 0 = unconditional; other values run the doubled batch)")
+        if name == "restore":
+            p.add_argument("--task", required=True, choices=["mask", "gray", "pool2", "pool4"],
+                           help="the degradation A: mask (the pixels where --mask is 1), gray ((R + G + B) / sqrt 3), "
+                                "pool2 / pool4 (2x2 / 4x4 block averages); each has orthonormal rows")
+            p.add_argument("--sigma-y", type=float, default=0.0, metavar="S",
+                           help="standard deviation of the measurement noise, in network-input units (added here, seeded)")
+            p.add_argument("--guidance-scale", type=float, default=1.0, metavar="G",
+                           help="weight of the measurement term (1 = the posterior score under the Gaussian model of DESIGN "
+                                "section 13; 0 = unguided sampling: the plain forward, no backward)")
+            p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32", "f16"],
+                           help="as for sample.  A guided network call is a RECORDING pass (forward + input gradient), and the "
+                                "reduced modes bf16x3 / f16 touch only non-recording forwards: among the limb modes this "
+                                "setting changes only the unguided calls (--guidance-scale 0); record math (ops.set_record_math) "
+                                "governs the guided ones; f32 takes every pass off the limb kernels")
         if name in ("sample", "cc_sample", "inpaint"):
             p.add_argument("--math", default=None, choices=["bf16x6", "bf16x3", "f32", "f16"],
                            help="arithmetic of the network evaluations (ops.set_math_mode; default: the process's mode, "
@@ -661,7 +778,7 @@ def main(argv=None):
         from psld_amd import ops
         ops.set_grad_shift(args.grad_shift)
     {"train": train, "sample": sample, "inpaint": inpaint, "train_clf": train_clf,
-     "cc_sample": cc_sample, "bpd": bpd}[args.cmd](args, overrides)
+     "cc_sample": cc_sample, "bpd": bpd, "restore": restore}[args.cmd](args, overrides)
 
 
 if __name__ == "__main__":

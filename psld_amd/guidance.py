@@ -1,4 +1,6 @@
-"""Classifier-free guidance for a label-conditioned NCSN++ (``model.score_fn.label_classes`` > 0).
+"""Guidance fronts of a score network: each is a ``score_fn`` ``(x32, t32) -> eps`` for every sampler, so no sampler changes.
+
+``CFGScoreFn``: classifier-free guidance for a label-conditioned NCSN++ (``model.score_fn.label_classes`` > 0).
 
 ``CFGScoreFn(net, labels, scale)`` is a ``score_fn`` for every sampler: ``(x32, t32) -> eps`` with
 
@@ -8,12 +10,18 @@ from ONE network call on the doubled batch ``[x; x]``, ``[t; t]``, ``[labels; no
 (``ops.cfg_combine``).  ``scale == 1`` is plain conditional sampling and ``scale == 0`` plain unconditional sampling: each
 runs its B-batch alone and launches no combine.  The samplers see an opaque callable, so none of them changes; there is
 no ``vjp_input`` here, so ``PFLikelihood`` takes its plain-callable path.
+
+``PosteriorScoreFn``: measurement guidance for linear inverse problems ``y = A x0 + noise`` with the unconditional network
+(at the end of this file).
 """
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 class CFGScoreFn:
@@ -64,3 +72,220 @@ class CFGScoreFn:
         null = torch.full_like(y, self.net.label_classes)
         eps2 = self.net(torch.cat([x32, x32]), torch.cat([t32, t32]), y=torch.cat([y, null]))
         return ops.cfg_combine(eps2.contiguous(), self.scale)
+
+
+# ---- measurement guidance -----------------------------------------------------------------------------
+# task -> (operator code, block size); every operator has orthonormal rows (A A^T = I on its range)
+OPERATORS = {"mask": (_lib.RESTORE_MASK, 1), "gray": (_lib.RESTORE_GRAY, 1), "pool2": (_lib.RESTORE_POOL, 2),
+             "pool4": (_lib.RESTORE_POOL, 4)}
+
+
+def check_task(task) -> str:
+    if task not in OPERATORS:
+        raise ValueError(f"restore: task must be one of {sorted(OPERATORS)}, got {task!r}")
+    return task
+
+
+def apply_operator(x: torch.Tensor, task: str, mask=None) -> torch.Tensor:
+    """``A x`` of images ``x`` ``[B, C, H, W]`` in torch operations (setting a problem up; the per-step arithmetic is
+    ``ops.restore_measure``): mask ``M . x``, gray ``(x_R + x_G + x_B) / sqrt(3)``, pool the block sums over ``k``."""
+    op, k = OPERATORS[check_task(task)]
+    want = ops.restore_measurement_shape(x.shape, op, k, 0)
+    if op == _lib.RESTORE_MASK:
+        if mask is None or tuple(mask.shape) != want:
+            raise ValueError(f"restore: the mask operator needs a mask of shape {want}")
+        return x * mask.to(x.dtype)
+    if op == _lib.RESTORE_GRAY:
+        return x.sum(dim=1, keepdim=True) / math.sqrt(3.0)
+    b, c, h, w = x.shape
+    return x.reshape(b, c, h // k, k, w // k, k).sum(dim=(3, 5)) / k
+
+
+def apply_adjoint(y: torch.Tensor, task: str, mask=None) -> torch.Tensor:
+    """``A^T y`` at image shape: the measurement itself (mask), the mean grey value in all three channels (gray), the block
+    mean in every pixel of its block (pool) - the measurement shown at image scale."""
+    op, k = OPERATORS[check_task(task)]
+    if op == _lib.RESTORE_MASK:
+        return y * mask.to(y.dtype)
+    if op == _lib.RESTORE_GRAY:
+        return (y / math.sqrt(3.0)).expand(-1, 3, -1, -1).contiguous()
+    return (y / k).repeat_interleave(k, dim=2).repeat_interleave(k, dim=3)
+
+
+def _uniform_time(t32) -> float:
+    """The one time of a sampler's network call (as ``predict_x_from_eps``: one coefficient set serves the whole batch)."""
+    if torch.is_tensor(t32):
+        vals = t32.detach().reshape(-1).tolist()
+        if not vals or any(v != vals[0] for v in vals):
+            raise ValueError("PosteriorScoreFn takes ONE time for the whole batch (its coefficients are host scalars)")
+        return float(vals[0])
+    return float(t32)
+
+
+def posterior_coeffs(sde, t: float, sigma_y: float, scale: float = 1.0, prior_var: float = 1.0) -> _lib.RestoreCoeffs:
+    """The ``psld_restore_coeffs_t`` of forward time ``t`` in host float64.
+
+    PSLD (mode score_xm, lower factor): ``Sigma_t = L L^T`` the perturbation covariance for ``xx_0 = 0``, ``mm_0 = kappa M``,
+    ``a_t`` the mean of ``u_t`` for ``x0 = 1, m0 = 0`` (first column of ``predict_x_from_eps``'s matrix), ``p = a / (a . a)``:
+    ``q_u = p``, ``q_e = (p_x l11 + p_m l21, p_m l22)``, ``r_t^2 = 1 / (1 / v0 + a^T Sigma^-1 a)``.  VP-SDE: ``q_u = 1 / alpha``,
+    ``q_e = sigma / alpha``, ``r_t^2 = v0 sigma^2 / (sigma^2 + v0 alpha^2)``.  ``kappa = scale / (sigma_y^2 + r_t^2)``."""
+    from .sde import PSLD
+    from .vpsde import VPSDE
+    v0, t = float(prior_var), float(t)
+    q = _lib.RestoreCoeffs()
+    if isinstance(sde, PSLD):
+        if sde.mode != "score_xm" or sde.decomp_mode != "lower":
+            raise ValueError(f"PosteriorScoreFn needs the PSLD mode score_xm with the lower factor, got {sde.mode} / "
+                             f"{sde.decomp_mode}: the Tweedie estimate u - L eps needs both halves of eps")
+        xx, xm, mm = sde._cov_host(0.0, float(sde.mm_0), t)
+        l11 = math.sqrt(xx)
+        l21 = xm / l11
+        l22 = math.sqrt(mm - l21 * l21)
+        b = float(sde.b_t(t))
+        sf = math.exp((sde.nu + sde.gamma) / 4 * b)
+        ax, am = ((sde.nu - sde.gamma) / 4 * b + 1) / sf, (-0.5 * b) / sf
+        aa = ax * ax + am * am
+        px, pm = ax / aa, am / aa
+        z1 = ax / l11
+        z2 = (am - l21 * z1) / l22
+        r2 = v0 / (1.0 + v0 * (z1 * z1 + z2 * z2))                 # 1 / (1 / v0 + a^T Sigma^-1 a), defined at v0 = 0 too
+        q.augmented = 1
+        q.q_u[0], q.q_u[1] = px, pm
+        q.q_e[0], q.q_e[1] = px * l11 + pm * l21, pm * l22
+        q.l[0], q.l[1], q.l[2] = l11, l21, l22
+    elif isinstance(sde, VPSDE):
+        la = float(sde._lmc(t))
+        alpha, s2 = math.exp(la), -math.expm1(2.0 * la)
+        sigma = math.sqrt(s2)
+        r2 = v0 * s2 / (s2 + v0 * alpha * alpha)
+        q.augmented = 0
+        q.q_u[0], q.q_e[0], q.l[0] = 1.0 / alpha, sigma / alpha, sigma
+    else:
+        raise TypeError(f"PosteriorScoreFn: no coefficients for an SDE of type {type(sde).__name__}")
+    var = float(sigma_y) ** 2 + r2
+    if not (var > 0.0 and math.isfinite(var)) or not all(math.isfinite(v) for v in (*q.q_u, *q.q_e, *q.l)):
+        raise ValueError(f"PosteriorScoreFn: sigma_y^2 + r_t^2 = {var!r} at t = {t} is not a positive number "
+                         f"(sigma_y = {sigma_y}, prior_var = {prior_var})")
+    q.kappa = float(scale) / var
+    return q
+
+
+class PosteriorScoreFn:
+    """``PosteriorScoreFn(net, sde, operator, sigma_y, scale=1.0, prior_var=1.0)``: the unconditional network ``net`` guided
+    towards a measurement ``y = A x0 + N(0, sigma_y^2)`` set with ``set_measurement(y, mask=None)``; ``operator`` is one of
+    ``mask | gray | pool2 | pool4``.  A call returns
+
+        eps' = eps - kappa L^T (q_u g - J^T (q_e g)),   g = A^T (y - A x0^(u, eps)),   kappa = scale / (sigma_y^2 + r_t^2)
+
+    i.e. ``-L^T`` times the score plus ``scale * grad_u log N(y; A x0^(u), (sigma_y^2 + r_t^2) I)`` with the Jacobian ``J`` of
+    the network kept (exact for Gaussian data; PiGDM's weighting otherwise).  Per call: ONE
+    ``net.vjp_input`` (recorded forward + input-gradient-only backward) with ``ops.restore_measure`` between its two phases,
+    then ``ops.restore_combine``.  ``scale == 0`` is the plain forward, bit for bit, and launches neither kernel.  A ``net``
+    without ``vjp_input`` (a torch callable) is differentiated with ``torch.autograd`` under ``torch.enable_grad()``.
+
+    The guided pass is a RECORDING pass: its arithmetic is the record arithmetic (``ops.set_record_math``), not the
+    evaluation arithmetic of the plain sampling forward (``ops.set_math_mode`` / ``ops.set_eval_math``), as for ``bpd``.
+    Labels are out of scope here: a ``CFGScoreFn`` is refused as ``net``."""
+
+    def __init__(self, net, sde, operator: str, sigma_y: float, scale: float = 1.0, prior_var: float = 1.0):
+        if isinstance(net, CFGScoreFn):
+            raise ValueError("PosteriorScoreFn: labels are out of scope here - pass the network itself, not a CFGScoreFn")
+        self.net, self.sde = net, sde
+        self.operator = check_task(operator)
+        self.op, self.k = OPERATORS[operator]
+        self.sigma_y, self.scale, self.prior_var = float(sigma_y), float(scale), float(prior_var)
+        if not math.isfinite(self.scale) or not math.isfinite(self.sigma_y) or self.sigma_y < 0:
+            raise ValueError(f"PosteriorScoreFn: sigma_y must be >= 0 and scale finite, got {sigma_y!r}, {scale!r}")
+        posterior_coeffs(sde, float(sde.T), self.sigma_y, self.scale, self.prior_var)      # refuses what no time can serve
+        self.y = self.mask = self._pin = None
+        self._coeffs = {}
+
+    # what wrappers and samplers ask of a score network besides calling it
+    @property
+    def training(self) -> bool:
+        return bool(getattr(self.net, "training", False))
+
+    def eval(self):
+        if hasattr(self.net, "eval"):
+            self.net.eval()
+        return self
+
+    def parameters(self):
+        return self.net.parameters()
+
+    def set_measurement(self, y: torch.Tensor, mask=None):
+        """``y``: the measurement (mask ``[B, C, H, W]``, gray ``[B, 1, H, W]``, pool ``[B, C, H/k, W/k]``), ``mask``: {0, 1}
+        ``[B, C, H, W]``, for the mask operator and no other.  Kept as contiguous float32 device tensors."""
+        if (mask is not None) != (self.op == _lib.RESTORE_MASK):
+            raise ValueError("PosteriorScoreFn: a mask goes with the mask operator and with no other")
+        if y.dim() != 4:
+            raise ValueError(f"PosteriorScoreFn: measurement of shape {tuple(y.shape)} is not [B, C, H, W]")
+        if mask is not None and tuple(mask.shape) != tuple(y.shape):
+            raise ValueError(f"PosteriorScoreFn: mask of shape {tuple(mask.shape)} for a measurement of shape {tuple(y.shape)}")
+        self.y = y.detach().to(torch.float32).contiguous()
+        self.mask = None if mask is None else mask.detach().to(device=y.device, dtype=torch.float32).contiguous()
+        return self
+
+    def coeffs(self, t: float) -> _lib.RestoreCoeffs:
+        q = self._coeffs.get(t)
+        if q is None:
+            if len(self._coeffs) > 4096:
+                self._coeffs.clear()
+            q = self._coeffs[t] = posterior_coeffs(self.sde, t, self.sigma_y, self.scale, self.prior_var)
+        return q
+
+    def _measurement_for(self, x32):
+        if self.y is None:
+            raise RuntimeError("PosteriorScoreFn: set_measurement(y, mask) first")
+        want = ops.restore_measurement_shape(x32.shape, self.op, self.k, 0 if self.sde.type == "vpsde" else 1)
+        if tuple(self.y.shape) != want or self.y.device != x32.device:
+            raise ValueError(f"PosteriorScoreFn: measurement of shape {tuple(self.y.shape)} on {self.y.device}, the operator "
+                             f"{self.operator} and a state of shape {tuple(x32.shape)} on {x32.device} need {want}")
+        return self.y, self.mask
+
+    def _time_reader(self, t32):
+        """Start fetching the call's time; the returned function hands it over as a host float (and refuses a ``t32`` whose
+        entries differ).  A device ``t32`` is copied to pinned memory asynchronously NOW, ahead of the forward on the stream,
+        and waited for only between the two phases - when the forward is already queued - so that reading it never leaves
+        the device idle behind a drained queue."""
+        if not (torch.is_tensor(t32) and t32.is_cuda):
+            t = _uniform_time(t32)
+            return lambda: t
+        n = t32.numel()
+        if self._pin is None or self._pin.numel() < n or self._pin.dtype != t32.dtype:
+            self._pin = torch.empty(max(n, 1), dtype=t32.dtype).pin_memory()
+        buf = self._pin[:n]
+        buf.copy_(t32.detach().reshape(-1), non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+
+        def read():
+            done.synchronize()
+            return _uniform_time(buf)
+        return read
+
+    def __call__(self, x32: torch.Tensor, t32: torch.Tensor) -> torch.Tensor:
+        if self.scale == 0.0:
+            return self.net(x32, t32)
+        y, mask = self._measurement_for(x32)
+        read_time = self._time_reader(t32)
+        x32 = x32.contiguous()
+        kept = []
+
+        def w_fn(out):
+            q = self.coeffs(read_time())
+            g, w = ops.restore_measure(x32, out, y, mask, self.op, self.k, q)
+            kept.extend((g, q))
+            return w
+
+        if hasattr(self.net, "vjp_input"):
+            eps, dx = self.net.vjp_input(x32, t32, w_fn)
+        else:
+            with torch.enable_grad():
+                x = x32.detach().clone().requires_grad_()
+                out = self.net(x, t32)
+                eps = out.detach().to(torch.float32).contiguous()
+                (dx,) = torch.autograd.grad(out, x, grad_outputs=w_fn(eps).to(out.dtype))
+            dx = dx.detach().to(torch.float32)
+        g, q = kept
+        return ops.restore_combine(eps.contiguous(), g, dx.contiguous(), q)

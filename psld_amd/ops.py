@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EiCoeffs, EiSdeCoeffs, Epilogue, EmCoeffs, SdeParams, SscsCoeffs, check
+from ._lib import EiCoeffs, EiSdeCoeffs, Epilogue, EmCoeffs, RestoreCoeffs, SdeParams, SscsCoeffs, check
 
 Tensor = torch.Tensor
 INV_SQRT2 = float(1.0 / np.sqrt(2.0))
@@ -1690,6 +1690,74 @@ def ei_sde_step(x: Tensor, eps: Tensor, z: Optional[Tensor], k: EiSdeCoeffs, x_f
     check(lib().psld_ei_sde_step_f64(_chk(x, torch.float64).data_ptr(), eps.data_ptr(), _p(z), C.byref(k), b,
                                      ct // 2 if k.augmented else ct, h * w, _p(x_f32), _stream()), "psld_ei_sde_step_f64")
     return x
+
+
+def restore_measurement_shape(state_shape, op: int, k: int, augmented) -> tuple:
+    """Shape of the measurement ``y = A x0`` that fits a state of ``state_shape`` under operator ``op`` (_lib.RESTORE_*):
+    mask ``[B, C, H, W]``, gray ``[B, 1, H, W]`` (C must be 3), pool ``[B, C, H/k, W/k]`` (k = 2 or 4 dividing H and W)."""
+    b, ct, h, w = state_shape
+    if augmented not in (0, 1):
+        raise ValueError(f"restore: augmented must be 0 or 1, got {augmented}")
+    if augmented and ct % 2:
+        raise ValueError(f"restore: an augmented state needs an even channel count, got {ct}")
+    c = ct // 2 if augmented else ct
+    if op == _lib.RESTORE_MASK:
+        return b, c, h, w
+    if op == _lib.RESTORE_GRAY:
+        if c != 3:
+            raise ValueError(f"restore: the gray operator needs 3 image channels, got {c}")
+        return b, 1, h, w
+    if op == _lib.RESTORE_POOL:
+        if k not in (2, 4):
+            raise ValueError(f"restore: pool block size must be 2 or 4, got {k}")
+        if h % k or w % k:
+            raise ValueError(f"restore: a {h} x {w} map is no multiple of the pool block {k}")
+        return b, c, h // k, w // k
+    raise ValueError(f"restore: operator code {op} not 0 (mask) / 1 (gray) / 2 (pool)")
+
+
+def restore_measure(u: Tensor, eps: Tensor, y: Tensor, mask: Optional[Tensor], op: int, k: int, q: RestoreCoeffs):
+    """``(g, w)`` of one guided call (psld_restore_measure_f32): ``g = A^T (y - A x0^)`` ``[B, C, H, W]`` and the network
+    cotangent ``w = (q_e[0] g | q_e[1] g)`` of the state's shape, from the float32 state ``u``, the network output ``eps`` of
+    the same shape, the measurement ``y`` and - for the mask operator alone - the float32 mask of {0, 1}."""
+    if tuple(_chk(eps).shape) != tuple(_chk(u).shape):
+        raise ValueError(f"restore_measure: eps of shape {tuple(eps.shape)} for a state of shape {tuple(u.shape)}")
+    want = restore_measurement_shape(u.shape, op, k, q.augmented)
+    if tuple(_chk(y).shape) != want:
+        raise ValueError(f"restore_measure: measurement of shape {tuple(y.shape)}, this operator and state need {want}")
+    if (mask is not None) != (op == _lib.RESTORE_MASK):
+        raise ValueError("restore_measure: a mask goes with the mask operator and with no other")
+    if mask is not None and tuple(_chk(mask).shape) != want:
+        raise ValueError(f"restore_measure: mask of shape {tuple(mask.shape)} for a measurement of shape {want}")
+    b, ct, h, w = u.shape
+    c = ct // 2 if q.augmented else ct
+    g = torch.empty((b, c, h, w), device=u.device, dtype=torch.float32)
+    cot = torch.empty_like(u)
+    check(lib().psld_restore_measure_f32(u.data_ptr(), eps.data_ptr(), y.data_ptr(), _p(mask), int(op), int(k), C.byref(q),
+                                         b, c, h, w, g.data_ptr(), cot.data_ptr(), _stream()), "psld_restore_measure_f32")
+    return g, cot
+
+
+def restore_combine(eps: Tensor, g: Tensor, dx: Tensor, q: RestoreCoeffs, out: Optional[Tensor] = None) -> Tensor:
+    """The guided network output ``eps - kappa (q_e g - L^T dx)`` (psld_restore_combine_f32): ``eps`` and ``dx`` float32 of the
+    state's shape, ``g`` ``[B, C, H, W]`` as ``restore_measure`` wrote it."""
+    b, ct, h, w = _chk(eps).shape
+    if q.augmented not in (0, 1):
+        raise ValueError(f"restore_combine: augmented must be 0 or 1, got {q.augmented}")
+    if q.augmented and ct % 2:
+        raise ValueError(f"restore_combine: an augmented state needs an even channel count, got {ct}")
+    c = ct // 2 if q.augmented else ct
+    if tuple(_chk(dx).shape) != tuple(eps.shape):
+        raise ValueError(f"restore_combine: dx of shape {tuple(dx.shape)} for an eps of shape {tuple(eps.shape)}")
+    if tuple(_chk(g).shape) != (b, c, h, w):
+        raise ValueError(f"restore_combine: g of shape {tuple(g.shape)}, this eps needs {(b, c, h, w)}")
+    if out is None:
+        out = torch.empty_like(eps)
+    elif tuple(_chk(out).shape) != tuple(eps.shape):
+        raise ValueError(f"restore_combine: out of shape {tuple(out.shape)} for an eps of shape {tuple(eps.shape)}")
+    check(lib().psld_restore_combine_f32(eps.data_ptr(), g.data_ptr(), dx.data_ptr(), C.byref(q), b, c, h * w,
+                                         out.data_ptr(), _stream()), "psld_restore_combine_f32")
+    return out
 
 
 def samples_to_uint8(samples: Tensor, is_augmented: bool = True, denorm: bool = True) -> Tensor:

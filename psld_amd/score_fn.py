@@ -614,17 +614,24 @@ class NCSNpp(nn.Module):
         with torch.no_grad():
             return _Exec(self, record=False).run(x, t, lab, drop)
 
-    def vjp_input(self, x: Tensor, time_cond: Tensor, w: Tensor, y: Optional[Tensor] = None):
+    def vjp_input(self, x: Tensor, time_cond: Tensor, w, y: Optional[Tensor] = None):
         """``(y, dx)``: the network output at ``(x, time_cond)`` and the vector-Jacobian product ``w^T dy/dx`` (NCHW, fp32),
         from ONE recorded forward in the module's current train / eval state (eval: no dropout) and one backward that runs
         the data-gradient launches alone (``_Exec.input_grad_only``).  No autograd node is built and no parameter gradient
         is touched: nothing is written into ``flat_grad()`` or any ``p.grad``, so an EMA copy that is only being evaluated
         needs no gradient buffer.  ``dx`` is bit for bit the ``x.grad`` of ``forward(x.requires_grad_()).backward(w)``.
-        The pass runs in the record arithmetic in force (``ops.pass_arith(record=True)``), like any recording pass."""
+        The pass runs in the record arithmetic in force (``ops.pass_arith(record=True)``), like any recording pass.
+
+        Two phases: ``w`` may be a callable ``w_fn(out) -> w`` for a cotangent that depends on the output (measurement
+        guidance, psld_amd.guidance.PosteriorScoreFn).  It is called between the recorded forward and the backward, with the
+        output that is also returned, and hands back the float32 cotangent of that shape.  Whatever it launches runs on the
+        current stream and allocates through torch alone: the executor's arena and workspaces hold the recorded pass until
+        the backward has run."""
         if not x.is_cuda:
             raise RuntimeError("psld_amd.NCSNpp runs on MI355X only: the HIP extension has no CPU fallback "
                                "(use oracle/psld_oracle.py as the CPU checker)")
-        if x.dtype != torch.float32 or time_cond.dtype != torch.float32 or w.dtype != torch.float32:
+        two_phase = not torch.is_tensor(w) and callable(w)
+        if x.dtype != torch.float32 or time_cond.dtype != torch.float32 or (not two_phase and w.dtype != torch.float32):
             raise RuntimeError("NCSNpp.vjp_input expects float32 x, time_cond and w")
         ops.lib()
         lab, drop = self._labels(x, y)
@@ -633,6 +640,10 @@ class NCSNpp(nn.Module):
             ex = _Exec(self, record=True, input_grad_only=True)
             ex.want_dx = True
             out = ex.run(x.detach().contiguous(), time_cond.detach().contiguous(), lab, drop)
+            if two_phase:
+                w = w(out)
+                if not torch.is_tensor(w) or w.dtype != torch.float32:
+                    raise RuntimeError("NCSNpp.vjp_input: the cotangent callable must return a float32 tensor")
             if w.shape != out.shape:
                 raise ValueError(f"vjp_input: cotangent of shape {tuple(w.shape)} for an output of shape {tuple(out.shape)}")
             ex.backward(w.detach())

@@ -90,11 +90,23 @@ class SDEWrapper(_Base):
         pass
 
     def _guided(self, net):
-        """The network the sampler calls: ``net`` itself, or - for a label-conditioned network with
-        ``evaluation.label_to_sample`` set - its classifier-free-guidance front (``evaluation.cfg_scale``, default 1)."""
+        """The network the sampler calls: ``net`` itself; for a label-conditioned network with
+        ``evaluation.label_to_sample`` set its classifier-free-guidance front (``evaluation.cfg_scale``, default 1); with
+        ``evaluation.restore.task`` set its measurement-guidance front (``psld_amd.guidance.PosteriorScoreFn``:
+        ``evaluation.restore.sigma_y`` / ``.scale`` / ``.prior_var``), whose measurement the caller sets per batch."""
         ev = self.config.evaluation
+        restore = ev.get("restore", None)
+        task = restore.get("task", None) if restore is not None else None
         label = ev.get("label_to_sample", None)
-        if label is None or int(getattr(net, "label_classes", 0) or 0) <= 0:
+        labelled = label is not None and int(getattr(net, "label_classes", 0) or 0) > 0
+        if task is not None:
+            if labelled:
+                raise ValueError("evaluation.restore.task with evaluation.label_to_sample: measurement guidance runs the "
+                                 "unconditional network (labels are out of scope there)")
+            from .guidance import PosteriorScoreFn
+            return PosteriorScoreFn(net, self.sde, task, float(restore.get("sigma_y", 0.0)),
+                                    float(restore.get("scale", 1.0)), float(restore.get("prior_var", 1.0)))
+        if not labelled:
             return net
         from .guidance import CFGScoreFn
         return CFGScoreFn(net, int(label), float(ev.get("cfg_scale", 1.0)))
