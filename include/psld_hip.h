@@ -831,6 +831,29 @@ int psld_restore_measure_f32(const float* u, const float* eps, const float* y, c
                              hipStream_t stream);
 int psld_restore_combine_f32(const float* eps, const float* g, const float* dx, const psld_restore_coeffs_t* q,
                              int batch, int c, int hw, float* out, hipStream_t stream);
+/* The deconv operator ("Deconvolution"; csrc/deconv.hip): A x = k (*) x per channel, PERIODIC boundary, one PSF k for
+ * every image and channel.  A A^T is no multiple of the identity, so these are entry points of their own and not a fourth
+ * operator code of psld_restore_measure_f32 (which keeps refusing code 3).  h and w: each a power of two from 4 to 128
+ * (psld_restore_deconv_supported returns 1 for such a pair and 0 otherwise; anything else is refused before the launch).
+ *   hhat: float64 [h][w/2 + 1][2], the Hermitian half of FFT2(k wrapped onto the h x w torus, centred at its middle tap),
+ *         computed once on the host; yhat: float64 [planes][h][w/2 + 1][2], the same half of FFT2(y) per plane, written by
+ *         psld_restore_deconv_spectrum_f32 once per measurement.  Both 16-byte aligned.
+ * psld_restore_deconv_f32 is the measure step: with x0^ as above and x^ = FFT2(x0^) it writes
+ *         g = IFFT2( conj(hhat) (sigma_y2 + r2) / (sigma_y2 + r2 |hhat|^2) (yhat - hhat x^) )      [batch, c, h, w]
+ *   and the cotangent (q_e[0] g | q_e[1] g) of the state's shape; a frequency whose denominator is exactly 0 contributes 0.
+ *   sigma_y2 = sigma_y^2 and r2 = r_t^2 (kappa of q = scale / (sigma_y2 + r2) is read by psld_restore_combine_f32 alone,
+ *   which serves this operator unchanged); both >= 0 with a positive finite sum.  For |hhat| = 1 this is A^T (y - A x0^).
+ * psld_restore_deconv_apply_f32 writes A x (adjoint = 0) or A^T x (adjoint = 1) of float32 planes x [planes][h][w].
+ * float32 planes in memory, float64 in registers and LDS; one workgroup per plane at a time (any number of planes), the
+ * plane's packed transform in LDS: (h (w/2 + 1) + max(h, w) / 2) * 16 bytes, 131 KiB at 128 x 128; no scratch beyond LDS.
+ * 16-byte accesses to the float32 tensors when their pointers are 16-byte aligned, 4-byte ones otherwise: same values. */
+int psld_restore_deconv_supported(int h, int w);
+int psld_restore_deconv_spectrum_f32(const float* y, int planes, int h, int w, double* yhat, hipStream_t stream);
+int psld_restore_deconv_f32(const float* u, const float* eps, const double* yhat, const double* hhat,
+                            const psld_restore_coeffs_t* q, double sigma_y2, double r2, int batch, int c, int h, int w,
+                            float* g, float* cot, hipStream_t stream);
+int psld_restore_deconv_apply_f32(const float* x, const double* hhat, int adjoint, int planes, int h, int w, float* out,
+                                  hipStream_t stream);
 /* Edges of the path.  Writer: position half of the f64 [B,c_total,H,W] state ->
  * uint8 [B,H,W,c] = trunc(clip((x*0.5+0.5)*255, 0, 255)) (callbacks.py:103-107, util.py:147-158).
  * Loader: uint8 [B,H,W,c] -> f32 [B,c,H,W] = img/127.5-1 (norm) or img/255, optional per-image

@@ -244,6 +244,10 @@ SIGNATURES = {
     "psld_ei_sde_step_f64": (I, [P, P, P, C.POINTER(EiSdeCoeffs), I, I, I, P, P]),
     "psld_restore_measure_f32": (I, [P, P, P, P, I, I, C.POINTER(RestoreCoeffs), I, I, I, I, P, P, P]),
     "psld_restore_combine_f32": (I, [P, P, P, C.POINTER(RestoreCoeffs), I, I, I, P, P]),
+    "psld_restore_deconv_supported": (I, [I, I]),
+    "psld_restore_deconv_spectrum_f32": (I, [P, I, I, I, P, P]),
+    "psld_restore_deconv_f32": (I, [P, P, P, P, C.POINTER(RestoreCoeffs), D, D, I, I, I, I, P, P, P]),
+    "psld_restore_deconv_apply_f32": (I, [P, P, I, I, I, I, P, P]),
     "psld_samples_to_uint8": (I, [P, P, I, I, I, I, I, P]),
     "psld_uint8_to_images_f32": (I, [P, P, P, I, I, I, I, I, P]),
     "psld_lincomb_f64": (I, [P, P, P, P, I, LL, P, P]),

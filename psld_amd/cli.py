@@ -19,6 +19,7 @@
     python -m psld_amd.cli bpd --config c10_sota --data x.npy --ckpt last.ckpt [--n-probes N --n-momentum N --rtol R --atol A]
                                                                            (no counterpart: psld_amd/likelihood.py)
     python -m psld_amd.cli restore --config c10_sota --data x.npy --task mask|gray|pool2|pool4 --sigma-y 0.05
+    python -m psld_amd.cli restore --config c10_sota --data x.npy --task deconv --psf gauss:1.5 --sigma-y 0.05
                                    [--mask m.npy --guidance-scale G evaluation.sampler.name=ei_sde ...]
                                                                            (no counterpart: measurement-guided restoration
                                                                            with the unconditional network, psld_amd/guidance.py)
@@ -526,14 +527,15 @@ def _masks(cfg, args, n, dev):
 def restore(args, overrides):
     """Measurement-guided restoration (no counterpart in the reference): the images of ``--data`` are
     degraded here - ``y = A x0 + N(0, sigma_y^2)`` with ``A`` the operator of ``--task`` (``mask``: the pixels where
-    ``--mask`` is 1; ``gray``; ``pool2`` / ``pool4``: block averages) and the noise from a generator seeded with
+    ``--mask`` is 1; ``gray``; ``pool2`` / ``pool4``: block averages; ``deconv``: the PERIODIC convolution with ``--psf``, by the
+    apply kernel - the boundary the guidance assumes) and the noise from a generator seeded with
     ``evaluation.seed`` + rank - and restored from ``prior_sampling`` by the sampler ``evaluation.sampler.name`` running the
     unconditional network under ``PosteriorScoreFn``.  Writes images/ (the restorations), corrupt/ (the measurement shown at
-    image scale, ``A^T y``) and batch/ (the originals) like ``inpaint``; ``evaluation.restore.prior_var=V`` sets the pixel
-    prior's variance."""
+    image scale, ``A^T y``; for ``deconv`` the blurred image ``y`` itself) and batch/ (the originals) like ``inpaint``;
+    ``evaluation.restore.prior_var=V`` sets the pixel prior's variance."""
     from psld_amd import config as C, ops
     from psld_amd.ddp import init_distributed, shard_range
-    from psld_amd.guidance import apply_adjoint, apply_operator
+    from psld_amd.guidance import apply_adjoint, apply_operator, check_task, parse_psf
     from psld_amd.registry import get_module
     import torch.distributed as dist
     rank, local, world = init_distributed()
@@ -541,8 +543,17 @@ def restore(args, overrides):
     dev = torch.device("cuda", local)
     cfg = getattr(C, args.config)()
     cfg.evaluation.restore = {"task": args.task, "sigma_y": args.sigma_y, "scale": args.guidance_scale, "prior_var": 1.0}
+    if args.psf is not None:
+        cfg.evaluation.restore["psf"] = args.psf
     cfg = parse_overrides(cfg, overrides)
     ev = cfg.evaluation
+    psf = ev.restore.get("psf", None)
+    try:
+        check_task(args.task, psf)
+        if psf is not None:
+            parse_psf(psf, cfg.data.image_size, cfg.data.image_size)
+    except ValueError as e:
+        raise SystemExit(str(e))
     momentum = _wants_momentum(cfg)
     if ev.sampler.name in ("ip_em_sde", "cc_em_sde"):
         raise SystemExit(f"restore: evaluation.sampler.name={ev.sampler.name} takes its own conditioning; use an "
@@ -573,7 +584,7 @@ def restore(args, overrides):
         stop = min(start + ev.batch_size, hi)
         x0 = ops.uint8_to_images(data[start:stop].contiguous(), norm=cfg.data.norm)
         mask = masks[start:stop].permute(0, 3, 1, 2).contiguous().to(torch.float32) if masks is not None else None
-        y = apply_operator(x0, args.task, mask)
+        y = apply_operator(x0, args.task, mask, psf)
         y = y + float(ev.restore.sigma_y) * torch.randn(y.shape, device=dev, generator=gen)
         if mask is not None:
             y = y * mask                                                   # nothing is measured where the mask is 0
@@ -586,7 +597,7 @@ def restore(args, overrides):
         _save_u8(os.path.join(dirs["images"], name), u8.cpu().numpy(), ev.save_mode)
         to01 = lambda t: (t * 0.5 + 0.5) if cfg.data.norm else t
         to_u8 = lambda t: (t.clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
-        shown = to01(apply_adjoint(y, args.task, mask))
+        shown = to01(y if args.task == "deconv" else apply_adjoint(y, args.task, mask))
         _save_u8(os.path.join(dirs["corrupt"], name), to_u8(shown * mask if mask is not None else shown), ev.save_mode)
         _save_u8(os.path.join(dirs["batch"], name), to_u8(to01(x0)), ev.save_mode)
         if momentum:
@@ -712,9 +723,14 @@ def build_parser() -> argparse.ArgumentParser:
                            help="classifier-free guidance scale (evaluation.cfg_scale, default 1.0 = plain conditional "
                                 "sampling; 0 = unconditional; other values run the doubled batch)")
         if name == "restore":
-            p.add_argument("--task", required=True, choices=["mask", "gray", "pool2", "pool4"],
+            p.add_argument("--task", required=True, choices=["mask", "gray", "pool2", "pool4", "deconv"],
                            help="the degradation A: mask (the pixels where --mask is 1), gray ((R + G + B) / sqrt 3), "
-                                "pool2 / pool4 (2x2 / 4x4 block averages); each has orthonormal rows")
+                                "pool2 / pool4 (2x2 / 4x4 block averages), each with orthonormal rows; deconv (the periodic "
+                                "convolution with --psf: deblurring; image sides powers of two from 4 to 128)")
+            p.add_argument("--psf", default=None, metavar="PSF",
+                           help="deconv only (and required there; evaluation.restore.psf): gauss:S (standard deviation S "
+                                "pixels), box:K (K x K, K odd), motion:L (1 x L horizontal, L odd) or a float [kh, kw] .npy "
+                                "file with odd sizes, used as given; the same PSF for every image and channel, periodic boundary")
             p.add_argument("--sigma-y", type=float, default=0.0, metavar="S",
                            help="standard deviation of the measurement noise, in network-input units (added here, seeded)")
             p.add_argument("--guidance-scale", type=float, default=1.0, metavar="G",

@@ -75,21 +75,109 @@ class CFGScoreFn:
 
 
 # ---- measurement guidance -----------------------------------------------------------------------------
-# task -> (operator code, block size); every operator has orthonormal rows (A A^T = I on its range)
+# task -> (operator code, block size); mask, gray and pool have orthonormal rows (A A^T = I on their range) and share
+# ops.restore_measure; deconv (a periodic blur, DESIGN section 13, "Deconvolution") has not, and has kernels of its own:
+# DECONV is a host-side tag that is never handed to the library (whose operator code 3 stays refused)
+DECONV = -1
 OPERATORS = {"mask": (_lib.RESTORE_MASK, 1), "gray": (_lib.RESTORE_GRAY, 1), "pool2": (_lib.RESTORE_POOL, 2),
-             "pool4": (_lib.RESTORE_POOL, 4)}
+             "pool4": (_lib.RESTORE_POOL, 4), "deconv": (DECONV, 1)}
 
 
-def check_task(task) -> str:
+def check_task(task, psf="unchecked") -> str:
+    """The task's name if it is one; with ``psf`` given also: a PSF goes with ``deconv`` and with no other task."""
     if task not in OPERATORS:
         raise ValueError(f"restore: task must be one of {sorted(OPERATORS)}, got {task!r}")
+    if not (isinstance(psf, str) and psf == "unchecked") and (psf is not None) != (task == "deconv"):
+        raise ValueError("restore: a PSF (gauss:S | box:K | motion:L | file.npy) goes with the task deconv and with no other"
+                         f" (task {task!r}, psf {psf!r})")
     return task
 
 
-def apply_operator(x: torch.Tensor, task: str, mask=None) -> torch.Tensor:
-    """``A x`` of images ``x`` ``[B, C, H, W]`` in torch operations (setting a problem up; the per-step arithmetic is
-    ``ops.restore_measure``): mask ``M . x``, gray ``(x_R + x_G + x_B) / sqrt(3)``, pool the block sums over ``k``."""
-    op, k = OPERATORS[check_task(task)]
+# ---- the deconv operator: A x = k (*) x per channel, periodic boundary ------------------------------------------------------
+def parse_psf(psf, h: int, w: int) -> np.ndarray:
+    """The PSF on the ``h x w`` torus, float64 ``[h, w]`` with its middle tap at ``[0, 0]``.  ``psf``: ``gauss:S`` (``exp(-d^2 /
+    2 S^2)`` of the wrapped distance ``d``, ``S > 0``, normalised to sum 1), ``box:K`` (K x K uniform, K odd), ``motion:L`` (1 x L
+    horizontal uniform, L odd), the path of a ``.npy`` file or an array: float ``[kh, kw]``, both odd and no larger than the
+    image, used as given."""
+    h, w = int(h), int(w)
+    if isinstance(psf, str) and not psf.endswith(".npy"):
+        kind, _, arg = psf.partition(":")
+        try:
+            val = float(arg)
+        except ValueError:
+            raise ValueError(f"restore: PSF {psf!r} is not gauss:S | box:K | motion:L | file.npy") from None
+        if kind == "gauss":
+            if not (val > 0.0 and math.isfinite(val)):
+                raise ValueError(f"restore: PSF {psf!r}: S must be > 0")
+            dy = np.minimum(np.arange(h), h - np.arange(h)).astype(np.float64)[:, None]
+            dx = np.minimum(np.arange(w), w - np.arange(w)).astype(np.float64)[None, :]
+            k = np.exp(-(dy * dy + dx * dx) / (2.0 * val * val))
+            return k / k.sum()
+        if kind not in ("box", "motion"):
+            raise ValueError(f"restore: PSF {psf!r} is not gauss:S | box:K | motion:L | file.npy")
+        n = int(val)
+        if n != val or n < 1 or n % 2 == 0:
+            raise ValueError(f"restore: PSF {psf!r}: the size must be an odd whole number (an even size has no middle tap)")
+        taps = np.full((n, n) if kind == "box" else (1, n), 1.0 / (n * n if kind == "box" else n))
+    else:
+        taps = np.asarray(np.load(psf) if isinstance(psf, str) else psf, dtype=np.float64)
+        if taps.ndim != 2 or taps.shape[0] % 2 == 0 or taps.shape[1] % 2 == 0:
+            raise ValueError(f"restore: a PSF array must be [kh, kw] with both sizes odd, got shape {taps.shape}")
+        if not np.isfinite(taps).all():
+            raise ValueError("restore: the PSF array holds values that are not finite")
+    kh, kw = taps.shape
+    if kh > h or kw > w:
+        raise ValueError(f"restore: a {kh} x {kw} PSF is larger than the {h} x {w} image")
+    k = np.zeros((h, w))
+    rows, cols = (np.arange(kh) - kh // 2) % h, (np.arange(kw) - kw // 2) % w
+    k[np.ix_(rows, cols)] = taps
+    return k
+
+
+def psf_spectrum(psf, h: int, w: int) -> np.ndarray:
+    """``h^ = FFT2`` of ``parse_psf(psf, h, w)`` in host float64: the Hermitian half, complex128 ``[h, w/2 + 1]``."""
+    return np.fft.rfft2(parse_psf(psf, h, w))
+
+
+def _psf_key(psf):
+    return psf if isinstance(psf, str) else (np.asarray(psf, dtype=np.float64).tobytes(), np.asarray(psf).shape)
+
+
+_HHAT = {}
+
+
+def device_spectrum(psf, h: int, w: int, device) -> torch.Tensor:
+    """``psf_spectrum`` as the float64 ``[h, w/2 + 1, 2]`` device tensor the deconv kernels read (kept per PSF, size, device)."""
+    key = (_psf_key(psf), int(h), int(w), str(device))
+    if key not in _HHAT:
+        if len(_HHAT) > 64:
+            _HHAT.clear()
+        hh = psf_spectrum(psf, h, w)
+        _HHAT[key] = torch.from_numpy(np.stack([hh.real, hh.imag], axis=-1).copy()).to(device).contiguous()
+    return _HHAT[key]
+
+
+def _apply_deconv(x: torch.Tensor, psf, adjoint: bool) -> torch.Tensor:
+    """``k (*) x`` (adjoint: the correlation) over the last two dimensions: the apply kernel on device tensors (float32
+    arithmetic in memory, as the kernels'), ``torch.fft`` in float64 on CPU tensors."""
+    if x.dim() != 4:
+        raise ValueError(f"restore: images of shape {tuple(x.shape)} are not [B, C, H, W]")
+    h, w = x.shape[-2:]
+    if x.is_cuda:
+        hhat = device_spectrum(psf, h, w, x.device)
+        return ops.restore_deconv_apply(x.detach().to(torch.float32).contiguous(), hhat, adjoint).to(x.dtype)
+    hh = torch.from_numpy(psf_spectrum(psf, h, w))
+    xf = torch.fft.rfft2(x.detach().to(torch.float64))
+    return torch.fft.irfft2(xf * (hh.conj() if adjoint else hh), s=(h, w)).to(x.dtype)
+
+
+def apply_operator(x: torch.Tensor, task: str, mask=None, psf=None) -> torch.Tensor:
+    """``A x`` of images ``x`` ``[B, C, H, W]`` (setting a problem up; the per-step arithmetic is ``ops.restore_measure`` /
+    ``ops.restore_deconv_measure``): mask ``M . x``, gray ``(x_R + x_G + x_B) / sqrt(3)``, pool the block sums over ``k``,
+    deconv the periodic convolution with the PSF ``psf`` (``parse_psf``) - on device tensors by the apply kernel."""
+    op, k = OPERATORS[check_task(task, psf)]
+    if op == DECONV:
+        return _apply_deconv(x, psf, False)
     want = ops.restore_measurement_shape(x.shape, op, k, 0)
     if op == _lib.RESTORE_MASK:
         if mask is None or tuple(mask.shape) != want:
@@ -101,10 +189,12 @@ def apply_operator(x: torch.Tensor, task: str, mask=None) -> torch.Tensor:
     return x.reshape(b, c, h // k, k, w // k, k).sum(dim=(3, 5)) / k
 
 
-def apply_adjoint(y: torch.Tensor, task: str, mask=None) -> torch.Tensor:
+def apply_adjoint(y: torch.Tensor, task: str, mask=None, psf=None) -> torch.Tensor:
     """``A^T y`` at image shape: the measurement itself (mask), the mean grey value in all three channels (gray), the block
-    mean in every pixel of its block (pool) - the measurement shown at image scale."""
-    op, k = OPERATORS[check_task(task)]
+    mean in every pixel of its block (pool) - the measurement shown at image scale; deconv: the correlation with the PSF."""
+    op, k = OPERATORS[check_task(task, psf)]
+    if op == DECONV:
+        return _apply_deconv(y, psf, True)
     if op == _lib.RESTORE_MASK:
         return y * mask.to(y.dtype)
     if op == _lib.RESTORE_GRAY:
@@ -167,6 +257,7 @@ def posterior_coeffs(sde, t: float, sigma_y: float, scale: float = 1.0, prior_va
         raise ValueError(f"PosteriorScoreFn: sigma_y^2 + r_t^2 = {var!r} at t = {t} is not a positive number "
                          f"(sigma_y = {sigma_y}, prior_var = {prior_var})")
     q.kappa = float(scale) / var
+    q.r2, q.sigma_y2 = r2, float(sigma_y) ** 2      # python attributes beside the struct's fields: what the deconv measure step takes
     return q
 
 
@@ -185,14 +276,25 @@ class PosteriorScoreFn:
 
     The guided pass is a RECORDING pass: its arithmetic is the record arithmetic (``ops.set_record_math``), not the
     evaluation arithmetic of the plain sampling forward (``ops.set_math_mode`` / ``ops.set_eval_math``), as for ``bpd``.
-    Labels are out of scope here: a ``CFGScoreFn`` is refused as ``net``."""
+    Labels are out of scope here: a ``CFGScoreFn`` is refused as ``net``.
 
-    def __init__(self, net, sde, operator: str, sigma_y: float, scale: float = 1.0, prior_var: float = 1.0):
+    ``operator="deconv"`` with ``psf=`` (``parse_psf``: ``gauss:S | box:K | motion:L``, a ``.npy`` path or an array; required
+    with this operator, refused with the others) is a periodic blur ``A x = k (*) x`` ("Deconvolution").  Its rows are not
+    orthonormal, so ``g`` is ``(sigma_y^2 + r_t^2) A^T (sigma_y^2 I + r_t^2 A A^T)^-1 (y - A x0^)``, computed per plane in the
+    2-D DFT domain by ``ops.restore_deconv_measure`` from the PSF's spectrum (host float64, held on the device) and the
+    measurement's (``ops.restore_deconv_spectrum``, once per measurement, at the first guided call).  The measurement has
+    the image's shape; H and W are powers of two from 4 to 128."""
+
+    def __init__(self, net, sde, operator: str, sigma_y: float, scale: float = 1.0, prior_var: float = 1.0, psf=None):
         if isinstance(net, CFGScoreFn):
             raise ValueError("PosteriorScoreFn: labels are out of scope here - pass the network itself, not a CFGScoreFn")
         self.net, self.sde = net, sde
-        self.operator = check_task(operator)
+        self.operator = check_task(operator, psf)
         self.op, self.k = OPERATORS[operator]
+        self.psf = psf
+        if psf is not None:
+            parse_psf(psf, 128, 128)                     # refuses a malformed PSF now; its size is checked against the image's
+        self.yhat = None
         self.sigma_y, self.scale, self.prior_var = float(sigma_y), float(scale), float(prior_var)
         if not math.isfinite(self.scale) or not math.isfinite(self.sigma_y) or self.sigma_y < 0:
             raise ValueError(f"PosteriorScoreFn: sigma_y must be >= 0 and scale finite, got {sigma_y!r}, {scale!r}")
@@ -224,6 +326,7 @@ class PosteriorScoreFn:
             raise ValueError(f"PosteriorScoreFn: mask of shape {tuple(mask.shape)} for a measurement of shape {tuple(y.shape)}")
         self.y = y.detach().to(torch.float32).contiguous()
         self.mask = None if mask is None else mask.detach().to(device=y.device, dtype=torch.float32).contiguous()
+        self.yhat = None                                  # deconv: the measurement's spectrum, made by the first guided call
         return self
 
     def coeffs(self, t: float) -> _lib.RestoreCoeffs:
@@ -237,7 +340,22 @@ class PosteriorScoreFn:
     def _measurement_for(self, x32):
         if self.y is None:
             raise RuntimeError("PosteriorScoreFn: set_measurement(y, mask) first")
-        want = ops.restore_measurement_shape(x32.shape, self.op, self.k, 0 if self.sde.type == "vpsde" else 1)
+        augmented = 0 if self.sde.type == "vpsde" else 1
+        if self.op == DECONV:
+            # the measurement has the image's shape; what the kernels read is its spectrum and the PSF's
+            want = ops.restore_measurement_shape(x32.shape, _lib.RESTORE_MASK, 1, augmented)
+            if tuple(self.y.shape) != want or self.y.device != x32.device:
+                raise ValueError(f"PosteriorScoreFn: measurement of shape {tuple(self.y.shape)} on {self.y.device}, the operator "
+                                 f"deconv and a state of shape {tuple(x32.shape)} on {x32.device} need {want}")
+            h, w = want[2:]
+            hhat = device_spectrum(self.psf, h, w, x32.device) if x32.is_cuda else None
+            if hhat is None or not ops.restore_deconv_supported(h, w):
+                raise ValueError(f"PosteriorScoreFn: the deconv operator needs device tensors and a map whose sides are powers "
+                                 f"of two from 4 to 128, got {h} x {w} on {x32.device}")
+            if self.yhat is None:
+                self.yhat = ops.restore_deconv_spectrum(self.y)
+            return self.yhat, hhat
+        want = ops.restore_measurement_shape(x32.shape, self.op, self.k, augmented)
         if tuple(self.y.shape) != want or self.y.device != x32.device:
             raise ValueError(f"PosteriorScoreFn: measurement of shape {tuple(self.y.shape)} on {self.y.device}, the operator "
                              f"{self.operator} and a state of shape {tuple(x32.shape)} on {x32.device} need {want}")
@@ -274,7 +392,10 @@ class PosteriorScoreFn:
 
         def w_fn(out):
             q = self.coeffs(read_time())
-            g, w = ops.restore_measure(x32, out, y, mask, self.op, self.k, q)
+            if self.op == DECONV:                           # (y, mask) are (the measurement's spectrum, the PSF's)
+                g, w = ops.restore_deconv_measure(x32, out, y, mask, q, q.sigma_y2, q.r2)
+            else:
+                g, w = ops.restore_measure(x32, out, y, mask, self.op, self.k, q)
             kept.extend((g, q))
             return w
 

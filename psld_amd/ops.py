@@ -1760,6 +1760,76 @@ def restore_combine(eps: Tensor, g: Tensor, dx: Tensor, q: RestoreCoeffs, out: O
     return out
 
 
+def restore_deconv_supported(h: int, w: int) -> bool:
+    """Whether the deconv kernels take ``h x w`` planes (psld_restore_deconv_supported: each side a power of two, 4 .. 128)."""
+    return bool(lib().psld_restore_deconv_supported(int(h), int(w)))
+
+
+def _deconv_planes(x: Tensor, hhat: Optional[Tensor], what: str):
+    """(planes, h, w) of float32 ``[..., h, w]`` planes for the deconv kernels; ``hhat`` float64 ``[h, w/2 + 1, 2]`` checked."""
+    if _chk(x).dim() < 2:
+        raise ValueError(f"{what}: planes of shape {tuple(x.shape)} are not [..., H, W]")
+    h, w = int(x.shape[-2]), int(x.shape[-1])
+    if not restore_deconv_supported(h, w):
+        raise ValueError(f"{what}: a {h} x {w} map: each side must be a power of two from 4 to 128")
+    if x.numel() == 0:
+        raise ValueError(f"{what}: no planes in a tensor of shape {tuple(x.shape)}")
+    if hhat is not None and (tuple(_chk(hhat, torch.float64).shape) != (h, w // 2 + 1, 2) or hhat.device != x.device):
+        raise ValueError(f"{what}: PSF spectrum of shape {tuple(hhat.shape)} on {hhat.device}, {h} x {w} planes on {x.device} "
+                         f"need {(h, w // 2 + 1, 2)}")
+    return x.numel() // (h * w), h, w
+
+
+def restore_deconv_spectrum(y: Tensor) -> Tensor:
+    """``FFT2`` of float32 planes ``y`` ``[..., H, W]``: the Hermitian half as float64 ``[..., H, W/2 + 1, 2]`` (real, imaginary)
+    - what ``restore_deconv_measure`` takes as ``yhat`` (psld_restore_deconv_spectrum_f32; once per measurement)."""
+    planes, h, w = _deconv_planes(y, None, "restore_deconv_spectrum")
+    out = torch.empty(tuple(y.shape[:-1]) + (w // 2 + 1, 2), device=y.device, dtype=torch.float64)
+    check(lib().psld_restore_deconv_spectrum_f32(y.data_ptr(), planes, h, w, out.data_ptr(), _stream()),
+          "psld_restore_deconv_spectrum_f32")
+    return out
+
+
+def restore_deconv_measure(u: Tensor, eps: Tensor, yhat: Tensor, hhat: Tensor, q: RestoreCoeffs, sigma_y2: float, r2: float):
+    """``(g, w)`` of one guided call under the deconv operator (psld_restore_deconv_f32; DESIGN section 13, "Deconvolution"):
+    ``g = IFFT2(conj(h^) (sigma_y2 + r2) / (sigma_y2 + r2 |h^|^2) (y^ - h^ FFT2(x0^)))`` ``[B, C, H, W]`` and the cotangent
+    ``(q_e[0] g | q_e[1] g)`` of the state's shape.  ``yhat``: ``restore_deconv_spectrum(y)`` of the measurement ``[B, C, H, W]``;
+    ``hhat``: float64 ``[H, W/2 + 1, 2]``, the PSF's spectrum."""
+    if tuple(_chk(eps).shape) != tuple(_chk(u).shape) or u.dim() != 4:
+        raise ValueError(f"restore_deconv_measure: eps of shape {tuple(eps.shape)} for a state of shape {tuple(u.shape)}")
+    if q.augmented not in (0, 1):
+        raise ValueError(f"restore_deconv_measure: augmented must be 0 or 1, got {q.augmented}")
+    b, ct, h, w = u.shape
+    if q.augmented and ct % 2:
+        raise ValueError(f"restore_deconv_measure: an augmented state needs an even channel count, got {ct}")
+    c = ct // 2 if q.augmented else ct
+    _deconv_planes(u, hhat, "restore_deconv_measure")
+    if tuple(_chk(yhat, torch.float64).shape) != (b, c, h, w // 2 + 1, 2):
+        raise ValueError(f"restore_deconv_measure: measurement spectrum of shape {tuple(yhat.shape)}, this state needs "
+                         f"{(b, c, h, w // 2 + 1, 2)}")
+    sigma_y2, r2 = float(sigma_y2), float(r2)
+    if not (sigma_y2 >= 0.0 and r2 >= 0.0 and 0.0 < sigma_y2 + r2 < float("inf")):
+        raise ValueError(f"restore_deconv_measure: sigma_y^2 = {sigma_y2!r} and r_t^2 = {r2!r} must be >= 0 with a positive sum")
+    g = torch.empty((b, c, h, w), device=u.device, dtype=torch.float32)
+    cot = torch.empty_like(u)
+    check(lib().psld_restore_deconv_f32(u.data_ptr(), eps.data_ptr(), yhat.data_ptr(), hhat.data_ptr(), C.byref(q), sigma_y2,
+                                        r2, b, c, h, w, g.data_ptr(), cot.data_ptr(), _stream()), "psld_restore_deconv_f32")
+    return g, cot
+
+
+def restore_deconv_apply(x: Tensor, hhat: Tensor, adjoint: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """``A x`` (``adjoint``: ``A^T x``) of float32 planes ``[..., H, W]`` under the periodic blur with spectrum ``hhat``
+    (psld_restore_deconv_apply_f32)."""
+    planes, h, w = _deconv_planes(x, hhat, "restore_deconv_apply")
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(_chk(out).shape) != tuple(x.shape):
+        raise ValueError(f"restore_deconv_apply: out of shape {tuple(out.shape)} for planes of shape {tuple(x.shape)}")
+    check(lib().psld_restore_deconv_apply_f32(x.data_ptr(), hhat.data_ptr(), int(bool(adjoint)), planes, h, w, out.data_ptr(),
+                                              _stream()), "psld_restore_deconv_apply_f32")
+    return out
+
+
 def samples_to_uint8(samples: Tensor, is_augmented: bool = True, denorm: bool = True) -> Tensor:
     """[B,2C,H,W] f64 sampler output -> uint8 [B,H,W,C] ready for the PNG encoder (SimpleImageWriter,
     callbacks.py:88-124): 16x less device->host traffic than copying the f64 state."""

@@ -93,7 +93,8 @@ class SDEWrapper(_Base):
         """The network the sampler calls: ``net`` itself; for a label-conditioned network with
         ``evaluation.label_to_sample`` set its classifier-free-guidance front (``evaluation.cfg_scale``, default 1); with
         ``evaluation.restore.task`` set its measurement-guidance front (``psld_amd.guidance.PosteriorScoreFn``:
-        ``evaluation.restore.sigma_y`` / ``.scale`` / ``.prior_var``), whose measurement the caller sets per batch."""
+        ``evaluation.restore.sigma_y`` / ``.scale`` / ``.prior_var``, and ``.psf`` for the task ``deconv``), whose measurement
+        the caller sets per batch."""
         ev = self.config.evaluation
         restore = ev.get("restore", None)
         task = restore.get("task", None) if restore is not None else None
@@ -105,7 +106,8 @@ class SDEWrapper(_Base):
                                  "unconditional network (labels are out of scope there)")
             from .guidance import PosteriorScoreFn
             return PosteriorScoreFn(net, self.sde, task, float(restore.get("sigma_y", 0.0)),
-                                    float(restore.get("scale", 1.0)), float(restore.get("prior_var", 1.0)))
+                                    float(restore.get("scale", 1.0)), float(restore.get("prior_var", 1.0)),
+                                    psf=restore.get("psf", None))
         if not labelled:
             return net
         from .guidance import CFGScoreFn
