@@ -854,6 +854,29 @@ int psld_restore_deconv_f32(const float* u, const float* eps, const double* yhat
                             float* g, float* cot, hipStream_t stream);
 int psld_restore_deconv_apply_f32(const float* x, const double* hhat, int adjoint, int planes, int h, int w, float* out,
                                   hipStream_t stream);
+/* Super-resolution ("Super-resolution"; csrc/deconv.hip): A x = D_s (k (*) x), the periodic blur of the deconv
+ * operator followed by keeping the samples (s i, s j), s = 2 or 4; the measurement is [batch, c, h/s, w/s].  A A^T is circulant
+ * on the low-resolution grid with eigenvalues lam, so (sigma_y2 I + r2 A A^T)^-1 is a pointwise division there.  h and w: each
+ * a power of two up to 128 with h/s >= 4 and w/s >= 4 (psld_restore_sr_supported returns 1 for such a triple, 0 otherwise;
+ * anything else is refused before the launch).
+ *   hhat: as for deconv, float64 [h][w/2 + 1][2], 16-byte aligned;
+ *   lam:  float64 [h/s][w/(2s) + 1], lam[m1][m2] = (1 / s^2) sum_{a, b < s} |h^[m1 + a h/s][m2 + b w/s]|^2, real and symmetric,
+ *         computed once on the host.
+ * psld_restore_sr_f32 is the measure step: z = IFFT2(hhat FFT2(x0^)), rho[i][j] = y[i][j] - z[s i][s j],
+ *         v = IFFT2'( (sigma_y2 + r2) / (sigma_y2 + r2 lam) FFT2'(rho) ) on the low-resolution grid (denominator 0: 0),
+ *         g = IFFT2( conj(hhat) FFT2(D_s^T v) )                                                   [batch, c, h, w]
+ *   and the cotangent (q_e[0] g | q_e[1] g), all three transform pairs of a plane in the LDS of one workgroup, the
+ *   low-resolution plane in the storage of the full one (the deconv kernels' LDS budget, nothing added).
+ * psld_restore_sr_apply_f32: adjoint = 0: out [planes][h/s][w/s] = A x of x [planes][h][w]; adjoint = 1: out [planes][h][w] =
+ *   A^T x of x [planes][h/s][w/s].  h and w are the FULL plane's sides in both directions.
+ * float32 tensors, float64 in registers and LDS; 16-byte accesses when the float32 pointers are 16-byte aligned, 4-byte ones
+ * otherwise: same values. */
+int psld_restore_sr_supported(int h, int w, int s);
+int psld_restore_sr_f32(const float* u, const float* eps, const float* y, const double* hhat, const double* lam,
+                        const psld_restore_coeffs_t* q, double sigma_y2, double r2, int batch, int c, int h, int w, int s,
+                        float* g, float* cot, hipStream_t stream);
+int psld_restore_sr_apply_f32(const float* x, const double* hhat, int adjoint, int planes, int h, int w, int s, float* out,
+                              hipStream_t stream);
 /* Edges of the path.  Writer: position half of the f64 [B,c_total,H,W] state ->
  * uint8 [B,H,W,c] = trunc(clip((x*0.5+0.5)*255, 0, 255)) (callbacks.py:103-107, util.py:147-158).
  * Loader: uint8 [B,H,W,c] -> f32 [B,c,H,W] = img/127.5-1 (norm) or img/255, optional per-image

@@ -248,6 +248,9 @@ SIGNATURES = {
     "psld_restore_deconv_spectrum_f32": (I, [P, I, I, I, P, P]),
     "psld_restore_deconv_f32": (I, [P, P, P, P, C.POINTER(RestoreCoeffs), D, D, I, I, I, I, P, P, P]),
     "psld_restore_deconv_apply_f32": (I, [P, P, I, I, I, I, P, P]),
+    "psld_restore_sr_supported": (I, [I, I, I]),
+    "psld_restore_sr_f32": (I, [P, P, P, P, P, C.POINTER(RestoreCoeffs), D, D, I, I, I, I, I, P, P, P]),
+    "psld_restore_sr_apply_f32": (I, [P, P, I, I, I, I, I, P, P]),
     "psld_samples_to_uint8": (I, [P, P, I, I, I, I, I, P]),
     "psld_uint8_to_images_f32": (I, [P, P, P, I, I, I, I, I, P]),
     "psld_lincomb_f64": (I, [P, P, P, P, I, LL, P, P]),

@@ -20,6 +20,7 @@
                                                                            (no counterpart: psld_amd/likelihood.py)
     python -m psld_amd.cli restore --config c10_sota --data x.npy --task mask|gray|pool2|pool4 --sigma-y 0.05
     python -m psld_amd.cli restore --config c10_sota --data x.npy --task deconv --psf gauss:1.5 --sigma-y 0.05
+    python -m psld_amd.cli restore --config c10_sota --data x.npy --task sr4 [--psf bicubic|block|gauss:S|box:K|motion:L|file.npy] --sigma-y 0.05
                                    [--mask m.npy --guidance-scale G evaluation.sampler.name=ei_sde ...]
                                                                            (no counterpart: measurement-guided restoration
                                                                            with the unconditional network, psld_amd/guidance.py)
@@ -528,14 +529,15 @@ def restore(args, overrides):
     """Measurement-guided restoration (no counterpart in the reference): the images of ``--data`` are
     degraded here - ``y = A x0 + N(0, sigma_y^2)`` with ``A`` the operator of ``--task`` (``mask``: the pixels where
     ``--mask`` is 1; ``gray``; ``pool2`` / ``pool4``: block averages; ``deconv``: the PERIODIC convolution with ``--psf``, by the
-    apply kernel - the boundary the guidance assumes) and the noise from a generator seeded with
+    apply kernel - the boundary the guidance assumes; ``sr2`` / ``sr4``: that convolution (``--psf``, default ``bicubic``) sampled at
+    every 2nd / 4th pixel, the measurement at low resolution) and the noise from a generator seeded with
     ``evaluation.seed`` + rank - and restored from ``prior_sampling`` by the sampler ``evaluation.sampler.name`` running the
     unconditional network under ``PosteriorScoreFn``.  Writes images/ (the restorations), corrupt/ (the measurement shown at
-    image scale, ``A^T y``; for ``deconv`` the blurred image ``y`` itself) and batch/ (the originals) like ``inpaint``;
+    image scale, ``A^T y``; for ``deconv`` the blurred image ``y`` itself, for ``sr2`` / ``sr4`` ``y`` replicated ``s x s``) and batch/ (the originals) like ``inpaint``;
     ``evaluation.restore.prior_var=V`` sets the pixel prior's variance."""
     from psld_amd import config as C, ops
     from psld_amd.ddp import init_distributed, shard_range
-    from psld_amd.guidance import apply_adjoint, apply_operator, check_task, parse_psf
+    from psld_amd.guidance import OPERATORS, SR, apply_adjoint, apply_operator, check_task, parse_psf, sr_kernel
     from psld_amd.registry import get_module
     import torch.distributed as dist
     rank, local, world = init_distributed()
@@ -550,7 +552,9 @@ def restore(args, overrides):
     psf = ev.restore.get("psf", None)
     try:
         check_task(args.task, psf)
-        if psf is not None:
+        if OPERATORS[args.task][0] == SR:
+            sr_kernel(psf, OPERATORS[args.task][1], cfg.data.image_size, cfg.data.image_size)
+        elif psf is not None:
             parse_psf(psf, cfg.data.image_size, cfg.data.image_size)
     except ValueError as e:
         raise SystemExit(str(e))
@@ -597,7 +601,11 @@ def restore(args, overrides):
         _save_u8(os.path.join(dirs["images"], name), u8.cpu().numpy(), ev.save_mode)
         to01 = lambda t: (t * 0.5 + 0.5) if cfg.data.norm else t
         to_u8 = lambda t: (t.clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
-        shown = to01(y if args.task == "deconv" else apply_adjoint(y, args.task, mask))
+        if OPERATORS[args.task][0] == SR:
+            factor = OPERATORS[args.task][1]
+            shown = to01(y.repeat_interleave(factor, dim=2).repeat_interleave(factor, dim=3))
+        else:
+            shown = to01(y if args.task == "deconv" else apply_adjoint(y, args.task, mask))
         _save_u8(os.path.join(dirs["corrupt"], name), to_u8(shown * mask if mask is not None else shown), ev.save_mode)
         _save_u8(os.path.join(dirs["batch"], name), to_u8(to01(x0)), ev.save_mode)
         if momentum:
@@ -723,14 +731,19 @@ def build_parser() -> argparse.ArgumentParser:
                            help="classifier-free guidance scale (evaluation.cfg_scale, default 1.0 = plain conditional "
                                 "sampling; 0 = unconditional; other values run the doubled batch)")
         if name == "restore":
-            p.add_argument("--task", required=True, choices=["mask", "gray", "pool2", "pool4", "deconv"],
+            p.add_argument("--task", required=True, choices=["mask", "gray", "pool2", "pool4", "deconv", "sr2", "sr4"],
                            help="the degradation A: mask (the pixels where --mask is 1), gray ((R + G + B) / sqrt 3), "
                                 "pool2 / pool4 (2x2 / 4x4 block averages), each with orthonormal rows; deconv (the periodic "
-                                "convolution with --psf: deblurring; image sides powers of two from 4 to 128)")
+                                "convolution with --psf: deblurring; image sides powers of two from 4 to 128); sr2 / sr4 "
+                                "(super-resolution: that periodic convolution followed by keeping every 2nd / 4th sample, the "
+                                "measurement at low resolution and image intensity; image sides powers of two from 8 / 16 to 128)")
             p.add_argument("--psf", default=None, metavar="PSF",
-                           help="deconv only (and required there; evaluation.restore.psf): gauss:S (standard deviation S "
-                                "pixels), box:K (K x K, K odd), motion:L (1 x L horizontal, L odd) or a float [kh, kw] .npy "
-                                "file with odd sizes, used as given; the same PSF for every image and channel, periodic boundary")
+                           help="deconv (required there) and sr2 / sr4 (optional, default bicubic; evaluation.restore.psf): gauss:S "
+                                "(standard deviation S pixels), box:K (K x K, K odd), motion:L (1 x L horizontal, L odd) or a float "
+                                "[kh, kw] .npy file with odd sizes, used as given; the same PSF for every image and channel, periodic "
+                                "boundary.  sr2 / sr4 also take bicubic (the anti-aliased Keys cubic, a = -0.5, 4 s taps per axis) and "
+                                "block (the s x s block mean), both centred on the block; the other forms sample the blurred image "
+                                "at the top-left pixel of each block")
             p.add_argument("--sigma-y", type=float, default=0.0, metavar="S",
                            help="standard deviation of the measurement noise, in network-input units (added here, seeded)")
             p.add_argument("--guidance-scale", type=float, default=1.0, metavar="G",

@@ -8,6 +8,15 @@
 //   spectrum:  y^ = FFT2(y), the Hermitian half [H][W/2 + 1] in float64 - once per measurement;
 //   apply:     A x = IFFT2(h^ x^) or A^T x = IFFT2(conj(h^) x^) - setting a problem up.
 //
+// And two more for super-resolution, A = D_s C_k: that blur followed by keeping the samples (s i, s j), s = 2 or 4 (DESIGN section
+// 13, "Super-resolution").  A A^T is circulant on the H/s x W/s grid with eigenvalues Lambda (host float64), so the measure
+// step is three transform pairs in the SAME plane storage - the low-resolution plane is compacted into the full one's place
+// and expanded again (deconv_core.h, dc_sr_*) - and the apply kernel maps between the two resolutions:
+//
+//   sr measure: z = IFFT2(h^ FFT2 x0^), rho = y - D_s z, v = IFFT2'((sigma_y^2 + r_t^2) / (sigma_y^2 + r_t^2 Lambda) FFT2' rho),
+//               g = IFFT2(conj(h^) FFT2(D_s^T v)), cotangent q_e g;
+//   sr apply:   A x [H/s][W/s] = D_s IFFT2(h^ x^), or A^T r [H][W] = IFFT2(conj(h^) FFT2(D_s^T r)).
+//
 // float32 planes in memory; float64 in registers and LDS (towards sigma_y -> 0 the weight reaches 1 / |h^|, 1e4 and more for
 // a Gaussian PSF: a float32 transform's rounding times that weight would leave the 1e-4 gate), float64 h^ and y^ in memory.
 // LDS: H (W/2 + 1) + max(H, W) / 2 complex float64 - 131 KiB at 128 x 128, of a CU's 160 KiB; nothing beyond LDS.
@@ -149,6 +158,133 @@ __global__ __launch_bounds__(DC_THREADS) void restore_deconv_plane_kernel(const 
     }
 }
 
+// ---- super-resolution ("Super-resolution"): A = D_s C_k, y at H/s x W/s ---------------------------------------
+// 4 low-resolution samples (i, col .. col + 3) of one float32 plane with rows of wl elements
+template <bool V16>
+struct sr_load4 {
+    const float* p;
+    int wl;
+    __device__ __forceinline__ void operator()(int i, int col, double (&v)[4]) const { dc_read4<V16>(p + (long long)i * wl + col, v); }
+};
+template <bool V16>
+struct sr_store4 {
+    float* p;
+    int wl;
+    __device__ __forceinline__ void operator()(int i, int col, const double (&v)[4]) const { dc_write4<V16>(p + (long long)i * wl + col, v); }
+};
+
+// the measure step: three transform pairs on the one plane storage (deconv_core.h)
+template <bool AUG, bool V16>
+__global__ __launch_bounds__(DC_THREADS) void restore_sr_kernel(const float* __restrict__ u, const float* __restrict__ eps,
+                                                                 const float* __restrict__ y, const dc2* __restrict__ hhat,
+                                                                 const double* __restrict__ lam, const psld_restore_coeffs_t q,
+                                                                 double s2, double r2, int planes, int c, dc_geom g, int s, int lgs,
+                                                                 float* __restrict__ gout, float* __restrict__ cot) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dc_lds_raw[];
+    dc2* z = reinterpret_cast<dc2*>(dc_lds_raw);
+    dc2* tw = z + dc_plane_elems(g);
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const dc_geom gl = dc_sr_low(g, s, lgs);
+    const long long hw = (long long)g.h * 2 * g.m, hwl = (long long)gl.h * 2 * gl.m;
+    const double inv = 1.0 / (double)(g.h * g.m), invl = 1.0 / (double)(gl.h * gl.m);
+    dc_twiddles(tw, g, tid, nthr);
+    for (int pl = blockIdx.x; pl < planes; pl += gridDim.x) {
+        const int b = pl / c, ch = pl - b * c;
+        const long long ox = ((long long)(AUG ? b * 2 * c + ch : pl)) * hw, om = ox + (long long)c * hw, og = (long long)pl * hw;
+        DC_FOR(i, (int)(hw / 4)) {
+            double ux[4], ex[4], x0[4];
+            dc_read4<V16>(u + ox + 4 * i, ux);
+            dc_read4<V16>(eps + ox + 4 * i, ex);
+            if constexpr (AUG) {
+                double um[4], em[4];
+                dc_read4<V16>(u + om + 4 * i, um);
+                dc_read4<V16>(eps + om + 4 * i, em);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x0[e] = ((q.q_u[0] * ux[e] + q.q_u[1] * um[e]) - q.q_e[0] * ex[e]) - q.q_e[1] * em[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x0[e] = q.q_u[0] * ux[e] - q.q_e[0] * ex[e];
+            }
+            const int at = dc_lds_at(g, i);
+            z[at] = dc_make(x0[0], x0[1]);
+            z[at + 1] = dc_make(x0[2], x0[3]);
+        }
+        __syncthreads();
+        // z = k (*) x0^
+        dc_forward(z, tw, g, tid, nthr);
+        dc_filter<false>(z, tw, g, dc_apply_filter{hhat, false}, nullptr, tid, nthr);
+        dc_inverse(z, tw, g, tid, nthr);
+        // rho = y - D_s z, then v = (s2 + r2) (s2 I + r2 A A^T)^-1 rho on the low-resolution grid
+        dc_sr_residual(z, g, gl, s, inv, sr_load4<V16>{y + (long long)pl * hwl, 2 * gl.m}, tid, nthr);
+        dc_forward(z, tw, gl, tid, nthr);
+        dc_filter<false>(z, tw, gl, dc_sr_solve_filter{lam, s2, r2}, nullptr, tid, nthr);
+        dc_inverse(z, tw, gl, tid, nthr);
+        // g = A^T v = conj(k) (*) D_s^T v
+        dc_sr_zero_insert(z, g, gl, s, invl, tid, nthr);
+        dc_forward(z, tw, g, tid, nthr);
+        dc_filter<false>(z, tw, g, dc_apply_filter{hhat, true}, nullptr, tid, nthr);
+        dc_inverse(z, tw, g, tid, nthr);
+        DC_FOR(i, (int)(hw / 4)) {
+            const int at = dc_lds_at(g, i);
+            const dc2 a = z[at], d = z[at + 1];
+            const double gv[4] = {a.x * inv, a.y * inv, d.x * inv, d.y * inv};
+            double w[4];
+            dc_write4<V16>(gout + og + 4 * i, gv);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[e] = q.q_e[0] * gv[e];
+            dc_write4<V16>(cot + ox + 4 * i, w);
+            if constexpr (AUG) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w[e] = q.q_e[1] * gv[e];
+                dc_write4<V16>(cot + om + 4 * i, w);
+            }
+        }
+        __syncthreads();  // the next plane overwrites z
+    }
+}
+
+// ADJ false: out [planes][h/s][w/s] = A x of x [planes][h][w]; true: out [planes][h][w] = A^T x of x [planes][h/s][w/s]
+template <bool ADJ, bool V16>
+__global__ __launch_bounds__(DC_THREADS) void restore_sr_apply_kernel(const float* __restrict__ x, const dc2* __restrict__ hhat,
+                                                                       int planes, dc_geom g, int s, int lgs, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dc_lds_raw[];
+    dc2* z = reinterpret_cast<dc2*>(dc_lds_raw);
+    dc2* tw = z + dc_plane_elems(g);
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const dc_geom gl = dc_sr_low(g, s, lgs);
+    const long long hw = (long long)g.h * 2 * g.m, hwl = (long long)gl.h * 2 * gl.m;
+    const double inv = 1.0 / (double)(g.h * g.m);
+    dc_twiddles(tw, g, tid, nthr);
+    for (int pl = blockIdx.x; pl < planes; pl += gridDim.x) {
+        if constexpr (ADJ) {
+            dc_sr_spread(z, g, gl, s, sr_load4<V16>{x + (long long)pl * hwl, 2 * gl.m}, tid, nthr);
+        } else {
+            DC_FOR(i, (int)(hw / 4)) {
+                double v[4];
+                dc_read4<V16>(x + (long long)pl * hw + 4 * i, v);
+                const int at = dc_lds_at(g, i);
+                z[at] = dc_make(v[0], v[1]);
+                z[at + 1] = dc_make(v[2], v[3]);
+            }
+            __syncthreads();
+        }
+        dc_forward(z, tw, g, tid, nthr);
+        dc_filter<false>(z, tw, g, dc_apply_filter{hhat, ADJ}, nullptr, tid, nthr);
+        dc_inverse(z, tw, g, tid, nthr);
+        if constexpr (ADJ) {
+            DC_FOR(i, (int)(hw / 4)) {
+                const int at = dc_lds_at(g, i);
+                const dc2 a = z[at], d = z[at + 1];
+                const double v[4] = {a.x * inv, a.y * inv, d.x * inv, d.y * inv};
+                dc_write4<V16>(out + (long long)pl * hw + 4 * i, v);
+            }
+            __syncthreads();
+        } else {
+            dc_sr_decimate(z, g, gl, s, inv, sr_store4<V16>{out + (long long)pl * hwl, 2 * gl.m}, tid, nthr);
+        }
+    }
+}
+
 inline int dc_log2(int n) {
     int l = 0;
     while ((1 << l) < n) ++l;
@@ -237,6 +373,66 @@ extern "C" int psld_restore_deconv_apply_f32(const float* x, const double* hhat,
     else
         rc = v16 ? dc_launch<&restore_deconv_plane_kernel<0, true>>(name, planes, geo, stream, x, hh, planes, geo, out, (dc2*)nullptr)
                  : dc_launch<&restore_deconv_plane_kernel<0, false>>(name, planes, geo, stream, x, hh, planes, geo, out, (dc2*)nullptr);
+    if (rc) return rc;
+    PSLD_CHECK_LAUNCH(name);
+    return PSLD_OK;
+}
+
+extern "C" int psld_restore_sr_supported(int h, int w, int s) {
+    return (s == 2 || s == 4) && dc_size_ok(h) && dc_size_ok(w) && h / s >= DC_MIN && w / s >= DC_MIN ? 1 : 0;
+}
+
+extern "C" int psld_restore_sr_f32(const float* u, const float* eps, const float* y, const double* hhat, const double* lam,
+                                   const psld_restore_coeffs_t* q, double sigma_y2, double r2, int batch, int c, int h, int w,
+                                   int s, float* g, float* cot, hipStream_t stream) {
+    PSLD_CHECK_ARG(u && eps && y && hhat && lam && q && g && cot && batch > 0 && c > 0, "psld_restore_sr_f32: bad args");
+    PSLD_CHECK_ARG(psld_restore_sr_supported(h, w, s),
+                   "psld_restore_sr_f32: map %d x %d, factor %d: the factor must be 2 or 4 and each side a power of two from %d to %d",
+                   h, w, s, DC_MIN * (s > 0 ? s : 1), DC_MAX);
+    PSLD_CHECK_ARG(q->augmented == 0 || q->augmented == 1, "psld_restore_sr_f32: augmented %d not 0 / 1", q->augmented);
+    PSLD_CHECK_ARG(sigma_y2 >= 0.0 && r2 >= 0.0 && sigma_y2 + r2 > 0.0 && sigma_y2 + r2 < HUGE_VAL,
+                   "psld_restore_sr_f32: sigma_y^2 = %g, r_t^2 = %g: both must be >= 0 with a positive finite sum", sigma_y2, r2);
+    PSLD_CHECK_ARG((long long)batch * c <= 0x7fffffffLL / 2, "psld_restore_sr_f32: %lld planes are too many", (long long)batch * c);
+    PSLD_CHECK_ARG((uintptr_t)hhat % 16 == 0 && (uintptr_t)lam % 8 == 0,
+                   "psld_restore_sr_f32: hhat must be 16-byte aligned and lam 8-byte aligned");
+    const dc_geom geo = dc_geometry(h, w, dc_log2(h), dc_log2(w));
+    const int planes = batch * c, lgs = dc_log2(s);
+    const bool v16 = ((uintptr_t)u | (uintptr_t)eps | (uintptr_t)y | (uintptr_t)g | (uintptr_t)cot) % 16 == 0;
+    const dc2* hh = reinterpret_cast<const dc2*>(hhat);
+    const char* name = "psld_restore_sr_f32";
+    int rc;
+    if (q->augmented) {
+        rc = v16 ? dc_launch<&restore_sr_kernel<true, true>>(name, planes, geo, stream, u, eps, y, hh, lam, *q, sigma_y2, r2, planes, c, geo, s, lgs, g, cot)
+                 : dc_launch<&restore_sr_kernel<true, false>>(name, planes, geo, stream, u, eps, y, hh, lam, *q, sigma_y2, r2, planes, c, geo, s, lgs, g, cot);
+    } else {
+        rc = v16 ? dc_launch<&restore_sr_kernel<false, true>>(name, planes, geo, stream, u, eps, y, hh, lam, *q, sigma_y2, r2, planes, c, geo, s, lgs, g, cot)
+                 : dc_launch<&restore_sr_kernel<false, false>>(name, planes, geo, stream, u, eps, y, hh, lam, *q, sigma_y2, r2, planes, c, geo, s, lgs, g, cot);
+    }
+    if (rc) return rc;
+    PSLD_CHECK_LAUNCH(name);
+    return PSLD_OK;
+}
+
+extern "C" int psld_restore_sr_apply_f32(const float* x, const double* hhat, int adjoint, int planes, int h, int w, int s,
+                                         float* out, hipStream_t stream) {
+    PSLD_CHECK_ARG(x && hhat && out && planes > 0 && planes <= 0x7fffffff / 2, "psld_restore_sr_apply_f32: bad args");
+    PSLD_CHECK_ARG(adjoint == 0 || adjoint == 1, "psld_restore_sr_apply_f32: adjoint %d not 0 / 1", adjoint);
+    PSLD_CHECK_ARG(psld_restore_sr_supported(h, w, s),
+                   "psld_restore_sr_apply_f32: map %d x %d, factor %d: the factor must be 2 or 4 and each side a power of two from %d to %d",
+                   h, w, s, DC_MIN * (s > 0 ? s : 1), DC_MAX);
+    PSLD_CHECK_ARG((uintptr_t)hhat % 16 == 0, "psld_restore_sr_apply_f32: hhat must be 16-byte aligned");
+    const dc_geom geo = dc_geometry(h, w, dc_log2(h), dc_log2(w));
+    const int lgs = dc_log2(s);
+    const char* name = "psld_restore_sr_apply_f32";
+    const dc2* hh = reinterpret_cast<const dc2*>(hhat);
+    const bool v16 = ((uintptr_t)x | (uintptr_t)out) % 16 == 0;
+    int rc;
+    if (adjoint)
+        rc = v16 ? dc_launch<&restore_sr_apply_kernel<true, true>>(name, planes, geo, stream, x, hh, planes, geo, s, lgs, out)
+                 : dc_launch<&restore_sr_apply_kernel<true, false>>(name, planes, geo, stream, x, hh, planes, geo, s, lgs, out);
+    else
+        rc = v16 ? dc_launch<&restore_sr_apply_kernel<false, true>>(name, planes, geo, stream, x, hh, planes, geo, s, lgs, out)
+                 : dc_launch<&restore_sr_apply_kernel<false, false>>(name, planes, geo, stream, x, hh, planes, geo, s, lgs, out);
     if (rc) return rc;
     PSLD_CHECK_LAUNCH(name);
     return PSLD_OK;

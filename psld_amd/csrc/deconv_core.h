@@ -205,3 +205,112 @@ DC_HD void dc_filter(dc2* z, const dc2* tw, const dc_geom& g, const F& f, dc2* s
     }
     DC_SYNC();
 }
+
+// ---- super-resolution: A = D_s C_k, a periodic blur followed by keeping every s-th sample ("Super-resolution") ---
+// A A^T is circulant on the H/s x W/s grid with eigenvalues Lambda, so the measure step is three transform pairs on ONE
+// plane storage: z = k (*) x0^ at full size, rho = y - D_s z compacted IN PLACE into the packed low-resolution plane,
+// v = IFFT2'((s2 + r2) / (s2 + r2 Lambda) FFT2' rho), D_s^T v expanded in place, g = IFFT2(conj(h^) FFT2(D_s^T v)).
+// The low-resolution geometry keeps the full plane's n, so the one twiddle table serves both.
+DC_HD dc_geom dc_sr_low(const dc_geom& g, int s, int lgs) {
+    dc_geom l;
+    l.h = g.h / s; l.m = g.m / s; l.lgh = g.lgh - lgs; l.lgm = g.lgm - lgs; l.p = l.m + 1; l.n = g.n;
+    return l;
+}
+
+// v^ = (s2 + r2) / (s2 + r2 Lambda) rho^ on the low-resolution half spectrum [H/s][W/(2s) + 1]; denominator 0: 0
+struct dc_sr_solve_filter {
+    const double* lam;
+    double s2, r2;
+    DC_HD dc2 operator()(int idx, dc2 x) const {
+        const double den = s2 + r2 * lam[idx];
+        if (den == 0.0) return dc_make(0.0, 0.0);
+        return dc_scale(x, (s2 + r2) / den);
+    }
+};
+
+// An item is two neighbouring elements of the packed low-resolution plane: 4 real samples (i, 4 jj .. 4 jj + 3), which lie
+// at the full plane's (s i, s (4 jj + e)): row s i, packed column (s / 2) (4 jj + e), real part.  Item `it` lives at low
+// elements i p' + 2 jj (+ 1) and reads full elements >= s i p + 2 s jj >= i p' + 2 jj: no item reads below its own place,
+// and the places rise with `it`.  So rounds of nthr items in rising order - read, barrier, write - never overwrite what a
+// later round reads; the expansion runs the rounds in falling order by the same argument.
+
+// rho = y - inv * (unscaled z)[s i][s j], compacted: on return z holds the packed low-resolution plane of geometry gl.
+// y(i, col, v): the 4 measurement samples (i, col .. col + 3) of this plane.
+template <class Y>
+DC_HD void dc_sr_residual(dc2* z, const dc_geom& g, const dc_geom& gl, int s, double inv, const Y& y, int tid, int nthr) {
+    const int per = gl.m >> 1, lgper = gl.lgm - 1, items = gl.h * per, hs = s >> 1;
+    for (int base = 0; base < items; base += nthr) {
+        const int it = base + tid;
+        const bool on = it < items;
+        double rho[4] = {0.0, 0.0, 0.0, 0.0};
+        int at = 0;
+        if (on) {
+            const int i = it >> lgper, jj = it & (per - 1);
+            y(i, 4 * jj, rho);
+            const dc2* row = z + (s * i) * g.p + hs * 4 * jj;
+            for (int e = 0; e < 4; ++e) rho[e] -= row[hs * e].x * inv;
+            at = i * gl.p + 2 * jj;
+        }
+        DC_SYNC();
+        if (on) {
+            z[at] = dc_make(rho[0], rho[1]);
+            z[at + 1] = dc_make(rho[2], rho[3]);
+        }
+    }
+    DC_SYNC();
+}
+
+// the reverse: z holds the (unscaled) packed low-resolution plane v; on return the packed full plane D_s^T (inv * v)
+DC_HD void dc_sr_zero_insert(dc2* z, const dc_geom& g, const dc_geom& gl, int s, double inv, int tid, int nthr) {
+    const int per = gl.m >> 1, lgper = gl.lgm - 1, items = gl.h * per, hs = s >> 1;
+    for (int base = ((items - 1) / nthr) * nthr; base >= 0; base -= nthr) {
+        const int it = base + tid;
+        const bool on = it < items;
+        const int i = it >> lgper, jj = it & (per - 1);
+        dc2 a = dc_make(0.0, 0.0), b = a;
+        if (on) {
+            a = z[i * gl.p + 2 * jj];
+            b = z[i * gl.p + 2 * jj + 1];
+        }
+        DC_SYNC();
+        if (on) {
+            // the item's block of the full plane: s rows x 2 s packed columns; the blocks tile the plane
+            const double v[4] = {a.x * inv, a.y * inv, b.x * inv, b.y * inv};
+            dc2* blk = z + (s * i) * g.p + 2 * s * jj;
+            for (int r = 0; r < s; ++r)
+                for (int c = 0; c < 2 * s; ++c)
+                    blk[r * g.p + c] = dc_make(r == 0 && (c & (hs - 1)) == 0 ? v[c / hs] : 0.0, 0.0);
+        }
+    }
+    DC_SYNC();
+}
+
+// A x: the (unscaled) blurred plane in z, decimated; out(i, col, v) takes the 4 low-resolution samples (i, col .. col + 3)
+template <class O>
+DC_HD void dc_sr_decimate(const dc2* z, const dc_geom& g, const dc_geom& gl, int s, double inv, const O& out, int tid, int nthr) {
+    const int per = gl.m >> 1, lgper = gl.lgm - 1, hs = s >> 1;
+    DC_FOR(it, gl.h * per) {
+        const int i = it >> lgper, jj = it & (per - 1);
+        const dc2* row = z + (s * i) * g.p + hs * 4 * jj;
+        double v[4];
+        for (int e = 0; e < 4; ++e) v[e] = row[hs * e].x * inv;
+        out(i, 4 * jj, v);
+    }
+    DC_SYNC();
+}
+
+// D_s^T r straight from memory: in(i, col, v) hands the 4 low-resolution samples (i, col .. col + 3)
+template <class I>
+DC_HD void dc_sr_spread(dc2* z, const dc_geom& g, const dc_geom& gl, int s, const I& in, int tid, int nthr) {
+    const int per = gl.m >> 1, lgper = gl.lgm - 1, hs = s >> 1;
+    DC_FOR(it, gl.h * per) {
+        const int i = it >> lgper, jj = it & (per - 1);
+        double v[4];
+        in(i, 4 * jj, v);
+        dc2* blk = z + (s * i) * g.p + 2 * s * jj;
+        for (int r = 0; r < s; ++r)
+            for (int c = 0; c < 2 * s; ++c)
+                blk[r * g.p + c] = dc_make(r == 0 && (c & (hs - 1)) == 0 ? v[c / hs] : 0.0, 0.0);
+    }
+    DC_SYNC();
+}

@@ -77,19 +77,25 @@ class CFGScoreFn:
 # ---- measurement guidance -----------------------------------------------------------------------------
 # task -> (operator code, block size); mask, gray and pool have orthonormal rows (A A^T = I on their range) and share
 # ops.restore_measure; deconv (a periodic blur, DESIGN section 13, "Deconvolution") has not, and has kernels of its own:
-# DECONV is a host-side tag that is never handed to the library (whose operator code 3 stays refused)
+# DECONV is a host-side tag that is never handed to the library (whose operator code 3 stays refused); so is SR (sr2 / sr4: a
+# periodic blur followed by keeping every 2nd / 4th sample, DESIGN section 13, "Super-resolution")
 DECONV = -1
+SR = -2
 OPERATORS = {"mask": (_lib.RESTORE_MASK, 1), "gray": (_lib.RESTORE_GRAY, 1), "pool2": (_lib.RESTORE_POOL, 2),
-             "pool4": (_lib.RESTORE_POOL, 4), "deconv": (DECONV, 1)}
+             "pool4": (_lib.RESTORE_POOL, 4), "deconv": (DECONV, 1), "sr2": (SR, 2), "sr4": (SR, 4)}
+SR_DEFAULT_PSF = "bicubic"
 
 
 def check_task(task, psf="unchecked") -> str:
-    """The task's name if it is one; with ``psf`` given also: a PSF goes with ``deconv`` and with no other task."""
+    """The task's name if it is one; with ``psf`` given also: a PSF is required with ``deconv``, optional with ``sr2`` / ``sr4``
+    (default ``bicubic``) and refused with every other task."""
     if task not in OPERATORS:
         raise ValueError(f"restore: task must be one of {sorted(OPERATORS)}, got {task!r}")
-    if not (isinstance(psf, str) and psf == "unchecked") and (psf is not None) != (task == "deconv"):
-        raise ValueError("restore: a PSF (gauss:S | box:K | motion:L | file.npy) goes with the task deconv and with no other"
-                         f" (task {task!r}, psf {psf!r})")
+    if (isinstance(psf, str) and psf == "unchecked") or OPERATORS[task][0] == SR:
+        return task
+    if (psf is not None) != (task == "deconv"):
+        raise ValueError("restore: a PSF (gauss:S | box:K | motion:L | file.npy) is required with the task deconv, optional with "
+                         f"sr2 / sr4 (which also take bicubic | block) and goes with no other (task {task!r}, psf {psf!r})")
     return task
 
 
@@ -171,13 +177,95 @@ def _apply_deconv(x: torch.Tensor, psf, adjoint: bool) -> torch.Tensor:
     return torch.fft.irfft2(xf * (hh.conj() if adjoint else hh), s=(h, w)).to(x.dtype)
 
 
+# ---- the super-resolution operator: A x = D_s (k (*) x), (D_s z)[i, j] = z[s i, s j] ----------------------------------------------
+def _cubic(x: np.ndarray) -> np.ndarray:
+    """The Keys cubic with a = -0.5."""
+    x, a = np.abs(x), -0.5
+    return np.where(x <= 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0,
+                    np.where(x < 2.0, ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a, 0.0))
+
+
+def sr_kernel(psf, s: int, h: int, w: int) -> np.ndarray:
+    """The convolution kernel ``k`` of ``A x = D_s (k (*) x)`` on the ``h x w`` torus, float64 ``[h, w]``.  ``psf``: ``bicubic`` (the
+    default, ``None``): the anti-aliased Keys cubic (a = -0.5), per axis the 4 s taps ``w[o] = cubic((o - (s - 1) / 2) / s)`` at
+    offsets ``o = -3 s / 2 .. 5 s / 2 - 1`` from ``s i``, normalised to sum 1 - ``y[i] = sum_o w[o] x[s i + o]``, a correlation, so
+    ``k[-o] = w[o]``; ``block``: the mean of each ``s x s`` block (offsets ``0 .. s - 1``; ``A`` is the ``pool`` operator divided
+    by ``s``); or anything ``parse_psf`` takes, centred on the sampled pixel ``(s i, s j)``.  ``bicubic`` and ``block`` are
+    centred on the block, the others sample the blurred image at the block's top-left pixel."""
+    s, h, w = int(s), int(h), int(w)
+    if s not in (2, 4) or h % s or w % s:
+        raise ValueError(f"restore: super-resolution takes the factors 2 and 4 and a map they divide, got {s} and {h} x {w}")
+    psf = SR_DEFAULT_PSF if psf is None else psf
+    if not (isinstance(psf, str) and psf in ("bicubic", "block")):
+        return parse_psf(psf, h, w)
+    if psf == "bicubic":
+        offs = np.arange(-3 * s // 2, 5 * s // 2)
+        taps = _cubic((offs - (s - 1) / 2.0) / s)
+        taps = taps / taps.sum()
+    else:
+        offs, taps = np.arange(s), np.full(s, 1.0 / s)
+    rows, cols = np.zeros(h), np.zeros(w)
+    np.add.at(rows, (-offs) % h, taps)
+    np.add.at(cols, (-offs) % w, taps)
+    return np.outer(rows, cols)
+
+
+def sr_spectrum(psf, s: int, h: int, w: int):
+    """``(h^, Lambda)`` in host float64: ``h^ = FFT2(sr_kernel(...))`` as the Hermitian half, complex128 ``[h, w/2 + 1]``, and the
+    eigenvalues of ``A A^T`` on the low-resolution grid, ``Lambda[m1, m2] = (1 / s^2) sum_{a, b < s} |h^[m1 + a h/s, m2 + b w/s]|^2``
+    for ``m2 <= w / 2s``: float64 ``[h/s, w/(2s) + 1]`` ("Super-resolution")."""
+    k = sr_kernel(psf, s, h, w)
+    hl, wl = h // s, w // s
+    power = np.abs(np.fft.fft2(k)) ** 2
+    lam = power.reshape(s, hl, s, wl).sum(axis=(0, 2)) / (s * s)
+    return np.fft.rfft2(k), np.ascontiguousarray(lam[:, :wl // 2 + 1])
+
+
+_SR = {}
+
+
+def sr_device_spectra(psf, s: int, h: int, w: int, device):
+    """``sr_spectrum`` as the device tensors the kernels read: ``h^`` float64 ``[h, w/2 + 1, 2]`` and ``Lambda`` float64
+    ``[h/s, w/(2s) + 1]`` (kept per kernel, factor, size, device)."""
+    psf = SR_DEFAULT_PSF if psf is None else psf
+    key = (_psf_key(psf), int(s), int(h), int(w), str(device))
+    if key not in _SR:
+        if len(_SR) > 64:
+            _SR.clear()
+        hh, lam = sr_spectrum(psf, s, h, w)
+        _SR[key] = (torch.from_numpy(np.stack([hh.real, hh.imag], axis=-1).copy()).to(device).contiguous(),
+                    torch.from_numpy(lam).to(device).contiguous())
+    return _SR[key]
+
+
+def _apply_sr(x: torch.Tensor, psf, s: int, adjoint: bool) -> torch.Tensor:
+    """``D_s (k (*) x)`` ``[B, C, H/s, W/s]`` of images (adjoint: ``A^T r`` ``[B, C, H, W]`` of measurements): the apply kernel on
+    device tensors, ``torch.fft`` in float64 on CPU tensors."""
+    if x.dim() != 4:
+        raise ValueError(f"restore: images of shape {tuple(x.shape)} are not [B, C, H, W]")
+    h, w = (x.shape[-2] * s, x.shape[-1] * s) if adjoint else x.shape[-2:]
+    if x.is_cuda:
+        hhat, _ = sr_device_spectra(psf, s, h, w, x.device)
+        return ops.restore_sr_apply(x.detach().to(torch.float32).contiguous(), hhat, s, adjoint).to(x.dtype)
+    hh = torch.from_numpy(sr_spectrum(psf, s, h, w)[0])
+    x64 = x.detach().to(torch.float64)
+    if adjoint:
+        up = torch.zeros(tuple(x.shape[:2]) + (h, w), dtype=torch.float64)
+        up[..., ::s, ::s] = x64
+        return torch.fft.irfft2(torch.fft.rfft2(up) * hh.conj(), s=(h, w)).to(x.dtype)
+    return torch.fft.irfft2(torch.fft.rfft2(x64) * hh, s=(h, w))[..., ::s, ::s].contiguous().to(x.dtype)
+
+
 def apply_operator(x: torch.Tensor, task: str, mask=None, psf=None) -> torch.Tensor:
     """``A x`` of images ``x`` ``[B, C, H, W]`` (setting a problem up; the per-step arithmetic is ``ops.restore_measure`` /
     ``ops.restore_deconv_measure``): mask ``M . x``, gray ``(x_R + x_G + x_B) / sqrt(3)``, pool the block sums over ``k``,
-    deconv the periodic convolution with the PSF ``psf`` (``parse_psf``) - on device tensors by the apply kernel."""
+    deconv the periodic convolution with the PSF ``psf`` (``parse_psf``) - on device tensors by the apply kernel; sr2 / sr4 that
+    convolution with ``sr_kernel(psf, s, H, W)`` sampled at ``(s i, s j)``, ``[B, C, H/s, W/s]`` at image intensity."""
     op, k = OPERATORS[check_task(task, psf)]
     if op == DECONV:
         return _apply_deconv(x, psf, False)
+    if op == SR:
+        return _apply_sr(x, psf, k, False)
     want = ops.restore_measurement_shape(x.shape, op, k, 0)
     if op == _lib.RESTORE_MASK:
         if mask is None or tuple(mask.shape) != want:
@@ -195,6 +283,8 @@ def apply_adjoint(y: torch.Tensor, task: str, mask=None, psf=None) -> torch.Tens
     op, k = OPERATORS[check_task(task, psf)]
     if op == DECONV:
         return _apply_deconv(y, psf, True)
+    if op == SR:
+        return _apply_sr(y, psf, k, True)
     if op == _lib.RESTORE_MASK:
         return y * mask.to(y.dtype)
     if op == _lib.RESTORE_GRAY:
@@ -283,7 +373,13 @@ class PosteriorScoreFn:
     orthonormal, so ``g`` is ``(sigma_y^2 + r_t^2) A^T (sigma_y^2 I + r_t^2 A A^T)^-1 (y - A x0^)``, computed per plane in the
     2-D DFT domain by ``ops.restore_deconv_measure`` from the PSF's spectrum (host float64, held on the device) and the
     measurement's (``ops.restore_deconv_spectrum``, once per measurement, at the first guided call).  The measurement has
-    the image's shape; H and W are powers of two from 4 to 128."""
+    the image's shape; H and W are powers of two from 4 to 128.
+
+    ``operator="sr2" | "sr4"`` ("Super-resolution") is that blur followed by keeping every 2nd / 4th sample,
+    ``A = D_s C_k`` with ``k = sr_kernel(psf, s, H, W)`` (``psf`` optional, default ``bicubic``; also ``block`` and what
+    ``parse_psf`` takes): the measurement is ``[B, C, H/s, W/s]`` at image intensity.  ``A A^T`` is circulant on the
+    low-resolution grid, so the same ``g`` costs three transform pairs per plane (``ops.restore_sr_measure``); H and W are
+    powers of two up to 128 with ``H/s >= 4`` and ``W/s >= 4``."""
 
     def __init__(self, net, sde, operator: str, sigma_y: float, scale: float = 1.0, prior_var: float = 1.0, psf=None):
         if isinstance(net, CFGScoreFn):
@@ -291,9 +387,11 @@ class PosteriorScoreFn:
         self.net, self.sde = net, sde
         self.operator = check_task(operator, psf)
         self.op, self.k = OPERATORS[operator]
-        self.psf = psf
-        if psf is not None:
-            parse_psf(psf, 128, 128)                     # refuses a malformed PSF now; its size is checked against the image's
+        self.psf = SR_DEFAULT_PSF if self.op == SR and psf is None else psf
+        if self.op == SR:
+            sr_kernel(self.psf, self.k, 128, 128)        # refuses a malformed PSF now; its size is checked against the image's
+        elif psf is not None:
+            parse_psf(psf, 128, 128)
         self.yhat = None
         self.sigma_y, self.scale, self.prior_var = float(sigma_y), float(scale), float(prior_var)
         if not math.isfinite(self.scale) or not math.isfinite(self.sigma_y) or self.sigma_y < 0:
@@ -317,7 +415,8 @@ class PosteriorScoreFn:
 
     def set_measurement(self, y: torch.Tensor, mask=None):
         """``y``: the measurement (mask ``[B, C, H, W]``, gray ``[B, 1, H, W]``, pool ``[B, C, H/k, W/k]``), ``mask``: {0, 1}
-        ``[B, C, H, W]``, for the mask operator and no other.  Kept as contiguous float32 device tensors."""
+        ``[B, C, H, W]``, for the mask operator and no other; sr2 / sr4 ``[B, C, H/s, W/s]``.  Kept as contiguous float32 device
+        tensors."""
         if (mask is not None) != (self.op == _lib.RESTORE_MASK):
             raise ValueError("PosteriorScoreFn: a mask goes with the mask operator and with no other")
         if y.dim() != 4:
@@ -355,6 +454,16 @@ class PosteriorScoreFn:
             if self.yhat is None:
                 self.yhat = ops.restore_deconv_spectrum(self.y)
             return self.yhat, hhat
+        if self.op == SR:
+            b, c, h, w = ops.restore_measurement_shape(x32.shape, _lib.RESTORE_MASK, 1, augmented)
+            if not x32.is_cuda or not ops.restore_sr_supported(h, w, self.k):
+                raise ValueError(f"PosteriorScoreFn: the operator {self.operator} needs device tensors and a map whose sides are "
+                                 f"powers of two from {4 * self.k} to 128, got {h} x {w} on {x32.device}")
+            want = (b, c, h // self.k, w // self.k)
+            if tuple(self.y.shape) != want or self.y.device != x32.device:
+                raise ValueError(f"PosteriorScoreFn: measurement of shape {tuple(self.y.shape)} on {self.y.device}, the operator "
+                                 f"{self.operator} and a state of shape {tuple(x32.shape)} on {x32.device} need {want}")
+            return self.y, sr_device_spectra(self.psf, self.k, h, w, x32.device)
         want = ops.restore_measurement_shape(x32.shape, self.op, self.k, augmented)
         if tuple(self.y.shape) != want or self.y.device != x32.device:
             raise ValueError(f"PosteriorScoreFn: measurement of shape {tuple(self.y.shape)} on {self.y.device}, the operator "
@@ -394,6 +503,8 @@ class PosteriorScoreFn:
             q = self.coeffs(read_time())
             if self.op == DECONV:                           # (y, mask) are (the measurement's spectrum, the PSF's)
                 g, w = ops.restore_deconv_measure(x32, out, y, mask, q, q.sigma_y2, q.r2)
+            elif self.op == SR:                             # (y, mask) are (the measurement, (the kernel's spectrum, Lambda))
+                g, w = ops.restore_sr_measure(x32, out, y, mask[0], mask[1], q, q.sigma_y2, q.r2, self.k)
             else:
                 g, w = ops.restore_measure(x32, out, y, mask, self.op, self.k, q)
             kept.extend((g, q))

@@ -1830,6 +1830,77 @@ def restore_deconv_apply(x: Tensor, hhat: Tensor, adjoint: bool = False, out: Op
     return out
 
 
+def restore_sr_supported(h: int, w: int, s: int) -> bool:
+    """Whether the super-resolution kernels take ``h x w`` planes at factor ``s`` (psld_restore_sr_supported: ``s`` 2 or 4, each
+    side a power of two up to 128 with ``h / s >= 4`` and ``w / s >= 4``)."""
+    return bool(lib().psld_restore_sr_supported(int(h), int(w), int(s)))
+
+
+def _sr_check(h: int, w: int, s: int, hhat: Tensor, device, what: str):
+    if not restore_sr_supported(h, w, s):
+        raise ValueError(f"{what}: a {h} x {w} map at factor {s}: the factor must be 2 or 4 and each side a power of two from "
+                         f"{4 * s if s in (2, 4) else 8} to 128")
+    if tuple(_chk(hhat, torch.float64).shape) != (h, w // 2 + 1, 2) or hhat.device != device:
+        raise ValueError(f"{what}: PSF spectrum of shape {tuple(hhat.shape)} on {hhat.device}, {h} x {w} planes on {device} "
+                         f"need {(h, w // 2 + 1, 2)}")
+    if hhat.data_ptr() % 16:
+        raise ValueError(f"{what}: the PSF spectrum must be 16-byte aligned")
+
+
+def restore_sr_measure(u: Tensor, eps: Tensor, y: Tensor, hhat: Tensor, lam: Tensor, q: RestoreCoeffs, sigma_y2: float,
+                       r2: float, s: int):
+    """``(g, w)`` of one guided call under the super-resolution operator ``A = D_s C_k`` (psld_restore_sr_f32; DESIGN section 13,
+    "Super-resolution"): ``g = (sigma_y2 + r2) A^T (sigma_y2 I + r2 A A^T)^-1 (y - A x0^)`` ``[B, C, H, W]`` and the cotangent
+    ``(q_e[0] g | q_e[1] g)`` of the state's shape.  ``y``: the float32 measurement ``[B, C, H/s, W/s]``; ``hhat``: float64
+    ``[H, W/2 + 1, 2]``, the kernel's spectrum; ``lam``: float64 ``[H/s, W/(2s) + 1]``, the eigenvalues of ``A A^T``."""
+    if tuple(_chk(eps).shape) != tuple(_chk(u).shape) or u.dim() != 4:
+        raise ValueError(f"restore_sr_measure: eps of shape {tuple(eps.shape)} for a state of shape {tuple(u.shape)}")
+    if q.augmented not in (0, 1):
+        raise ValueError(f"restore_sr_measure: augmented must be 0 or 1, got {q.augmented}")
+    b, ct, h, w = u.shape
+    if q.augmented and ct % 2:
+        raise ValueError(f"restore_sr_measure: an augmented state needs an even channel count, got {ct}")
+    c, s = ct // 2 if q.augmented else ct, int(s)
+    _sr_check(h, w, s, hhat, u.device, "restore_sr_measure")
+    if tuple(_chk(y).shape) != (b, c, h // s, w // s) or y.device != u.device:
+        raise ValueError(f"restore_sr_measure: measurement of shape {tuple(y.shape)}, this state and factor need "
+                         f"{(b, c, h // s, w // s)}")
+    if tuple(_chk(lam, torch.float64).shape) != (h // s, w // (2 * s) + 1) or lam.device != u.device:
+        raise ValueError(f"restore_sr_measure: eigenvalues of shape {tuple(lam.shape)}, this state and factor need "
+                         f"{(h // s, w // (2 * s) + 1)}")
+    sigma_y2, r2 = float(sigma_y2), float(r2)
+    if not (sigma_y2 >= 0.0 and r2 >= 0.0 and 0.0 < sigma_y2 + r2 < float("inf")):
+        raise ValueError(f"restore_sr_measure: sigma_y^2 = {sigma_y2!r} and r_t^2 = {r2!r} must be >= 0 with a positive sum")
+    g = torch.empty((b, c, h, w), device=u.device, dtype=torch.float32)
+    cot = torch.empty_like(u)
+    check(lib().psld_restore_sr_f32(u.data_ptr(), eps.data_ptr(), y.data_ptr(), hhat.data_ptr(), lam.data_ptr(), C.byref(q),
+                                    sigma_y2, r2, b, c, h, w, s, g.data_ptr(), cot.data_ptr(), _stream()), "psld_restore_sr_f32")
+    return g, cot
+
+
+def restore_sr_apply(x: Tensor, hhat: Tensor, s: int, adjoint: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """``A x`` ``[..., H/s, W/s]`` of float32 planes ``x`` ``[..., H, W]``, or with ``adjoint`` ``A^T x`` ``[..., H, W]`` of planes
+    ``[..., H/s, W/s]``, under ``A = D_s C_k`` with the kernel's spectrum ``hhat`` ``[H, W/2 + 1, 2]`` (psld_restore_sr_apply_f32)."""
+    s = int(s)
+    if _chk(x).dim() < 2 or x.numel() == 0:
+        raise ValueError(f"restore_sr_apply: planes of shape {tuple(x.shape)} are not [..., H, W] with at least one plane")
+    if _chk(hhat, torch.float64).dim() != 3 or hhat.shape[2] != 2:
+        raise ValueError(f"restore_sr_apply: PSF spectrum of shape {tuple(hhat.shape)} is not [H, W/2 + 1, 2]")
+    h, w = int(hhat.shape[0]), 2 * (int(hhat.shape[1]) - 1)
+    _sr_check(h, w, s, hhat, x.device, "restore_sr_apply")
+    src, dst = ((h // s, w // s), (h, w)) if adjoint else ((h, w), (h // s, w // s))
+    if tuple(x.shape[-2:]) != src:
+        raise ValueError(f"restore_sr_apply: planes of shape {tuple(x.shape)}, this spectrum and factor need [..., {src[0]}, {src[1]}]")
+    want = tuple(x.shape[:-2]) + dst
+    if out is None:
+        out = torch.empty(want, device=x.device, dtype=torch.float32)
+    elif tuple(_chk(out).shape) != want:
+        raise ValueError(f"restore_sr_apply: out of shape {tuple(out.shape)}, these planes need {want}")
+    check(lib().psld_restore_sr_apply_f32(x.data_ptr(), hhat.data_ptr(), int(bool(adjoint)), x.numel() // (src[0] * src[1]), h, w,
+                                          s, out.data_ptr(), _stream()), "psld_restore_sr_apply_f32")
+    return out
+
+
 def samples_to_uint8(samples: Tensor, is_augmented: bool = True, denorm: bool = True) -> Tensor:
     """[B,2C,H,W] f64 sampler output -> uint8 [B,H,W,C] ready for the PNG encoder (SimpleImageWriter,
     callbacks.py:88-124): 16x less device->host traffic than copying the f64 state."""

@@ -93,7 +93,7 @@ class SDEWrapper(_Base):
         """The network the sampler calls: ``net`` itself; for a label-conditioned network with
         ``evaluation.label_to_sample`` set its classifier-free-guidance front (``evaluation.cfg_scale``, default 1); with
         ``evaluation.restore.task`` set its measurement-guidance front (``psld_amd.guidance.PosteriorScoreFn``:
-        ``evaluation.restore.sigma_y`` / ``.scale`` / ``.prior_var``, and ``.psf`` for the task ``deconv``), whose measurement
+        ``evaluation.restore.sigma_y`` / ``.scale`` / ``.prior_var``, and ``.psf`` for the tasks ``deconv``, ``sr2``, ``sr4``), whose measurement
         the caller sets per batch."""
         ev = self.config.evaluation
         restore = ev.get("restore", None)
